@@ -7,7 +7,10 @@ BASELINE workload: n=1024 spins, K=1e6 samples (block-Ising, 64 blocks x 16 spin
 the device by the library's exact block sampler (no host sample matrix).  Inputs (packed spins,
 weights, and the parameters Theta) are resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs writes f and the gradient of the last timed pass to DIR as float64 .npy files (dump_outputs()); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 With N > 1 and no WORLD_SIZE in the environment this process only launches
 `python -m torch.distributed.run --nproc-per-node N ... bench.py` (before anything touches a GPU) and
@@ -82,6 +85,8 @@ def parse_args():
     ap.add_argument("--cpu-learn-full", action="store_true", help="run the CPU learn() of THIS config in full instead of extrapolating")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: only the rank launch, node partition and rendezvous "
                                                             "(gloo); used by the CPU test of the N > 1 launch path")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write f and the gradient of the last timed pass (all nodes) to DIR/*.npy "
+                                                          "so that two builds can be compared output for output")
     return ap.parse_args()
 
 
@@ -107,6 +112,26 @@ def launch_ranks(args):
     if line:
         print(line)
     sys.exit(r.returncode if r.returncode else (0 if line else 1))
+
+
+DUMP_LIMIT = 64 * 10**6  # bytes of array data --dump-outputs writes at most
+
+
+def dump_outputs(out_dir, f, g):
+    """f (n,) and the gradient (n, P) of the last timed pass as DIR/f.npy and DIR/grad.npy, float64.  A gradient over the
+    size limit is cut to a fixed, seeded sample of its rows, whose indices go to DIR/grad_rows.npy.  Returns the names."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"f": f, "grad": g}
+    rows_cap = (DUMP_LIMIT - f.nbytes) // (8 * (g.shape[1] + 1))
+    if g.shape[0] > rows_cap:
+        rows = np.sort(np.random.default_rng(0).choice(g.shape[0], size=rows_cap, replace=False))
+        arrays.update(grad=g[rows], grad_rows=rows)
+    elif os.path.exists(os.path.join(out_dir, "grad_rows.npy")):
+        os.remove(os.path.join(out_dir, "grad_rows.npy"))  # (left by an earlier, larger run: it would mislabel this grad.npy)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def pass_roofline(km, K, P, nloc, precision):
@@ -283,6 +308,16 @@ def main():
     extra = {"per_rank_ms_per_step": [e / args.steps * 1e3 for e in per_rank],
              # spread of the timed passes on this rank (HIP events around every pass, device time)
              "step_ms_min": float(step[0]), "step_ms_median": float(np.median(step)), "step_ms_max": float(step[-1])}
+    if args.dump_outputs:
+        # what the timed path handed back after its last step, every rank's node rows in node order
+        f_all, g_all = f_res, g_res
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, (f_res, g_res))
+            f_all, g_all = np.concatenate([q[0] for q in parts]), np.concatenate([q[1] for q in parts])
+        if rank == 0:
+            extra["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dump_outputs(args.dump_outputs, f_all, g_all)}
+
     def gather_list(x):
         """one float per rank -> list over ranks (rank order)"""
         return max_over_ranks(x)[1]
