@@ -10,12 +10,16 @@
 //   exp         in FP64 (Cody-Waite reduction, 2^(j/64) table, degree-5 polynomial: 1e-16 relative).
 // Results are deterministic and independent of tiling, split-K order and GPU count, like those of the i8x pass.
 //
-// Register budget.  7 planes x 2 sample tiles x 16 accumulators do not fit the 256 registers of a wave at two workgroups per
-// CU, so the forward kernel sweeps the columns TWICE inside one workgroup: sweep A multiplies the planes 0..3 (128
-// accumulators), folds them into 32 FP64 partial energies per lane (64 registers), sweep B multiplies the planes 4..6 (96
-// accumulators).  The LDS-DMA ring runs through both sweeps without a restart; the sample bits are loaded twice (2 KB per step
-// against 8 / 6 KB of digit planes).  V is kept as two halves of 3 planes, V / tau = lo + 2^24 hi: the backward GEMM runs as two
-// launches of the 3-plane form of k_bwd_i8 and every integer sum (per half) stays far inside 64 bits.
+// Register budget.  The full-width forward kernel multiplies all 7 planes in ONE sweep over the columns: 7 planes x 2 sample
+// tiles x 16 accumulators = 224 registers, the 4 of one plane's Theta fragment (read plane by plane, fed to both sample tiles),
+// the 8 of the bit fragments, a handful of offsets: at most 256 at two workgroups per CU.  A ring stage is one 64-column step
+// (2 KB of bits + 14 KB of digit planes, 4 DMA instructions per wave), 4 stages deep; the sample bits are read and expanded once
+// per step.  After the sweep the 7 accumulators of each element are folded into its energy, element by element.  The coarse
+// form sweeps only the top four planes (its own ring, two steps per stage).  -DI8W_TWO_SWEEPS builds the earlier form for A/B
+// runs: sweep A multiplies the planes 3..6 (128 accumulators), folds them into 32 FP64 partial energies per lane (64
+// registers), sweep B multiplies the planes 0..2 (96 accumulators), the sample bits loaded twice.  V is kept as two halves of 3
+// planes, V / tau = lo + 2^24 hi: the backward GEMM runs as two launches of the 3-plane form of k_bwd_i8 and every integer sum
+// (per half) stays far inside 64 bits.
 #include "gml_i8.h"
 #include <string>
 #include <type_traits>
@@ -30,6 +34,22 @@ constexpr int PA = 2 + 2 * LFA, PB = 2 + 2 * LFB; // 1-KB pieces of a 64-column 
 constexpr int STEPW = PA * 1024, DSW = 2, STAGEW = DSW * STEPW, NSW = 3, RINGW = NSW * STAGEW;
 constexpr int NLA = DSW * PA / 4, NLB = DSW * PB / 4; // DMA instructions per wave and stage: 5, 4
 static_assert(NLA == NLB + 1, "issue() drops the last load in sweep B");
+// the single sweep over all 7 planes: one 64-column step per stage, 16 pieces (2 of bits + 14 of digit-plane rows), 4 per wave
+constexpr int P1 = 2 + 2 * LFW, STEP1 = P1 * 1024, NS1 = 4, RING1 = NS1 * STEP1, NL1 = P1 / 4;
+static_assert(P1 % 4 == 0 && NL1 == 4, "one stage: 4 DMA instructions per wave");
+#ifdef I8W_TWO_SWEEPS
+constexpr bool ONE_SWEEP = false;
+#else
+constexpr bool ONE_SWEEP = true;
+#endif
+#if defined(I8W_LINE_STORES) && !defined(I8W_TWO_SWEEPS)
+#error "I8W_LINE_STORES stages through the ring of the two-sweep form: build it with -DI8W_TWO_SWEEPS"
+#endif
+// the forms that take the single sweep: the full-width ones, but RPLE beyond 32768 columns (its epilogue keeps 2 more registers
+// through the fold, which spills them: it keeps the two sweeps)
+constexpr bool one_sweep(int form, bool wide, bool coarse) { return ONE_SWEEP && !coarse && !(form == 2 && wide); }
+// bytes of the LDS ring of a form (the exp / log tables follow it)
+constexpr int ring_bytes(int form, bool wide, bool coarse) { return one_sweep(form, wide, coarse) ? RING1 : RINGW; }
 
 __device__ __forceinline__ double flip_if(double v, int mneg /* 0 or -1 */) {
     return __hiloint2double(__double2hiint(v) + (mneg << 31), __double2loint(v));
@@ -76,10 +96,10 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     const int *__restrict__ cnk, const int8_t *__restrict__ Xc, int64_t xc_tile, int nk_tq) {
     constexpr int WM = 2; // 32-sample MFMA tiles per wave
     extern __shared__ __attribute__((aligned(16))) int8_t lds[]; // ring, then the exp (and log) tables
-    double *etab = reinterpret_cast<double *>(lds + RINGW);
+    double *etab = reinterpret_cast<double *>(lds + ring_bytes(FORM, WIDE, COARSE));
 
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int lr = lane & 31, h = lane >> 5;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int lane = tid & 63, lr = lane & 31, h = lane >> 5; // (the single sweep takes them afresh after its GEMM)
     if (tid < 64) {
         const double v = exp2((double)tid / 64.0);
         // exp forms: 2^(j/64) with j << 14 taken off the high word (the exponent of 2^(n >> 6), n = 64 q + j, goes on as n << 14)
@@ -122,66 +142,14 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         }
     }
 
-    // DMA plan: a ring stage holds DSW = 2 consecutive 64-column steps of ONE sweep; its 2 PA (2 PB) 1-KB pieces are dealt to the
-    // four waves, 5 (4) each.  Piece pc of a step: pc < 2 the two 128-sample pieces of bits, else 16 rows of the sweep's digit
-    // planes.  Addresses = a wave-uniform part (piece, step) + one of two per-lane offsets: the XOR swizzle of lds_off() is
-    // applied to the SOURCE (the LDS side of the DMA is linear) and depends on the lane only (16-row pieces: (row >> 2) & 3 =
-    // (lane >> 4) & 3).
     const int voffX = lane * 16;
     const int voffT = (lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4);
     const int8_t *const gX = xbase + (int64_t)(2 * st) * nk * 1024;
     const int8_t *const gT = Tq + (int64_t)mytile * nk_tq * BRT * 64;
-    const int nst = (nk + DSW - 1) / DSW; // ring stages per sweep; global stage gs < nst: sweep A, else sweep B
-    // per DMA instruction of this wave (wave-uniform, scalar registers): source of step 0, bytes per step, step within the
-    // stage, destination within the stage
-    const int8_t *baseA[NLA], *baseB[NLB];
-    int advA[NLA], advB[NLB], subA[NLA], subB[NLB], dstA[NLA], dstB[NLB];
-    bool bitsA[NLA], bitsB[NLB];
-    auto plan = [&](int sp, int pps, int row0, const int8_t *&base, int &adv, int &sub, int &dst, bool &bits) {
-        sub = sp / pps;
-        const int pc = sp - sub * pps;
-        dst = sub * STEPW + pc * 1024;
-        bits = pc < 2;
-        base = bits ? gX + (int64_t)pc * nk * 1024 : gT + (row0 + (pc - 2) * 16) * 64;
-        adv = bits ? 1024 : BRT * 64;
-    };
-#pragma unroll
-    for (int j = 0; j < NLA; ++j) plan(wave + 4 * j, PA, 32 * LFB, baseA[j], advA[j], subA[j], dstA[j], bitsA[j]); // planes 3..6
-#pragma unroll
-    for (int j = 0; j < NLB; ++j) plan(wave + 4 * j, PB, 0, baseB[j], advB[j], subB[j], dstB[j], bitsB[j]);        // planes 0..2
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) int8_t *)lds;
-    auto issue = [&](int gs) {
-        const unsigned stage_base = lds0 + (gs % NSW) * STAGEW;
-        if (gs < nst) {
-#pragma unroll
-            for (int j = 0; j < NLA; ++j) {
-                int kt = DSW * gs + subA[j];
-                kt = kt < nk ? kt : nk - 1; // (a step beyond the last one: the last one again, so that every stage counts the same loads)
-                dma16(baseA[j] + (int64_t)(kt * advA[j]), bitsA[j] ? voffX : voffT, stage_base + dstA[j]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NLB; ++j) {
-                int kt = DSW * (gs - nst) + subB[j];
-                kt = kt < nk ? kt : nk - 1;
-                dma16(baseB[j] + (int64_t)(kt * advB[j]), bitsB[j] ? voffX : voffT, stage_base + dstB[j]);
-            }
-        }
-    };
-
-    // what the fold between the sweeps needs is fetched now, so that the latency hides under the GEMM; the inputs of the pointwise
-    // arithmetic (sign bits, 1 / tau) are fetched behind sweep B -- registers are what this kernel is short of, and the
-    // co-resident workgroup covers the wait
-    const int r = mytile * 32 + lr;
+    int r = mytile * 32 + lr;
     const int rc = rowcol[r];
     const bool active = rc >= 0;
-    const double sg = active ? sigma[r] : 0.0;
-    // C0 = sum_c q_c + q_const: the energy of the all-(+1) configuration / sigma.  C0 = c_lo + 2^24 c_hi with 0 <= c_lo < 2^24: both
-    // halves, and everything combined with them below, are exact in FP64.  The coarse form has its own constant: the sum of the
-    // numbers the top four planes spell (q / 2^24 rounded to nearest, entry by entry).
-    const long long qc = active ? (COARSE ? qconst2[r] : qconst[r]) : 0;
-    const double c_lo = COARSE ? 0.0 : (double)(unsigned)(qc & 0xffffffll), c_hi = COARSE ? (double)qc : (double)(qc >> 24);
-    const double sgT = sg * 16777216.0, us0 = c_hi * sgT, m2sT = -2.0 * sgT;
 #ifdef ABL_EARLY_INPUTS
     unsigned sgn[WM];
 #pragma unroll
@@ -193,130 +161,295 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     unsigned long long tst[6];
     tst[0] = __builtin_amdgcn_s_memrealtime();
 #endif
-    __builtin_amdgcn_s_setprio(1);
-    const int ntot = COARSE ? nst : 2 * nst; // (the ring of a coarse pass ends with sweep A)
+    double us[WM][16]; // E / s of the lane's 32 elements (the two-sweep form keeps the partial sums of sweep A here first)
+    if constexpr (one_sweep(FORM, WIDE, COARSE)) {
+        // DMA plan: a ring stage is ONE 64-column step; its 16 1-KB pieces are dealt to the four waves, 4 each: piece pc = wave + 4 j,
+        // pc < 2 the two 128-sample pieces of bits (so j = 0 only), else 16 of the 224 digit-plane rows (planes 0..6).  Source
+        // swizzle and per-lane offsets as in the two-sweep form below.
+        const int8_t *base1[NL1];
+        int adv1[NL1];
 #pragma unroll
-    for (int s = 0; s < NSW - 1; ++s)
-        if (s < ntot) issue(s);
-    // one ring stage of GEMM work on NPL digit planes
-    auto gemm_stage = [&](int gs, int ks, auto first, auto &acc) {
-        constexpr bool FIRST = decltype(first)::value;
-        constexpr int NPL = sizeof(acc[0]) / sizeof(acc[0][0]);
-        // the next stage may stay in flight: its loads are the last ones this wave issued
-        if (gs + 1 < ntot) {
-            if (gs + 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLA) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLB) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        for (int j = 0; j < NL1; ++j) {
+            const int pc = wave + 4 * j;
+            base1[j] = pc < 2 ? gX + (int64_t)pc * nk * 1024 : gT + (pc - 2) * 16 * 64;
+            adv1[j] = pc < 2 ? 1024 : BRT * 64;
         }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (gs + NSW - 1 < ntot) issue(gs + NSW - 1);
+        const int voff0 = wave < 2 ? voffX : voffT;
+        auto issue1 = [&](int ks) {
+            const unsigned stage_base = lds0 + (ks % NS1) * STEP1;
 #pragma unroll
-        for (int sub = 0; sub < DSW; ++sub) {
-            if (sub > 0 && DSW * ks + sub >= nk) break; // (an odd number of steps: the last stage is half full)
-            const int8_t *cur = lds + (gs % NSW) * STAGEW + sub * STEPW;
+            for (int j = 0; j < NL1; ++j) dma16(base1[j] + (int64_t)ks * adv1[j], j == 0 ? voff0 : voffT, stage_base + (wave + 4 * j) * 1024);
+        };
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < NS1 - 1; ++s)
+            if (s < nk) issue1(s);
+        v16i acc[WM][LFW];
+        // one step: 7 planes x 2 sample tiles x 2 half-steps = 28 MFMAs; plane-outer, tile-inner, so that one plane's fragment of
+        // Theta (4 registers) is live at a time
+        auto step = [&](int ks, auto first) {
+            constexpr bool FIRST = decltype(first)::value;
+            // the next two stages may stay in flight: their loads are the last ones this wave issued
+            if (ks + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL1) : "memory");
+            else if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL1) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks + NS1 - 1 < nk) issue1(ks + NS1 - 1); // (into the stage every wave finished reading before the barrier)
+            const int8_t *cur = lds + (ks % NS1) * STEP1;
+            // lane (lr, h) needs dword h of its sample's 8 bytes of bits.  One ds_read_b64 per lane reads both: the 32 lanes of a
+            // half-wave cover 256 contiguous bytes, one bank each (ds_read_b32 banks modulo 32 dwords: lanes lr and lr + 16 collide).
             unsigned vb[WM];
 #pragma unroll
             for (int i = 0; i < WM; ++i) {
                 const int row = wave * 64 + i * 32 + lr;
-                vb[i] = *reinterpret_cast<const unsigned *>(cur + (row >> 7) * 1024 + (((row & 127) * 2 + h) << 2));
+                const uint2 v = *reinterpret_cast<const uint2 *>(cur + (row >> 7) * 1024 + (row & 127) * 8);
+                vb[i] = h ? v.y : v.x;
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                v4i fa[WM], fb[NPL];
-#pragma unroll
-                for (int l = 0; l < NPL; ++l) fb[l] = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * t + h));
+                v4i fa[WM];
 #pragma unroll
                 for (int i = 0; i < WM; ++i)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) fa[i][e] = (int)((vb[i] >> (4 * t + e)) & 0x01010101u);
 #pragma unroll
-                for (int i = 0; i < WM; ++i)
+                for (int l = 0; l < LFW; ++l) {
+                    const v4i fb = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * t + h));
 #pragma unroll
-                    for (int l = 0; l < NPL; ++l) {
-                        if (FIRST && sub == 0 && t == 0) acc[i][l] = MFMA_I8(fa[i], fb[l], ((v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}));
-                        else acc[i][l] = MFMA_I8(fa[i], fb[l], acc[i][l]);
+                    for (int i = 0; i < WM; ++i) {
+                        if (FIRST && t == 0) acc[i][l] = MFMA_I8(fa[i], fb, ((v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}));
+                        else acc[i][l] = MFMA_I8(fa[i], fb, acc[i][l]);
                     }
-            }
-        }
-    };
-
-    // ---- sweep A: digit planes 3..6, folded into us = sigma 2^24 (c_hi - 2 a_hi), a_hi = sum_{l>=3} 256^(l-3) C_l (exact: an integer
-    // below 2^53 times a power of two)
-    double us[WM][16];
-    {
-        v16i acc[WM][LFA];
-        if (nk > 0) { // Qfp >= 64; nk = 0: every row of Theta is zero (the caller says so): all sums are 0, nothing is loaded
-            gemm_stage(0, 0, std::true_type{}, acc);
-            for (int ks = 1; ks < nst; ++ks) gemm_stage(ks, ks, std::false_type{}, acc);
-        } else {
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int l = 0; l < LFA; ++l)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
-        }
-#ifdef ABL_TIMING
-        tst[1] = __builtin_amdgcn_s_memrealtime();
-#endif
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                double ahi;
-                if (WIDE) {
-                    ahi = (double)acc[i][3][e];
-#pragma unroll
-                    for (int l = 2; l >= 0; --l) ahi = fma(ahi, 256.0, (double)acc[i][l][e]);
-                } else { // |acc_l| <= 128 Qfp <= 2^22: pairs in int32
-                    const int p0 = acc[i][0][e] + (acc[i][1][e] << 8), p1 = acc[i][2][e] + (acc[i][3][e] << 8);
-                    ahi = fma((double)p1, 65536.0, (double)p0);
                 }
-                us[i][e] = fma(ahi, m2sT, us0);
-                // (pinned here: left alone, the compiler sinks the whole fold behind sweep B and keeps the 128 accumulators of
-                // sweep A alive under the 96 of sweep B)
-                asm volatile("" : "+v"(us[i][e]));
             }
-    }
-#ifdef ABL_TIMING
-    tst[2] = __builtin_amdgcn_s_memrealtime();
-#endif
-    if constexpr (!COARSE) {
-        // ---- sweep B: digit planes 0..2; E / s = sigma (c_lo - 2 a_lo) + us with ONE rounding (c_lo - 2 a_lo is an exact integer).
-        // Done for all 32 elements of the lane at once: the 96 accumulators and the 64 registers of `us` become 64 registers of
-        // energies before the pointwise arithmetic starts.
-        v16i acc[WM][LFB];
-        if (nk > 0) {
-            gemm_stage(nst, 0, std::true_type{}, acc);
-#ifndef ABL_ONESWEEP
-            for (int ks = 1; ks < nst; ++ks) gemm_stage(nst + ks, ks, std::false_type{}, acc);
-#else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+        };
+        if (nk > 0) { // Qfp >= 64; nk = 0: every row of Theta is zero (the caller says so): all sums are 0, nothing is loaded
+            step(0, std::true_type{});
+            for (int ks = 1; ks < nk; ++ks) step(ks, std::false_type{});
         } else {
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int l = 0; l < LFB; ++l)
+                for (int l = 0; l < LFW; ++l)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
         }
+#ifdef ABL_TIMING
+        tst[1] = tst[2] = __builtin_amdgcn_s_memrealtime();
+#endif
+        // the lane's coordinates, taken afresh from the lane id: kept alive through the sweep, they are the registers it lacks
+        lane = __lane_id();
+        lr = lane & 31;
+        h = lane >> 5;
+        r = mytile * 32 + lr;
+        // what the fold needs is fetched behind the sweep: registers are what the sweep is short of, and the co-resident
+        // workgroup covers the wait.  C0 = sum_c q_c + q_const = c_lo + 2^24 c_hi, 0 <= c_lo < 2^24 (see the two-sweep form).
+        const double sg = active ? sigma[r] : 0.0;
+        const long long qc = active ? qconst[r] : 0;
+        const double c_lo = (double)(unsigned)(qc & 0xffffffll), c_hi = (double)(qc >> 24);
+        const double sgT = sg * 16777216.0, us0 = c_hi * sgT, m2sT = -2.0 * sgT;
+        // E / s = sigma (c_lo - 2 a_lo) + sigma 2^24 (c_hi - 2 a_hi), a_lo = sum_{l<3} 256^l C_l, a_hi = sum_{l>=3} 256^(l-3) C_l:
+        // the two-sweep form's operations in its order, so the energies are the same bits.  Element by element, pinned, so that
+        // the 7 accumulators of an element die as its energy appears.
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                double alo;
+                double ahi, alo;
                 if (WIDE) {
+                    ahi = (double)acc[i][6][e];
+#pragma unroll
+                    for (int l = 5; l >= 3; --l) ahi = fma(ahi, 256.0, (double)acc[i][l][e]);
                     alo = fma((double)acc[i][2][e], 256.0, (double)acc[i][1][e]);
                     alo = fma(alo, 256.0, (double)acc[i][0][e]);
-                } else {
+                } else { // |acc_l| <= 128 Qfp <= 2^22: pairs in int32
+                    const int p0 = acc[i][3][e] + (acc[i][4][e] << 8), p1 = acc[i][5][e] + (acc[i][6][e] << 8);
+                    ahi = fma((double)p1, 65536.0, (double)p0);
                     alo = fma((double)acc[i][2][e], 65536.0, (double)(acc[i][0][e] + (acc[i][1][e] << 8)));
                 }
-                us[i][e] = fma(fma(alo, -2.0, c_lo), sg, us[i][e]);
+                us[i][e] = fma(fma(alo, -2.0, c_lo), sg, fma(ahi, m2sT, us0));
+                asm volatile("" : "+v"(us[i][e]));
             }
         __builtin_amdgcn_sched_barrier(0);
+    } else {
+        // DMA plan: a ring stage holds DSW = 2 consecutive 64-column steps of ONE sweep; its 2 PA (2 PB) 1-KB pieces are dealt to the
+        // four waves, 5 (4) each.  Piece pc of a step: pc < 2 the two 128-sample pieces of bits, else 16 rows of the sweep's digit
+        // planes.  Addresses = a wave-uniform part (piece, step) + one of two per-lane offsets: the XOR swizzle of lds_off() is
+        // applied to the SOURCE (the LDS side of the DMA is linear) and depends on the lane only (16-row pieces: (row >> 2) & 3 =
+        // (lane >> 4) & 3).
+        const int nst = (nk + DSW - 1) / DSW; // ring stages per sweep; global stage gs < nst: sweep A, else sweep B
+        // per DMA instruction of this wave (wave-uniform, scalar registers): source of step 0, bytes per step, step within the
+        // stage, destination within the stage
+        const int8_t *baseA[NLA], *baseB[NLB];
+        int advA[NLA], advB[NLB], subA[NLA], subB[NLB], dstA[NLA], dstB[NLB];
+        bool bitsA[NLA], bitsB[NLB];
+        auto plan = [&](int sp, int pps, int row0, const int8_t *&base, int &adv, int &sub, int &dst, bool &bits) {
+            sub = sp / pps;
+            const int pc = sp - sub * pps;
+            dst = sub * STEPW + pc * 1024;
+            bits = pc < 2;
+            base = bits ? gX + (int64_t)pc * nk * 1024 : gT + (row0 + (pc - 2) * 16) * 64;
+            adv = bits ? 1024 : BRT * 64;
+        };
+#pragma unroll
+        for (int j = 0; j < NLA; ++j) plan(wave + 4 * j, PA, 32 * LFB, baseA[j], advA[j], subA[j], dstA[j], bitsA[j]); // planes 3..6
+#pragma unroll
+        for (int j = 0; j < NLB; ++j) plan(wave + 4 * j, PB, 0, baseB[j], advB[j], subB[j], dstB[j], bitsB[j]);        // planes 0..2
+        auto issue = [&](int gs) {
+            const unsigned stage_base = lds0 + (gs % NSW) * STAGEW;
+            if (gs < nst) {
+#pragma unroll
+                for (int j = 0; j < NLA; ++j) {
+                    int kt = DSW * gs + subA[j];
+                    kt = kt < nk ? kt : nk - 1; // (a step beyond the last one: the last one again, so that every stage counts the same loads)
+                    dma16(baseA[j] + (int64_t)(kt * advA[j]), bitsA[j] ? voffX : voffT, stage_base + dstA[j]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NLB; ++j) {
+                    int kt = DSW * (gs - nst) + subB[j];
+                    kt = kt < nk ? kt : nk - 1;
+                    dma16(baseB[j] + (int64_t)(kt * advB[j]), bitsB[j] ? voffX : voffT, stage_base + dstB[j]);
+                }
+            }
+        };
+
+        // what the fold between the sweeps needs is fetched now, so that the latency hides under the GEMM; the inputs of the pointwise
+        // arithmetic (sign bits, 1 / tau) are fetched behind sweep B -- registers are what this kernel is short of, and the
+        // co-resident workgroup covers the wait
+        const double sg = active ? sigma[r] : 0.0;
+        // C0 = sum_c q_c + q_const: the energy of the all-(+1) configuration / sigma.  C0 = c_lo + 2^24 c_hi with 0 <= c_lo < 2^24: both
+        // halves, and everything combined with them below, are exact in FP64.  The coarse form has its own constant: the sum of the
+        // numbers the top four planes spell (q / 2^24 rounded to nearest, entry by entry).
+        const long long qc = active ? (COARSE ? qconst2[r] : qconst[r]) : 0;
+        const double c_lo = COARSE ? 0.0 : (double)(unsigned)(qc & 0xffffffll), c_hi = COARSE ? (double)qc : (double)(qc >> 24);
+        const double sgT = sg * 16777216.0, us0 = c_hi * sgT, m2sT = -2.0 * sgT;
+
+        __builtin_amdgcn_s_setprio(1);
+        const int ntot = COARSE ? nst : 2 * nst; // (the ring of a coarse pass ends with sweep A)
+#pragma unroll
+        for (int s = 0; s < NSW - 1; ++s)
+            if (s < ntot) issue(s);
+        // one ring stage of GEMM work on NPL digit planes
+        auto gemm_stage = [&](int gs, int ks, auto first, auto &acc) {
+            constexpr bool FIRST = decltype(first)::value;
+            constexpr int NPL = sizeof(acc[0]) / sizeof(acc[0][0]);
+            // the next stage may stay in flight: its loads are the last ones this wave issued
+            if (gs + 1 < ntot) {
+                if (gs + 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLA) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLB) : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (gs + NSW - 1 < ntot) issue(gs + NSW - 1);
+#pragma unroll
+            for (int sub = 0; sub < DSW; ++sub) {
+                if (sub > 0 && DSW * ks + sub >= nk) break; // (an odd number of steps: the last stage is half full)
+                const int8_t *cur = lds + (gs % NSW) * STAGEW + sub * STEPW;
+                unsigned vb[WM];
+#pragma unroll
+                for (int i = 0; i < WM; ++i) {
+                    const int row = wave * 64 + i * 32 + lr;
+                    vb[i] = *reinterpret_cast<const unsigned *>(cur + (row >> 7) * 1024 + (((row & 127) * 2 + h) << 2));
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    v4i fa[WM], fb[NPL];
+#pragma unroll
+                    for (int l = 0; l < NPL; ++l) fb[l] = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * t + h));
+#pragma unroll
+                    for (int i = 0; i < WM; ++i)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) fa[i][e] = (int)((vb[i] >> (4 * t + e)) & 0x01010101u);
+#pragma unroll
+                    for (int i = 0; i < WM; ++i)
+#pragma unroll
+                        for (int l = 0; l < NPL; ++l) {
+                            if (FIRST && sub == 0 && t == 0) acc[i][l] = MFMA_I8(fa[i], fb[l], ((v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}));
+                            else acc[i][l] = MFMA_I8(fa[i], fb[l], acc[i][l]);
+                        }
+                }
+            }
+        };
+
+        // ---- sweep A: digit planes 3..6, folded into us = sigma 2^24 (c_hi - 2 a_hi), a_hi = sum_{l>=3} 256^(l-3) C_l (exact: an integer
+        // below 2^53 times a power of two)
+        {
+            v16i acc[WM][LFA];
+            if (nk > 0) { // Qfp >= 64; nk = 0: every row of Theta is zero (the caller says so): all sums are 0, nothing is loaded
+                gemm_stage(0, 0, std::true_type{}, acc);
+                for (int ks = 1; ks < nst; ++ks) gemm_stage(ks, ks, std::false_type{}, acc);
+            } else {
+#pragma unroll
+                for (int i = 0; i < WM; ++i)
+#pragma unroll
+                    for (int l = 0; l < LFA; ++l)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
+            }
+#ifdef ABL_TIMING
+            tst[1] = __builtin_amdgcn_s_memrealtime();
+#endif
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    double ahi;
+                    if (WIDE) {
+                        ahi = (double)acc[i][3][e];
+#pragma unroll
+                        for (int l = 2; l >= 0; --l) ahi = fma(ahi, 256.0, (double)acc[i][l][e]);
+                    } else { // |acc_l| <= 128 Qfp <= 2^22: pairs in int32
+                        const int p0 = acc[i][0][e] + (acc[i][1][e] << 8), p1 = acc[i][2][e] + (acc[i][3][e] << 8);
+                        ahi = fma((double)p1, 65536.0, (double)p0);
+                    }
+                    us[i][e] = fma(ahi, m2sT, us0);
+                    // (pinned here: left alone, the compiler sinks the whole fold behind sweep B and keeps the 128 accumulators of
+                    // sweep A alive under the 96 of sweep B)
+                    asm volatile("" : "+v"(us[i][e]));
+                }
+        }
+#ifdef ABL_TIMING
+        tst[2] = __builtin_amdgcn_s_memrealtime();
+#endif
+        if constexpr (!COARSE) {
+            // ---- sweep B: digit planes 0..2; E / s = sigma (c_lo - 2 a_lo) + us with ONE rounding (c_lo - 2 a_lo is an exact integer).
+            // Done for all 32 elements of the lane at once: the 96 accumulators and the 64 registers of `us` become 64 registers of
+            // energies before the pointwise arithmetic starts.
+            v16i acc[WM][LFB];
+            if (nk > 0) {
+                gemm_stage(nst, 0, std::true_type{}, acc);
+#ifndef ABL_ONESWEEP
+                for (int ks = 1; ks < nst; ++ks) gemm_stage(nst + ks, ks, std::false_type{}, acc);
+#else
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+            } else {
+#pragma unroll
+                for (int i = 0; i < WM; ++i)
+#pragma unroll
+                    for (int l = 0; l < LFB; ++l)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
+            }
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    double alo;
+                    if (WIDE) {
+                        alo = fma((double)acc[i][2][e], 256.0, (double)acc[i][1][e]);
+                        alo = fma(alo, 256.0, (double)acc[i][0][e]);
+                    } else {
+                        alo = fma((double)acc[i][2][e], 65536.0, (double)(acc[i][0][e] + (acc[i][1][e] << 8)));
+                    }
+                    us[i][e] = fma(fma(alo, -2.0, c_lo), sg, us[i][e]);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     __builtin_amdgcn_s_setprio(0);
 #ifdef ABL_TIMING
@@ -511,6 +644,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         // planes at a time (6 KB per wave).  Rows that are not part of this pass keep what they hold (a re-run of some rows of a
         // tile must not touch the planes of the others): their lines are stored partially.
         {
+            const int nst = (nk + DSW - 1) / DSW, ntot = COARSE ? nst : 2 * nst;
             const int lastslot = (ntot > 0 ? ntot - 1 : 0) % NSW;
             int8_t *stg = lds + ((lastslot + 1 + (wave >> 1)) % NSW) * STAGEW + (wave & 1) * 6144;
             const unsigned amask = (unsigned)__ballot(active); // bit lr (lanes 0..31)
@@ -683,7 +817,7 @@ void launch_finalize_i8w(const int32_t *Gacc, const SlotScalars &sc, const int *
 
 template <int FORM, bool WANTF, bool WIDE, bool UNIW, bool COARSE>
 static void launch_fwd_w5(const FwdWArgs &a) {
-    constexpr int shmem = RINGW + 512 + 1024; // ring + exp, log tables
+    constexpr int shmem = ring_bytes(FORM, WIDE, COARSE) + 512 + 1024; // ring + exp, log tables
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, shmem); // per device: set on every launch
     const DevProblem &d = *a.d;

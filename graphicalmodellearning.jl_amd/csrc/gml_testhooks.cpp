@@ -1,5 +1,6 @@
 // libgml_hip: test and experiment hooks (not part of include/gml.h).
 #include "gml_internal.h"
+#include "gml_i8.h"
 #include "gml_solver.h"
 #include "gml_pack.h"
 
@@ -187,3 +188,26 @@ extern "C" int gml_debug_read_vq(gml_problem *p, int64_t off, int64_t bytes, voi
     return GML_OK;
 }
 
+
+// Test hook (not part of include/gml.h): what the last objective/gradient pass of an int8-limb precision left on the device -- the
+// Vq image (slots x planes x Kp bytes, in the layout of gml_i8.h) and the per-slot sums csum, csum2, asum, asum2 (sums[5][slots]:
+// the fifth row is mmax, widened).  Null outputs: only the sizes.  tests/test_gpu_i8w_single_sweep.py.
+extern "C" int gml_test_i8_pass_state(gml_problem *p, int64_t *slots, int *planes, int64_t *kp, int8_t *vq, long long *sums) {
+    if (!p || !slots || !planes || !kp) return fail(GML_EINVAL, "bad argument");
+    const gml::I8Ws *w = static_cast<const gml::I8Ws *>(p->i8ws);
+    *slots = w ? w->slots : 0;
+    *planes = w ? w->LBT : 0;
+    *kp = p->d.Kp;
+    if (!w || !vq || !sums) return GML_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->st));
+    const size_t ns = (size_t)w->slots;
+    HIPCHK(hipMemcpy(vq, w->Vq, ns * w->LBT * p->d.Kp, hipMemcpyDeviceToHost));
+    const gml::SlotScalars &sc = w->sc[0];
+    const long long *src[4] = {sc.csum, sc.csum2, sc.asum, sc.asum2};
+    for (int j = 0; j < 4; ++j) HIPCHK(hipMemcpy(sums + j * ns, src[j], sizeof(long long) * ns, hipMemcpyDeviceToHost));
+    std::vector<unsigned> mm(ns);
+    HIPCHK(hipMemcpy(mm.data(), sc.mmax, sizeof(unsigned) * ns, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ns; ++i) sums[4 * ns + i] = mm[i];
+    return GML_OK;
+}
