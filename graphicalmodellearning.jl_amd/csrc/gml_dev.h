@@ -103,6 +103,7 @@ struct I8Pass {
     const int *vmap;      // hv: device [slots]
     int ksub;             // hv: the products run over ~1/ksub of the configurations (i8_split_plan); 0, 1 = all of them
     int64_t kchunk, kpart; // hv: a split plan fixed by the caller (one operator for all the steps of a CG solve); 0 = plan here
+    int64_t *plan_out;    // host [2] or NULL: receives the kchunk, kpart the pass ran with
     SlotResult *res;      // device [slots] or NULL: {f, tau, mmax} of every slot of the pass, written by its last kernel
     int lf;               // forward limb planes (3, 4, 5; 0 = the default, 5; 2 for Hessian-vector directions): 8 lf - 2 significant bits of theta
     bool wide;            // the FP64-grade pass (precision i8w): theta in 7 limb planes (54 bits), V in 6 (47 bits), FP64 exp;

@@ -142,6 +142,16 @@ struct ColCompact {
     int64_t xc_tile;
 };
 
+// Record of the kernel instances the launchers below have run (host side, gml_testhooks.cpp; read by the test hook
+// gml_test_i8_instances): one bit per template instance, set with a relaxed atomic OR, never read by the library itself.
+//   k_fwd_i8<LF, FORM, WANTF, WIDE, COARSE, UNIW>  bit (LF - 2) * 64 + f * 16 + WANTF * 8 + WIDE * 4 + COARSE * 2 + UNIW, f = 0, 1, 2, 3
+//                                                  for FORM = 0, 2, 3, 4
+//   k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>     bit 256 + (FORM == 2) * 16 + WANTF * 8 + WIDE * 4 + UNIW * 2 + COARSE
+//   k_bwd_i8<1, NL> from plane pl0                 bit 288 + n * 4 + p, n = 0, 1, 2, 3 for NL = 2, 3, 4, 6, p = 0, 1, 2 for pl0 = 0, 1, 3
+//   k_finalize_i8 (hv), k_finalize_i8w (coarse)    bits 304 + (hv != 0), 306 + coarse
+constexpr int kI8InstBits = 308;
+void i8_note_instance(int bit);
+
 // ---- launchers across the kernel files ----------------------------------------------------------------------------------
 // gml_i8_pack.hip
 void launch_quant_theta(int LF, int ns, const I8Pass &a, const DevProblem &d, int hv, const double *tauV, int8_t *Tq, const SlotScalars &sc,

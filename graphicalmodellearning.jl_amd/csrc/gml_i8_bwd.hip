@@ -228,6 +228,7 @@ void launch_bwd_i8(int NL, const int8_t *Vin, const DevProblem &d, const int *gr
     const int T = ngt * nNt;
     const int grid = ((nsplit + 7) / 8) * 8 * T;
     const int shmem = 4 * ((NL == 6 ? 12 : 8 * TM) + 2) * 1024;
+    i8_note_instance(288 + (NL == 2 ? 0 : NL == 3 ? 1 : NL == 6 ? 3 : 2) * 4 + (pl0 == 0 ? 0 : pl0 == 1 ? 1 : 2));
 #define BWD(NLV)                                                                                                                            \
     do {                                                                                                                                    \
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bwd_i8<1, NLV>), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);     \
@@ -243,6 +244,7 @@ void launch_bwd_i8(int NL, const int8_t *Vin, const DevProblem &d, const int *gr
 
 void launch_finalize_i8(const int32_t *Gacc, const SlotScalars &sc, const int *srow, const int *rowcol, int slot0, int ns, const DevProblem &d,
                         int form, int want_grad, int hv, double *G, double *F, int nplanes, int64_t plane_stride, SlotResult *res, hipStream_t st) {
+    i8_note_instance(304 + (hv ? 1 : 0));
     hipLaunchKernelGGL(k_finalize_i8, dim3((unsigned)((d.Qp + 255) / 256), (unsigned)ns), dim3(256), 0, st, Gacc, sc.tau, sc.csum, sc.asum, srow,
                        rowcol, slot0, d.Qp, d.Qfp, d.Qf, d.cconst, form, want_grad, hv, G, F, nplanes, plane_stride, sc.mmax, res);
 }

@@ -6,8 +6,8 @@
 
 namespace gml {
 
-// V / tau of one element of the exp forms: -s rint(w/tau exp(-s E) + dither), E = s Ea.  Ea to 3e-10 relative before
-// the rounding.  FP64 range reduction with one FMA (the product t * ln2/64 is not rounded inside an FMA), FP32
+// V / tau of one element of the exp forms: -s rint(w/tau exp(-s E) + dither), E = s Ea.  exp(-s E) to 1e-9 relative
+// before the rounding (three FP32 roundings of ~2^-24 |r| in the expm1 below).  FP64 range reduction with one FMA (the product t * ln2/64 is not rounded inside an FMA), FP32
 // polynomial for expm1 of the reduced argument, table of 2^(j/64), exponent added as an integer, and the final rounding
 // to an integer through the 1.5 * 2^52 trick, after adding a dither in [-1/2, 1/2) that is a fixed function of
 // (node, sample): the rounding is then "stochastic" -- still deterministic and within one unit, but uncorrelated across
@@ -593,6 +593,8 @@ static void launch_fwd5(const FwdLaunch &a) {
     constexpr int shmem = 3 * STAGE + 512 + 1024;   // ring + exp, log tables
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_i8<LF, FORM, WANTF, WIDE, COARSE, UNIW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, shmem); // per device: set on every launch
+    constexpr int fi = FORM == 0 ? 0 : FORM == 2 ? 1 : FORM == 3 ? 2 : 3;
+    i8_note_instance((LF - 2) * 64 + fi * 16 + WANTF * 8 + WIDE * 4 + COARSE * 2 + UNIW);
     const DevProblem &d = *a.d;
     const int ntk = a.ntk;
     const int grid = ((ntk + 7) / 8) * 8 * a.ngroups; // one workgroup per (sample tile, node tile); see the kernel's block mapping

@@ -185,6 +185,10 @@ int i8_pass(void **wsp, const DevProblem &d, int64_t slot_capacity, const I8Pass
         i8_split_plan(d, a.ngroups, hv ? a.ksub : 1, &kchunk, &kpart, &nsplit);
     }
     const int ksub = kpart < kchunk ? (int)(kchunk / kpart) : 1;
+    if (a.plan_out) {
+        a.plan_out[0] = kchunk;
+        a.plan_out[1] = kpart;
+    }
     if (ev) I8CHK(hipEventRecord(ev[0], st));
     if (wide) {
         FwdWArgs fw{&d, w->Tq, &sc, a.rowcol, a.groups, a.ngroups, a.form, !a.want_grad, coarse, a.F, w->Vq, st};

@@ -751,9 +751,11 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         ymax_hi = max(ymax_hi, __shfl_xor(ymax_hi, 32));
         // the high word + 1 bounds 2^32 max(|V| / tau + dither) from above (to 2^-20 relative); in units of 2^16 tau
         const double ymax = __hiloint2double(ymax_hi + 1, 0);
-        // (coarse: ymax bounds 2^32 |V| / (2^24 tau); reported in the same unit, rounded up to the next multiple of 2^24 tau)
-        const unsigned mxu = COARSE ? (((unsigned)fmin(ymax * 2.3283064365386963e-10 /* 2^-32 */, 8388606.0) + 1u) << 8)
-                                    : (unsigned)fmin(ymax * 3.5527136788005009e-15 /* 2^-48 */, 4294967295.0);
+        // (coarse: ymax bounds 2^32 (|V| / (2^24 tau) + dither), the dither down to -1/2 of that unit: |V| / (2^24 tau) < floor(ymax 2^-32)
+        // + 3/2, reported in units of 2^16 tau as the next multiple of 2^24 tau above it.  Full width: |V| / tau < ymax 2^-32 + 1/2, so
+        // mmax = floor((ymax 2^-32 + 1/2) / 2^16) -- the sum is exact in FP64 -- and (mmax + 1) 2^16 tau > |V| for every sample)
+        const unsigned mxu = COARSE ? (((unsigned)fmin(ymax * 2.3283064365386963e-10 /* 2^-32 */, 8388605.0) + 2u) << 8)
+                                    : (unsigned)fmin(fma(ymax, 3.5527136788005009e-15 /* 2^-48 */, 7.62939453125e-06 /* 2^-17 */), 4294967295.0);
         if (active && h == 0) atomicMax(&mmax[r], mxu);
     } else {
         fp += __shfl_xor(fp, 32);
@@ -810,6 +812,7 @@ __global__ __launch_bounds__(256) void k_finalize_i8w(const int32_t *__restrict_
 void launch_finalize_i8w(const int32_t *Gacc, const SlotScalars &sc, const int *srow, const int *rowcol, int slot0, int ns, int64_t Qp,
                          int64_t Qfp, int64_t Qf, int64_t cconst, int form, int want_grad, double *G, double *f, int nplanes,
                          int64_t plane_stride, SlotResult *res, bool coarse, hipStream_t st) {
+    i8_note_instance(306 + (coarse ? 1 : 0));
     hipLaunchKernelGGL(k_finalize_i8w, dim3((unsigned)((Qp + 255) / 256), (unsigned)ns), dim3(256), 0, st, Gacc, sc.tau, sc.csum, sc.csum2,
                        sc.asum, sc.asum2, srow, rowcol, slot0, Qp, Qfp, Qf, cconst, form, want_grad, G, f, nplanes, plane_stride, sc.mmax, res,
                        coarse ? 1 : 0);
@@ -820,6 +823,7 @@ static void launch_fwd_w5(const FwdWArgs &a) {
     constexpr int shmem = ring_bytes(FORM, WIDE, COARSE) + 512 + 1024; // ring + exp, log tables
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, shmem); // per device: set on every launch
+    i8_note_instance(256 + (FORM == 2) * 16 + WANTF * 8 + WIDE * 4 + UNIW * 2 + COARSE);
     const DevProblem &d = *a.d;
     const int ntk = (int)(d.Kp / 256);
     const int grid = ((ntk + 7) / 8) * 8 * a.ngroups; // one workgroup per (sample tile, node tile)

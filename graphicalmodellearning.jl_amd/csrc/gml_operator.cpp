@@ -109,8 +109,17 @@ static int upload_ctl(gml_problem *p, int64_t R, const int64_t *nodes, const std
 // (want_grad) -- or, hv, the Hessian-vector pass of the directions in dTheta, which leaves H p (RISE, RPLE) / Hess Z p (logRISE) in
 // dG from the curvature weights the objective pass left in the same slots.  tauovr: device [Rp] or NULL, the per-slot scale of a
 // rescaled re-run.  ev: [3] or NULL, recorded before the forward, between the two halves and after the backward.
+// kn: the forms of an int8-limb pass the public entry points leave at their defaults, set by the test hook gml_test_i8_pass (NULL:
+// the defaults)
+struct PassKnobs {
+    bool coarse = false, zero_theta = false;
+    int lf = 0, hv = 1, ksub = 0; // hv: 1 or 2 (a Hessian-vector pass only)
+    int64_t kchunk = 0, kpart = 0;
+    gml::SlotResult *res = nullptr;
+    int64_t *plan_out = nullptr;
+};
 static int launch_pass(gml_problem *p, int64_t Rp, int ngroups, int npad, int form, int precision, bool want_grad, bool hv,
-                       const double *tauovr, bool compact, hipEvent_t *ev) {
+                       const double *tauovr, bool compact, hipEvent_t *ev, const PassKnobs *kn = nullptr) {
     hipStream_t st = p->st;
     if (gml_is_i8(precision)) {
         gml::I8Pass a{};
@@ -130,6 +139,17 @@ static int launch_pass(gml_problem *p, int64_t Rp, int ngroups, int npad, int fo
         a.compact = compact;
         a.hv = hv ? 1 : 0;
         a.vmap = hv ? p->dSrow : nullptr; // (slot = row: the weights of the objective pass that ran in the same slot)
+        if (kn) {
+            a.coarse = kn->coarse;
+            a.zero_theta = kn->zero_theta;
+            a.lf = kn->lf;
+            if (hv) a.hv = kn->hv;
+            a.ksub = kn->ksub;
+            a.kchunk = kn->kchunk;
+            a.kpart = kn->kpart;
+            a.res = kn->res;
+            a.plan_out = kn->plan_out;
+        }
         std::string err;
         const int rc = gml::i8_pass(&p->i8ws, p->d, p->ws_rows, a, st, ev, &err);
         return rc ? fail(rc, "%s", err.c_str()) : GML_OK;
@@ -630,6 +650,108 @@ extern "C" int gml_test_hessian_blocks(gml_problem *p, int formulation, int prec
     return GML_OK;
 }
 
+// Test hook (not part of include/gml.h): ONE objective pass over caller-given rows in a form the public entry points do not choose, and
+// optionally one Hessian-vector pass after it, with no rescaled re-runs.  Host pointers; rows in the reference's parameter order.
+//   kn [11]: coarse, lf (0 / 3 / 4 / 5), want_grad, compact, zero_theta, then the product pass: hv (0 = none, 1, 2), its lf (2 .. 5),
+//            ksub, kchunk, kpart (0: planned in the pass)
+//   tauovr [nrows] or NULL: the per-row scale of V imposed on the objective pass (the operator's rescaled re-run), 0 = from the bound
+//   vec [nrows][ld]: the directions (read when hv)
+// Out: f [nrows] and g [nrows][ld] (may be NULL) of the objective pass, hv [nrows][ld] of the products, all as the passes leave them
+// (logRISE: Z, grad Z and Hess Z v, without the log finish); slots [2][nrows][3] = {f, tau, mmax} of every row in each pass (each pass's
+// SlotResult); plan [2] = the kchunk, kpart of the product pass.
+extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, int64_t nrows, const int64_t *nodes, const double *theta,
+                                const double *tauovr, const double *vec, int64_t ld, const int64_t *kn, double *f, double *g, double *hv,
+                                double *slots, int64_t *plan) {
+    if (!p || !nodes || !theta || !kn || !f || !slots) return fail(GML_EINVAL, "NULL argument");
+    if (precision != GML_PREC_F64 && !gml_is_i8(precision)) return fail(GML_EINVAL, "unknown precision %d", precision);
+    const int hvk = (int)kn[5];
+    if (hvk && (!vec || !hv)) return fail(GML_EINVAL, "a product pass needs vec and hv");
+    bool dev = false;
+    int rc = check_rows(p, formulation, nrows, nodes, ld, theta, f, nullptr, "theta and f", &dev);
+    if (rc) return rc;
+    if (dev) return fail(GML_EINVAL, "gml_test_i8_pass takes host pointers");
+    const int64_t Qp = p->d.Qp, Rp = gml_round_up(nrows, 32);
+    if ((rc = gml_ensure_ws(p, nrows))) return rc;
+    hipStream_t st = p->st;
+    std::vector<NodeLayout> lay;
+    std::vector<double> Th((size_t)nrows * Qp, 0.0), Vc((size_t)nrows * Qp, 0.0), Gi((size_t)nrows * Qp, 0.0), Hi((size_t)nrows * Qp, 0.0),
+        fv((size_t)Rp, 0.0);
+    if (to_internal(p, nrows, nodes, lay, theta, ld, Th.data(), hvk ? vec : nullptr, hvk ? Vc.data() : nullptr) >= 0)
+        return fail(GML_EINVAL, "a row contains a non-finite value");
+    std::vector<uint8_t> act((size_t)nrows, 1);
+    std::vector<int> groups;
+    int npad = 0;
+    if ((rc = upload_ctl(p, nrows, nodes, act, groups, &npad))) return rc;
+    Rescale rs;
+    if (tauovr) {
+        rs.ovr.assign((size_t)Rp, 0.0);
+        std::copy(tauovr, tauovr + nrows, rs.ovr.begin());
+        if ((rc = rs.upload(p, Rp))) return rc;
+    }
+    gml::SlotResult *dRes = nullptr;
+    HIPCHK(dev_malloc(&dRes, sizeof(gml::SlotResult) * 2 * Rp));
+    if (hipError_t e = hipMemsetAsync(dRes, 0, sizeof(gml::SlotResult) * 2 * Rp, st); e != hipSuccess) {
+        (void)dev_free(dRes);
+        return fail(GML_EHIP, "gml_test_i8_pass: %s", hipGetErrorString(e));
+    }
+    std::vector<gml::SlotResult> res((size_t)2 * Rp);
+    auto run = [&]() -> int {
+        PassKnobs k;
+        k.coarse = kn[0] != 0;
+        k.lf = (int)kn[1];
+        k.zero_theta = kn[4] != 0;
+        k.res = dRes;
+        const bool want_grad = kn[2] != 0;
+        std::memcpy(p->hTh, Th.data(), sizeof(double) * nrows * Qp);
+        HIPCHK(hipMemcpyAsync(p->dTheta, p->hTh, sizeof(double) * nrows * Qp, hipMemcpyHostToDevice, st));
+        int rc2 = launch_pass(p, Rp, (int)groups.size(), npad, formulation, precision, want_grad, false, tauovr ? rs.dOvr : nullptr,
+                              kn[3] != 0, nullptr, &k);
+        if (rc2) return rc2;
+        HIPCHK(hipMemcpyAsync(p->hF, p->dF, sizeof(double) * Rp, hipMemcpyDeviceToHost, st));
+        if (want_grad) HIPCHK(hipMemcpyAsync(p->hG, p->dG, sizeof(double) * nrows * Qp, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        std::memcpy(fv.data(), p->hF, sizeof(double) * Rp);
+        if (want_grad) std::memcpy(Gi.data(), p->hG, sizeof(double) * nrows * Qp);
+        if (!hvk) return GML_OK;
+        PassKnobs k2;
+        k2.hv = hvk;
+        k2.lf = (int)kn[6];
+        k2.ksub = (int)kn[7];
+        k2.kchunk = kn[8];
+        k2.kpart = kn[9];
+        k2.res = dRes + Rp;
+        k2.plan_out = plan;
+        std::memcpy(p->hTh, Vc.data(), sizeof(double) * nrows * Qp);
+        HIPCHK(hipMemcpyAsync(p->dTheta, p->hTh, sizeof(double) * nrows * Qp, hipMemcpyHostToDevice, st));
+        rc2 = launch_pass(p, Rp, (int)groups.size(), npad, formulation, precision, true, true, nullptr, false, nullptr, &k2);
+        if (rc2) return rc2;
+        HIPCHK(hipMemcpyAsync(p->hG, p->dG, sizeof(double) * nrows * Qp, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        std::memcpy(Hi.data(), p->hG, sizeof(double) * nrows * Qp);
+        return GML_OK;
+    };
+    rc = run();
+    if (rc == GML_OK) {
+        hipError_t e = hipMemcpyAsync(res.data(), dRes, sizeof(gml::SlotResult) * 2 * Rp, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(GML_EHIP, "gml_test_i8_pass: %s", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(st);
+    (void)dev_free(dRes);
+    if (rc) return rc;
+    // (raw sums: the layout gather of RISE, which leaves logRISE's Z and grad Z as they are)
+    to_reference(lay, p->P, Qp, GML_RISE, fv.data(), Gi.data(), f, kn[2] ? g : nullptr, ld);
+    if (hvk) to_reference(lay, p->P, Qp, GML_RISE, fv.data(), Hi.data(), nullptr, hv, ld);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int64_t r = 0; r < nrows; ++r) {
+            const gml::SlotResult &s = res[(size_t)pass * Rp + r];
+            double *o = slots + ((size_t)pass * nrows + r) * 3;
+            o[0] = s.f;
+            o[1] = s.tau;
+            o[2] = (double)s.mmax;
+        }
+    return GML_OK;
+}
 
 // Timing hook with the parameters RESIDENT in HBM: Theta is uploaded once, then `warmup + steps` passes run back
 // to back on the handle's stream with no host round trip (a device-side optimiser would call the operator this

@@ -778,6 +778,10 @@ int Solver::run_pass(const std::vector<int> &rows, const double *src, double *ds
         double noise = 1e-13 * std::max(1.0, std::fabs(fv));
         if (track) {
             noise += 3.3 * std::sqrt((double)p->K) * tauh[a] * (coarse_on ? i8_coarse_unit(wide) : 1.0); // (coarse: multiples of 2^24 / 2^8 tau)
+            // i8x exp forms: the FP32 expm1 of the forward epilogue (vq_exp) is off by up to 1e-9 of every |V_k| before the rounding
+            // (three FP32 roundings of about 2^-24 |r| each, |r| <= ln2/128: 3 * 2^-24 * ln2/128 / (1 - ln2/128) = 9.74e-10; 7.7e-10
+            // measured) -- one error for all the samples that share an energy, so it adds up with f, not like a random walk
+            if (!wide && formulation != GML_RPLE) noise += 1e-9 * std::fabs(fv);
             const double vmax = ((double)mmh[a] + 1.0) * i8_mmax_unit(wide) * tauh[a]; // rigorous bound on max_k |V_rk|
             vref[r] = vmax;
             dref[r] = at_trial ? stepn[r] : 0.0; // distance from the current iterate to the point just evaluated

@@ -22,6 +22,19 @@ namespace gml {
 double g_hv_sparse_ratio = 0.3; // (config 5 at the default regulariser: 25.6 s never, 23.6 s at 0.3 and at 0.6)
 std::atomic<long long> g_hv_sparse_calls{0}; // (every part of a gml_multi_learn counts from its own host thread)
 double g_tune[GML_NTUNE] = {};               // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
+// the kernel instances the int8-limb launchers have run (gml_i8.h: kI8InstBits)
+static std::atomic<uint64_t> g_i8_inst[(kI8InstBits + 63) / 64];
+void i8_note_instance(int bit) { g_i8_inst[bit >> 6].fetch_or(1ull << (bit & 63), std::memory_order_relaxed); }
+}
+// The record of launched int8-limb kernel instances (bit numbering: gml_i8.h): copies the first n words to out (if not NULL) and
+// clears the record when reset is set.  Host memory only.  Returns the number of words of the record.
+extern "C" int gml_test_i8_instances(uint64_t *out, int n, int reset) {
+    constexpr int nw = (kI8InstBits + 63) / 64;
+    for (int i = 0; i < nw; ++i) {
+        const uint64_t v = reset ? g_i8_inst[i].exchange(0, std::memory_order_relaxed) : g_i8_inst[i].load(std::memory_order_relaxed);
+        if (out && i < n) out[i] = v;
+    }
+    return nw;
 }
 // the solver's switch between the GEMM form and the entry-by-entry form of a Hessian-vector pass (gml_solver.h); returns the old value
 extern "C" long long gml_test_hv_sparse_calls(void) { return g_hv_sparse_calls.load(); }
