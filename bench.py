@@ -7,7 +7,7 @@ BASELINE workload: n=1024 spins, K=1e6 samples (block-Ising, 64 blocks x 16 spin
 the device by the library's exact block sampler (no host sample matrix).  Inputs (packed spins,
 weights, and the parameters Theta) are resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 --dump-outputs writes f and the gradient of the last timed pass to DIR as float64 .npy files (dump_outputs()); the inputs
 are seeded, so two builds run with the same arguments can be compared output for output.
@@ -17,13 +17,17 @@ With N > 1 and no WORLD_SIZE in the environment this process only launches
 relays rank 0's line; under torchrun each rank takes the nodes [rank*n/N, (rank+1)*n/N) of the SAME
 problem (strong scaling; no collective on the data path, one RCCL all-gather of the learned rows).
 
-Prints ONE JSON line (rank 0).  The headline (`value`, `ms_per_step`, `dtype`, `roofline`, `learn_wall_s`) is measured at
-precision "i8w": the int8 matrix cores at the width of the reference's Float64 arithmetic (Theta in 54-bit, the weights in
-47-bit int8 limbs, exp in FP64; tests/test_gpu_parity.py holds it to the same 1e-12 as the FP64-MFMA path, and this run
-re-checks it against that path and against the CPU oracle).  Extra objects: "f64" (the same pass on the FP64-MFMA path),
-"i8x" (the 38/31-bit accelerated mode that learn() uses by default), "cpu_baseline" (the CPU oracle's blocked restatement
-timed on this box's host cores on a bounded sample: all threads and one thread; CPU learn() wall-clock at config 2 and at
-this config), the learn() wall-clock of this config at all three precisions, and one pass over a weighted histogram.
+Prints ONE JSON line (rank 0).  The headline (`value`, `ms_per_step`, `dtype`, `roofline`) is measured at precision "i8w": the
+int8 matrix cores at the width of the reference's Float64 arithmetic (Theta in 54-bit, the weights in 47-bit int8 limbs, exp in
+FP64; tests/test_gpu_parity.py holds it to the same 1e-12 as the FP64-MFMA path).  A plain run does only that: set up, warm up,
+time the steps, write --dump-outputs, print the line; `roofline` there comes from the timed passes' own kernel times.
+
+--full adds the legs that take runs of their own (the --no-* switches skip single legs of it): the pass through the host-pointer
+operator boundary (roofline.pcie_*), "f64" (the same pass on the FP64-MFMA path, checked against the headline), "i8x" (the
+38/31-bit accelerated mode that learn() uses by default), the pass with column compaction on, the learn() wall-clock of this
+config at all three precisions (`learn_wall_s` ...), learn() from a host histogram, the 8-GPU shard projection, one pass over a
+weighted histogram, and "cpu_baseline" (the CPU oracle's blocked restatement timed on this box's host cores on a bounded sample:
+all threads and one thread, a parity check of the timed output against it; CPU learn() wall-clock at config 2 and at this config).
 """
 import argparse
 import json
@@ -70,6 +74,8 @@ def parse_args():
     ap.add_argument("--precision", default=os.environ.get("GML_BENCH_PRECISION", "i8w"), choices=["f64", "i8x", "i8w"],
                     help="arithmetic of the headline: i8w = FP64-grade int8-limb pass (default); i8x = 38/31-bit int8-limb pass; "
                          "f64 = FP64 MFMA pass")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline (other precisions, learn(), CPU "
+                                                         "baseline, ...); the --no-* switches below skip single legs of a --full run")
     ap.add_argument("--no-learn", action="store_true", help="skip the full learn() wall-clock leg")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-f64", action="store_true", help="skip the FP64-path leg")
@@ -157,7 +163,7 @@ def pass_roofline(km, K, P, nloc, precision):
                       "algorithmic product (fixed point), so frac <= 1/limb_products")
         if precision == "i8w":
             rf["note"] += ("; the backward GEMM of i8w is one launch over all six planes of V (k_bwd_i8<1, 6>), the forward "
-                           "kernel as one launch sweeping the columns twice (4 + 3 planes)")
+                           "kernel as one launch sweeping the columns once over all seven planes of Theta")
     return rf, dom
 
 
@@ -252,12 +258,13 @@ def main():
     value = n * args.steps / elapsed  # node evaluations per second, whole job
 
     roofline, dom = pass_roofline(km, K, n, nloc, args.precision)
-    # the same pass through the host-pointer operator boundary (Theta up and gradient down over PCIe every pass)
-    t0 = time.perf_counter()
-    prob.bench_pass("RISE", theta, steps=3, warmup=1, precision=args.precision)
-    pcie_ms = (time.perf_counter() - t0) / 4 * 1e3
-    roofline["pcie_inclusive_ms_per_step"] = pcie_ms
-    roofline["pcie_inclusive_node_evals_per_s_per_gpu"] = nloc / (pcie_ms * 1e-3)
+    if args.full:
+        # the same pass through the host-pointer operator boundary (Theta up and gradient down over PCIe every pass)
+        t0 = time.perf_counter()
+        prob.bench_pass("RISE", theta, steps=3, warmup=1, precision=args.precision)
+        pcie_ms = (time.perf_counter() - t0) / 4 * 1e3
+        roofline["pcie_inclusive_ms_per_step"] = pcie_ms
+        roofline["pcie_inclusive_node_evals_per_s_per_gpu"] = nloc / (pcie_ms * 1e-3)
 
     # HBM-side traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the value
     # measured with `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` on this same command (separate passes;
@@ -344,12 +351,13 @@ def main():
         extra["rccl_version"] = "unknown (%s)" % type(e).__name__
     extra["torch_version"], extra["hip_version"] = torch.__version__, str(torch.version.hip)
 
+    # ---- --full only from here on: the legs beyond the headline, each a run of its own ------------------------------------
     # ---- the other arithmetics on the same workload ------------------------------------------------------------------
     # f64: the FP64-MFMA path (fewer steps: ~85 ms each); i8x: the 38/31-bit int8-limb pass (learn()'s default)
     others = {}
     for prec, skip, nsteps in (("f64", args.no_f64, max(3, min(20, args.steps // 10))), ("i8x", args.no_i8x, max(3, min(50, args.steps // 4))),
                                ("i8w", True, 0)):
-        if skip or prec == args.precision:
+        if not args.full or skip or prec == args.precision:
             continue
         e_o, _, km_o, f_o, g_o = timed(prec, nsteps, 1)
         rf_o, _ = pass_roofline(km_o, K, n, nloc, prec)
@@ -363,7 +371,7 @@ def main():
     # gml_objgrad_batch does by default).  The evaluation point of this benchmark -- the rows of the generating model -- is sparse
     # (15 couplings + a field per node), so a 32-row tile sweeps 32-48 of the 1024 columns; the integer sums and therefore all results
     # are the same bits.  NOT the headline: `value` prices the contraction over all columns, which is what a dense Theta costs.
-    if args.precision in LIMBS and not args.no_sparse_theta:
+    if args.full and args.precision in LIMBS and not args.no_sparse_theta:
         import ctypes
         Lb = gml._lib.lib()
         Lb.gml_test_tune.restype = ctypes.c_double
@@ -397,7 +405,7 @@ def main():
         (t_, per_rank_), st_, o_ = sorted(runs, key=lambda r: r[0][0])[len(runs) // 2]
         return t_, per_rank_, st_, o_, [r[0][0] for r in runs]
 
-    if not args.no_learn:
+    if args.full and not args.no_learn:
         t_learn, learn_per_rank, st, out, runs_s = learn_leg(args.precision, 3)
         extra["learn_wall_runs_s"] = runs_s
         if world > 1:
@@ -440,7 +448,7 @@ def main():
     # ---- N > 1: the front door of the process-per-GPU route, learn(samples, RISE(), HIP(distributed=True)) from a HOST matrix that
     # only rank 0 holds: rank 0 packs it once (1 bit per spin), the bits go out by one broadcast (RCCL over xGMI), every rank builds
     # its handle from them, solves its node range, and the rows are all-gathered (start / end collectives)
-    if world > 1 and not args.no_learn and not args.no_host_learn:
+    if world > 1 and args.full and not args.no_learn and not args.no_host_learn:
         hist = None
         if rank == 0:
             sp = prob.spins()
@@ -467,7 +475,7 @@ def main():
     # ---- learn() from a HOST histogram: what a `learn(samples, RISE(), HIP())` caller pays (pack + upload +
     # solve + gather + symmetrise).  The samples as the reference holds them: a column-major Matrix{Int64}, K x (1+n)
     # (sampling.jl:52-54), 8.2 GB at this config.  Rank 0 of a 1-GPU run only (the matrix is built from the device's samples).
-    if rank == 0 and world == 1 and not args.no_learn and not args.no_host_learn:
+    if rank == 0 and world == 1 and args.full and not args.no_learn and not args.no_host_learn:
         avail_gb = 0.0
         try:
             avail_gb = [int(ln.split()[1]) for ln in open("/proc/meminfo") if ln.startswith("MemAvailable")][0] / 1e6
@@ -506,7 +514,7 @@ def main():
     # run only).  A PROJECTION of the N = 8 line, clearly not a measurement of it: no second device, no RCCL, no contention for the host.
     # It exists because the one thing that does not scale with the node count -- the latency-bound direction phase of a small shard -- can
     # be measured on one GPU, and because an 8-GPU node is not always available to the driver (SCALE_r01..r04 are skip records).
-    if rank == 0 and world == 1 and not args.no_learn and not args.no_shards and n % 8 == 0 and "learn_wall_s" in extra:
+    if rank == 0 and world == 1 and args.full and not args.no_learn and not args.no_shards and n % 8 == 0 and "learn_wall_s" in extra:
         parts, shard = 8, []
         for r8 in range(parts):
             a0, a1 = r8 * n // parts, (r8 + 1) * n // parts
@@ -532,7 +540,7 @@ def main():
     # ---- one pass over a WEIGHTED histogram (rank 0 of a 1-GPU run only): non-uniform counts take the weight-loading template
     # of the forward kernel (UNIW = false); the timed region above runs the uniform-weight one (every count equal) -----------
     spins = None
-    if rank == 0 and world == 1 and not (args.no_cpu and args.no_weighted):
+    if rank == 0 and world == 1 and args.full and not (args.no_cpu and args.no_weighted):
         spins = prob.spins()  # the K x n configurations the GPU path works on
     if spins is not None and not args.no_weighted:
         counts_w = 1.0 + (np.arange(K) % 3)
@@ -550,7 +558,7 @@ def main():
 
     # ---- CPU baseline (rank 0 of a 1-GPU run only) -----------------------------------------------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         from oracle import oracle as O
         hc = O.host_cpus()
         threads = hc["threads"]

@@ -65,3 +65,29 @@ def test_bench_dump_is_the_operator_at_the_seeded_inputs(tmp_path, gpus):
         f0, g0 = p.objgrad("RISE", np.arange(n), J, precision="i8w")
     assert np.abs(f - f0).max() <= 1e-12 * np.abs(f0).max()
     assert np.abs(g - g0).max() <= 1e-12
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    assert not bench.parse_args().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--no-cpu"])
+    a = bench.parse_args()
+    assert a.full and a.no_cpu and not a.no_learn
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only():
+    # no --full: set up, warm up, the timed steps, the line -- none of the legs that take runs of their own
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--spins", "256", "--samples", "50000"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["dtype"] == "i8w" and line["higher_is_better"] is True
+    assert line["unit"] == "node-evals/s" and line["value"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 256) <= 1e-6 * 256  # node evaluations per second of the timed steps
+    assert line["roofline"]["fwd_ms"] > 0 and line["roofline"]["bwd_ms"] > 0 and "pcie_inclusive_ms_per_step" not in line["roofline"]
+    assert line["f64"] is None and line["i8x"] is None and line["cpu_baseline"] is None
+    for key in ("value_f64", "value_i8x", "sparse_theta", "learn_wall_s", "learn_from_host", "projection_8gpu", "weighted",
+                "ms_per_step_weighted"):
+        assert key not in line, key

@@ -97,11 +97,11 @@ def test_two_rank_hip_solver_matches_single_process(tmp_path):
 @pytest.mark.gpu
 def test_bench_two_ranks_on_the_gpu_box():
     # bench.py --gpus 2 end to end on the 1-GPU box: its own launcher, both ranks on device 0, node-sharded passes,
-    # learn() and the gather; a small problem so that it takes seconds
+    # learn() and the gather (legs of a --full run); a small problem so that it takes seconds
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--spins", "256", "--samples", "50000", "--no-cpu"], env=env, capture_output=True, text=True, timeout=900)
+                        "--spins", "256", "--samples", "50000", "--full", "--no-cpu"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["nodes_per_gpu"] == 128 and len(line["per_rank_ms_per_step"]) == 2
