@@ -84,6 +84,7 @@ def lib():
     L.gml_problem_create_sampled.argtypes = [p, i64, i64, C.c_uint64, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_create_sampled_terms.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_create_mcmc_terms.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
+    L.gml_problem_create_mcmc_chains.argtypes = [p, i64, i64, i64, i32, i32, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -234,11 +235,29 @@ class Problem:
     """RAII wrapper of a gml_problem handle (packed spins + weights resident in HBM)."""
 
     def __init__(self, samples=None, *, counts=None, spins=None, packed=None, model=None, terms=None, n=None, num_samples=None,
-                 seed=0, mcmc_sweeps=None, order=2, node_range=None, device=0, ingest="host", histogram=False):
+                 seed=0, mcmc_sweeps=None, order=2, node_range=None, device=0, ingest="host", histogram=False, burn_in=None, thin=None,
+                 samples_per_chain=None):
         """histogram=True (sampled handles, n <= 64): the handle holds the distinct configurations with their counts
-        (gml_problem_create_sampled_hist: sorted and run-length encoded on the device), not one row per draw."""
+        (gml_problem_create_sampled_hist: sorted and run-length encoded on the device), not one row per draw.
+        burn_in / thin / samples_per_chain (with model=): num_samples // samples_per_chain Glauber chains of a pairwise model on the
+        int8 matrix cores, each recorded samples_per_chain times (gml_problem_create_mcmc_chains; defaults 200, 10, 1)."""
         L = lib()
         h = C.c_void_p()
+        if burn_in is not None or thin is not None or samples_per_chain is not None:
+            if model is None or terms is not None or samples is not None or spins is not None or packed is not None:
+                raise GMLError(GML_EINVAL, "burn_in / thin / samples_per_chain apply to a pairwise model given as model=")
+            spc = 1 if samples_per_chain is None else int(samples_per_chain)
+            if spc < 1 or num_samples is None or int(num_samples) % spc != 0:
+                raise GMLError(GML_EINVAL, f"num_samples must be a positive multiple of samples_per_chain ({spc})")
+            m = np.ascontiguousarray(model, dtype=np.float64)
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise GMLError(GML_EINVAL, "the model matrix must be square")
+            n = m.shape[0]
+            n0, n1 = node_range if node_range is not None else (0, n)
+            check(L.gml_problem_create_mcmc_chains(_ptr(m), n, int(num_samples) // spc, spc, int(200 if burn_in is None else burn_in),
+                                                   int(10 if thin is None else thin), int(seed), int(bool(histogram)), int(order), n0,
+                                                   n1, int(device), C.byref(h)))
+            model, histogram = None, False
         if histogram and (samples is not None or spins is not None or packed is not None):
             raise GMLError(GML_EINVAL, "histogram=True applies to handles sampled on the device (model= or terms=)")
         if histogram and model is not None and terms is None:
@@ -255,7 +274,9 @@ class Problem:
             n, model = m.shape[0], None
             if not terms:
                 terms = {(1,): 0.0}
-        if packed is not None:
+        if h.value:
+            pass  # made above (Glauber chains on the matrix cores)
+        elif packed is not None:
             # (sign_bits [n][words] uint32, counts [K] or None, K): the packed form (pack_histogram / sign_bits())
             bits, cnt, K = packed
             bits = np.ascontiguousarray(bits, dtype=np.uint32)

@@ -189,6 +189,15 @@ void launch_bits_from_keys(const unsigned long long *dkeys, int64_t K, int64_t n
 void launch_glauber(const int *dioff, const double *diw, const int *dooff, const int *doth, int64_t n, int64_t N, int64_t Np,
                     int sweeps, unsigned long long seed, int8_t *dSt, hipStream_t st);
 
+// Glauber chains of a dense pairwise model on the int8 matrix cores (gml_mcmc_chains.hip): the quantised model (digit planes Dg,
+// the blocks' own q, diagonal, scales, row sums of q), burn_in + (spc - 1) thin sweeps, the recorded states into out [n][ld].
+// A workgroup's chain tile is mcmc_chains_tile(n) chains (0: n too large), its state kMcmcChainsLds bytes at most.
+constexpr int64_t kMcmcChainsLds = 128 * 1024;
+constexpr int64_t kMcmcChainsMaxN = 16384;
+int mcmc_chains_tile(int64_t n);
+void launch_mcmc_chains(const int8_t *dDg, const double *dqblk, const double *ddiag, const double *dsig, const double *dqsum, int64_t n,
+                        int64_t chains, int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout, int64_t ld, hipStream_t st);
+
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].
 // faces: the orthant-face re-solves inside the kernel (working-set columns F [R][cap], iterates X [R][Qp] and their column kinds,

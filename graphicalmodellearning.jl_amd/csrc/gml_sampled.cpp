@@ -254,6 +254,123 @@ static int create_mcmc_terms(const int32_t *keys, int key_stride, const double *
     return gml_create_from_device_bytes(p, dSt, true, Np, nullptr, out, dedupe); // the chains' final states, spin-major
 }
 
+// gml_problem_create_mcmc_chains: Glauber chains of a dense pairwise model on the int8 matrix cores (gml_mcmc_chains.hip).  The
+// model is quantised here, row by row: sigma_i = 2^(e - 38) with max_{j != i} |A_ij| < 2^e, q_ij = rint(A_ij / sigma_i), q_ii = 0,
+// held in 5 balanced base-256 digit planes (include/gml.h).
+extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in,
+                                              int thin, uint64_t seed, int histogram, int order, int64_t node0, int64_t node1, int device,
+                                              gml_problem **out) {
+    if (!out) return fail(GML_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!model) return fail(GML_EINVAL, "model is NULL");
+    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
+    if (chains < 1 || samples_per_chain < 1 || burn_in < 1 || thin < 1)
+        return fail(GML_EINVAL, "chains, samples_per_chain, burn_in and thin must be at least 1");
+    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
+    if (node0 < 0 || node1 > n || node0 >= node1)
+        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
+    if (samples_per_chain > (int64_t)1 << 40 || chains > ((int64_t)1 << 40) / samples_per_chain)
+        return fail(GML_EINVAL, "chains * samples_per_chain is too large");
+    if ((int64_t)burn_in + (samples_per_chain - 1) * (int64_t)thin > INT32_MAX)
+        return fail(GML_EINVAL, "burn_in + (samples_per_chain - 1) * thin exceeds 2^31 - 1 sweeps");
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j <= i; ++j) {
+            const double v = model[i * n + j];
+            if (!std::isfinite(v)) return fail(GML_EINVAL, "the model matrix is not finite at (%lld,%lld)", (long long)i, (long long)j);
+            if (v != model[j * n + i])
+                return fail(GML_EINVAL, "the model matrix is not symmetric at (%lld,%lld)", (long long)i, (long long)j);
+        }
+    const int64_t M = chains * samples_per_chain;
+    if (n > kMcmcChainsMaxN || mcmc_chains_tile(n) == 0)
+        return fail(GML_EUNSUPPORTED, "the int8 chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN, (long long)n);
+    if (histogram && n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
+    if (histogram && M >= ((int64_t)1 << 31)) return fail(GML_EUNSUPPORTED, "histogramming on the device needs fewer than 2^31 samples");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    // quantisation; the digit planes pre-tiled as the kernel reads them: fragment (b, kt, l) = [64 lanes][16 B], lane (il, hh) byte t
+    // = digit l of q[32 b + il][32 kt + 16 hh + t]
+    const int64_t nb = (n + 31) / 32, np = 32 * nb;
+    std::vector<int8_t> dg((size_t)(5 * np * np), 0);
+    std::vector<double> qblk((size_t)(nb * 1024), 0.0), diag((size_t)np, 0.0), sig((size_t)np, 0.0), qsum((size_t)np, 0.0);
+    for (int64_t i = 0; i < n; ++i) {
+        const double *row = model + i * n;
+        double mx = 0.0;
+        for (int64_t j = 0; j < n; ++j)
+            if (j != i) mx = std::max(mx, std::fabs(row[j]));
+        int ex = 0;
+        if (mx > 0) (void)std::frexp(mx, &ex);
+        diag[(size_t)i] = row[i];
+        sig[(size_t)i] = std::ldexp(1.0, ex - 38);
+        const int64_t b = i >> 5, il = i & 31;
+        long long qs = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            if (j == i) continue;
+            long long q = (long long)std::nearbyint(std::ldexp(row[j], 38 - ex));
+            qs += q;
+            if ((j >> 5) == b) qblk[(size_t)(b * 1024 + il * 32 + (j & 31))] = (double)q;
+            const int64_t kt = j >> 5, lane = ((j >> 4) & 1) * 32 + il, t = j & 15;
+            int8_t *d = dg.data() + ((b * nb + kt) * 5 * 64 + lane) * 16 + t;
+            for (int l = 0; l < 5; ++l) {
+                const long long dgt = ((q + 128) & 255) - 128;
+                q = (q - dgt) >> 8;
+                d[l * 1024] = (int8_t)dgt;
+            }
+        }
+        qsum[(size_t)i] = (double)qs;
+    }
+    HIPCHK(hipSetDevice(device));
+    gml_problem *p = new gml_problem();
+    p->device = device;
+    p->n = n;
+    p->K = M;
+    p->M = (double)M;
+    p->order = order;
+    p->node0 = node0;
+    p->node1 = node1;
+    hipStream_t st = nullptr;
+    const int64_t ld = round_up(M, 256);
+    int8_t *dOut = nullptr, *dDg = nullptr;
+    double *dq = nullptr, *dd = nullptr, *ds = nullptr, *dsum = nullptr;
+    auto cleanup = [&](int rc) {
+        void *ptrs[] = {dDg, dq, dd, ds, dsum};
+        for (void *q : ptrs)
+            if (q) (void)dev_free(q);
+        if (st) (void)hipStreamDestroy(st);
+        return rc;
+    };
+#define SCHK(expr)                                                                                              \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess) {                                                                                 \
+            if (dOut) (void)dev_free(dOut);                                                                      \
+            delete p;                                                                                           \
+            return cleanup(fail(e_ == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", #expr,      \
+                                hipGetErrorString(e_)));                                                        \
+        }                                                                                                       \
+    } while (0)
+    SCHK(hipStreamCreate(&st));
+    SCHK(dev_malloc(&dOut, (size_t)n * ld));
+    SCHK(dev_malloc(&dDg, dg.size()));
+    SCHK(dev_malloc(&dq, sizeof(double) * qblk.size()));
+    SCHK(dev_malloc(&dd, sizeof(double) * np));
+    SCHK(dev_malloc(&ds, sizeof(double) * np));
+    SCHK(dev_malloc(&dsum, sizeof(double) * np));
+    SCHK(hipMemcpyAsync(dDg, dg.data(), dg.size(), hipMemcpyHostToDevice, st));
+    SCHK(hipMemcpyAsync(dq, qblk.data(), sizeof(double) * qblk.size(), hipMemcpyHostToDevice, st));
+    SCHK(hipMemcpyAsync(dd, diag.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
+    SCHK(hipMemcpyAsync(ds, sig.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
+    SCHK(hipMemcpyAsync(dsum, qsum.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
+    SCHK(hipMemsetAsync(dOut, 0, (size_t)n * ld, st));
+    launch_mcmc_chains(dDg, dq, dd, ds, dsum, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, dOut, ld, st);
+    SCHK(hipGetLastError());
+    SCHK(hipStreamSynchronize(st));
+#undef SCHK
+    cleanup(0);
+    return gml_create_from_device_bytes(p, dOut, true, ld, nullptr, out, histogram != 0); // the recorded states, spin-major
+}
+
 extern "C" int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,
                                              int64_t n, int64_t N, uint64_t seed, int sweeps, int order, int64_t node0,
                                              int64_t node1, int device, gml_problem **out) {

@@ -8,6 +8,7 @@
 // PCIe upload).  Random numbers: a counter-based splitmix64 hash of (seed, block, sample).
 #include "../../include/gml.h"
 #include "gml_dev.h"
+#include "gml_rng.h"
 
 namespace gml {
 
@@ -74,14 +75,6 @@ __global__ __launch_bounds__(1024) void k_block_cdf(const double *__restrict__ e
     __syncthreads();
     const double inv = 1.0 / total;
     for (int64_t i = b0; i < b1; ++i) cdf[i] *= inv;
-}
-
-__device__ __forceinline__ double u01(unsigned long long seed, unsigned long long block, unsigned long long k) {
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (k + 1) + 0xD1B54A32D192ED03ull * (block + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
 }
 
 // one thread per sample: CDF inversion by binary search, spins written sample-major

@@ -24,6 +24,16 @@ class Glauber(GMSampler):
         self.sweeps = int(sweeps)
 
 
+class GlauberChains(GMSampler):
+    """Not in the reference: long heat-bath chains of a PAIRWISE model on the int8 matrix cores
+    (gml_problem_create_mcmc_chains): N // samples_per_chain chains, each burnt in for `burn_in` sweeps and then recorded
+    every `thin` sweeps, samples_per_chain times.  Its cost is n^2 per chain-sweep whatever the density, so it serves dense
+    models (SK-type glasses, learned models) at the sizes learn() handles; sparse and multi-body models stay on Glauber."""
+
+    def __init__(self, burn_in=200, thin=10, samples_per_chain=1):
+        self.burn_in, self.thin, self.samples_per_chain = int(burn_in), int(thin), int(samples_per_chain)
+
+
 def _problem_args(model):
     """Keyword arguments of _lib.Problem for a model: matrix (order <= 2, :98-99) or term list (:100-101)."""
     if isinstance(model, FactorGraph):
@@ -41,7 +51,14 @@ def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, devic
     """sample(gm, N) -> histogram matrix [count, s_1..s_n], one row per observed configuration
     (sampling.jl:52-54); sample(gm, N, replicates) -> list of such matrices (:91)."""
     args = _problem_args(model)
-    if isinstance(sampler, Glauber):
+    if isinstance(sampler, GlauberChains):
+        if "model" not in args:
+            raise ValueError("GlauberChains samples pairwise models (order <= 2) only; use Glauber for multi-body models")
+        if int(number_sample) % sampler.samples_per_chain != 0:
+            raise ValueError(f"the number of samples ({number_sample}) must be a multiple of samples_per_chain "
+                             f"({sampler.samples_per_chain})")
+        args.update(burn_in=sampler.burn_in, thin=sampler.thin, samples_per_chain=sampler.samples_per_chain)
+    elif isinstance(sampler, Glauber):
         if "model" in args:  # the chains run on term lists
             fg = model if isinstance(model, FactorGraph) else FactorGraph(np.asarray(model, dtype=np.float64))
             args = {"terms": fg.terms, "n": fg.varible_count, "order": 2}

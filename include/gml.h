@@ -224,6 +224,33 @@ int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const dou
                                   int64_t node1, int device, gml_problem **out);
 
 /*
+ * gml_problem_create_mcmc_chains -- long Glauber chains of a dense PAIRWISE model on the int8 matrix cores, several recorded
+ * samples per chain.  `model` is the n x n symmetric matrix of FactorGraph(matrix) (diagonal = fields), as in
+ * gml_problem_create_sampled.  The chain is the one of gml_problem_create_mcmc_terms on the term list {(i,j): A_ij, i < j; (i): A_ii}:
+ *   start:    spin i of chain c is +1 iff u01(seed, 0xFFFFFFFF, c n + i) < 0.5;
+ *   sweep sw (0-based, burn-in included) updates the spins 0 .. n-1 in order (spins before i carry their new values):
+ *             u = u01(seed, sw, c n + i),  s_i = +1 iff u < 1.0 / (1.0 + exp(-2.0 h_i)),
+ * with u01 the samplers' counter-based splitmix64 hash (53 bits).  The fields use a fixed quantisation of the couplings, row by
+ * row: A_ij = sigma_i q_ij with sigma_i = 2^(e - 38), max_{j != i} |A_ij| < 2^e (e = 0 for a row without couplings), q_ij =
+ * rint(A_ij / sigma_i) (to nearest, ties to even) held in 5 balanced int8 digit planes, q_ii = 0, and
+ *   h_i = A_ii + sigma_i * (double) sum_{j != i} q_ij s_j,
+ * where the integer sum is exact (|sum| < n 2^38) and converts to FP64 exactly.  The samples therefore depend only on the model,
+ * seed, burn_in, thin, samples_per_chain and the chain index -- not on the kernel's chain tile, the grid or the device.  With
+ * samples_per_chain = 1, row c is what gml_problem_create_mcmc_terms gives for chain c at sweeps = burn_in, up to the quantisation
+ * (a decision whose u lies within ~1e-10 of its probability can differ).
+ * Recorded: chain c's state after burn_in + t thin completed sweeps (t = 0 .. samples_per_chain-1) is row t chains + c, count 1,
+ * M = chains samples_per_chain.  histogram != 0 (n <= 64): the handle holds the distinct configurations with their counts, as in
+ * gml_problem_create_sampled_hist.
+ * Cost: n^2 per chain-sweep (5 int8 planes on the matrix cores) WHATEVER the model's density; a sparse model stays cheaper on
+ * gml_problem_create_mcmc_terms, whose cost grows with the degree of a spin.
+ * GML_EINVAL (checked before any HIP call): NULL pointers, a non-symmetric or non-finite model, chains, samples_per_chain, burn_in
+ * or thin below 1, a bad order or node range.  GML_EUNSUPPORTED: n > 16384 (the kernel's limit), histogram with n > 64.
+ */
+int gml_problem_create_mcmc_chains(const double *model, int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in, int thin,
+                                   uint64_t seed, int histogram, int order, int64_t node0, int64_t node1, int device,
+                                   gml_problem **out);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
