@@ -85,6 +85,8 @@ def lib():
     L.gml_problem_create_sampled_terms.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_create_mcmc_terms.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_create_mcmc_chains.argtypes = [p, i64, i64, i64, i32, i32, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
+    L.gml_problem_create_mcmc_terms_chains.argtypes = [p, i32, p, i64, i64, i64, i64, i32, i32, C.c_uint64, i32, i32, i64, i64, i32,
+                                                       C.POINTER(p)]
     L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -236,13 +238,26 @@ class Problem:
 
     def __init__(self, samples=None, *, counts=None, spins=None, packed=None, model=None, terms=None, n=None, num_samples=None,
                  seed=0, mcmc_sweeps=None, order=2, node_range=None, device=0, ingest="host", histogram=False, burn_in=None, thin=None,
-                 samples_per_chain=None):
+                 samples_per_chain=None, mcmc_thin=None, mcmc_samples_per_chain=None):
         """histogram=True (sampled handles, n <= 64): the handle holds the distinct configurations with their counts
         (gml_problem_create_sampled_hist: sorted and run-length encoded on the device), not one row per draw.
         burn_in / thin / samples_per_chain (with model=): num_samples // samples_per_chain Glauber chains of a pairwise model on the
-        int8 matrix cores, each recorded samples_per_chain times (gml_problem_create_mcmc_chains; defaults 200, 10, 1)."""
+        int8 matrix cores, each recorded samples_per_chain times (gml_problem_create_mcmc_chains; defaults 200, 10, 1).
+        mcmc_thin / mcmc_samples_per_chain (with terms=; either one, even 1, selects it): num_samples // mcmc_samples_per_chain
+        Glauber chains of the term list with exact integer fields, burnt in for mcmc_sweeps sweeps (required) and then recorded every
+        mcmc_thin sweeps (gml_problem_create_mcmc_terms_chains; defaults thin 10, samples per chain 1).  mcmc_sweeps alone: one
+        sample per chain (gml_problem_create_mcmc_terms)."""
         L = lib()
         h = C.c_void_p()
+        term_chains = mcmc_thin is not None or mcmc_samples_per_chain is not None
+        if term_chains:
+            if terms is None or model is not None or samples is not None or spins is not None or packed is not None:
+                raise GMLError(GML_EINVAL, "mcmc_thin / mcmc_samples_per_chain apply to a term list given as terms=")
+            if not mcmc_sweeps:
+                raise GMLError(GML_EINVAL, "mcmc_thin / mcmc_samples_per_chain need mcmc_sweeps (the burn-in)")
+            tc_spc = 1 if mcmc_samples_per_chain is None else int(mcmc_samples_per_chain)
+            if tc_spc < 1 or num_samples is None or int(num_samples) < 1 or int(num_samples) % tc_spc != 0:
+                raise GMLError(GML_EINVAL, f"num_samples must be a positive multiple of mcmc_samples_per_chain ({tc_spc})")
         if burn_in is not None or thin is not None or samples_per_chain is not None:
             if model is None or terms is not None or samples is not None or spins is not None or packed is not None:
                 raise GMLError(GML_EINVAL, "burn_in / thin / samples_per_chain apply to a pairwise model given as model=")
@@ -313,7 +328,12 @@ class Problem:
                     keys[t, :len(k)] = np.asarray(k, dtype=np.int64) - 1
                     wts[t] = v
             n0, n1 = node_range if node_range is not None else (0, int(n))
-            if histogram:
+            if term_chains:  # thinned chains with exact integer fields (any order, any sparsity)
+                check(L.gml_problem_create_mcmc_terms_chains(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples) // tc_spc,
+                                                             tc_spc, int(mcmc_sweeps), int(10 if mcmc_thin is None else mcmc_thin),
+                                                             int(seed), int(bool(histogram)), int(order), n0, n1, int(device),
+                                                             C.byref(h)))
+            elif histogram:
                 check(L.gml_problem_create_sampled_hist(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples), int(seed),
                                                         int(mcmc_sweeps or 0), int(order), n0, n1, int(device), C.byref(h)))
             elif mcmc_sweeps:  # Glauber chains instead of exact enumeration (components above 22 spins)

@@ -198,6 +198,22 @@ int mcmc_chains_tile(int64_t n);
 void launch_mcmc_chains(const int8_t *dDg, const double *dqblk, const double *ddiag, const double *dsig, const double *dqsum, int64_t n,
                         int64_t chains, int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout, int64_t ld, hipStream_t st);
 
+// Glauber chains of any term list with exact integer fields (gml_term_chains.hip).  Spin i's record: its field sum a, scale sig,
+// Q = sum_e q_e and the word offsets of its incidences grouped by arity: those with k other spins (k = 1 .. 7) are the records
+// [off[k-1], off[k]) of the stream, k + 1 words each: the int64 q_e 2^24 + j_1 (low word first), then j_2 .. j_k.
+struct TermChainSpin {
+    double a, sig;
+    long long Q;
+    long long off[8];
+};
+constexpr int kTermChainsMaxOthers = 7;
+// the chain tile of a workgroup for n spins and `chains` chains (0: n too large); g_term_chains_tile (gml_testhooks.cpp), when
+// set to 64, 128 or 256 and the state fits, forces it
+extern int g_term_chains_tile;
+int term_chains_tile(int64_t n, int64_t chains);
+void launch_term_chains(const TermChainSpin *dspin, const unsigned *drec, int64_t n, int64_t chains, int burn_in, int thin, int spc,
+                        unsigned long long seed, int8_t *dout, int64_t ld, hipStream_t st);
+
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].
 // faces: the orthant-face re-solves inside the kernel (working-set columns F [R][cap], iterates X [R][Qp] and their column kinds,

@@ -158,21 +158,11 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
     return gml_create_from_device_bytes(p, dS, false, 0, nullptr, out, dedupe);
 }
 
-static int create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t N, uint64_t seed,
-                             int sweeps, int order, int64_t node0, int64_t node1, int device, gml_problem **out, bool dedupe) {
-    if (!out) return fail(GML_EINVAL, "out is NULL");
-    *out = nullptr;
-    if ((nterms > 0 && (!keys || !weights)) || key_stride < 1) return fail(GML_EINVAL, "NULL or malformed term list");
-    if (n <= 0 || N <= 0 || sweeps < 1) return fail(GML_EINVAL, "n, N and sweeps must be positive");
-    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
-    if (node0 < 0 || node1 > n || node0 >= node1)
-        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    // incidence lists: for every spin the terms it belongs to (weight + the other spins; a spin named twice cancels)
-    std::vector<std::vector<std::pair<double, std::vector<int>>>> inc((size_t)n);
+// Incidence lists of a term list (create_mcmc_terms, gml_problem_create_mcmc_terms_chains): for every spin the terms it belongs
+// to, in term order (weight + the other spins; a spin named twice cancels, zero-weight terms are skipped).
+using Incidences = std::vector<std::vector<std::pair<double, std::vector<int>>>>;
+static int build_incidences(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, Incidences &inc) {
+    inc.assign((size_t)n, {});
     for (int64_t t = 0; t < nterms; ++t) {
         if (!std::isfinite(weights[t])) return fail(GML_EINVAL, "weight of term %lld is not finite", (long long)t);
         std::vector<int> sp;
@@ -192,6 +182,24 @@ static int create_mcmc_terms(const int32_t *keys, int key_stride, const double *
             inc[(size_t)sp[a]].emplace_back(weights[t], std::move(others));
         }
     }
+    return GML_OK;
+}
+
+static int create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t N, uint64_t seed,
+                             int sweeps, int order, int64_t node0, int64_t node1, int device, gml_problem **out, bool dedupe) {
+    if (!out) return fail(GML_EINVAL, "out is NULL");
+    *out = nullptr;
+    if ((nterms > 0 && (!keys || !weights)) || key_stride < 1) return fail(GML_EINVAL, "NULL or malformed term list");
+    if (n <= 0 || N <= 0 || sweeps < 1) return fail(GML_EINVAL, "n, N and sweeps must be positive");
+    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
+    if (node0 < 0 || node1 > n || node0 >= node1)
+        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    Incidences inc;
+    if (int rc = build_incidences(keys, key_stride, weights, nterms, n, inc)) return rc;
     std::vector<int> ioff((size_t)n + 1, 0), ooff(1, 0), oth;
     std::vector<double> iw;
     for (int64_t i = 0; i < n; ++i) {
@@ -364,6 +372,143 @@ extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, in
     SCHK(hipMemcpyAsync(dsum, qsum.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
     SCHK(hipMemsetAsync(dOut, 0, (size_t)n * ld, st));
     launch_mcmc_chains(dDg, dq, dd, ds, dsum, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, dOut, ld, st);
+    SCHK(hipGetLastError());
+    SCHK(hipStreamSynchronize(st));
+#undef SCHK
+    cleanup(0);
+    return gml_create_from_device_bytes(p, dOut, true, ld, nullptr, out, histogram != 0); // the recorded states, spin-major
+}
+
+// gml_problem_create_mcmc_terms_chains: thinned Glauber chains of any term list with exact integer fields (gml_term_chains.hip).
+// The couplings of every spin are quantised here: sigma_i = 2^(E - 38) with max_e |w_e| < 2^E over its incidences with other spins,
+// q_e = rint(w_e / sigma_i), and the incidences grouped by arity into the record stream of TermChainSpin (gml_dev.h).
+extern "C" int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                                    int64_t chains, int64_t samples_per_chain, int burn_in, int thin, uint64_t seed,
+                                                    int histogram, int order, int64_t node0, int64_t node1, int device, gml_problem **out) {
+    if (!out) return fail(GML_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!keys || !weights || key_stride < 1 || nterms < 0) return fail(GML_EINVAL, "NULL or malformed term list");
+    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
+    if (chains < 1 || samples_per_chain < 1 || burn_in < 1 || thin < 1)
+        return fail(GML_EINVAL, "chains, samples_per_chain, burn_in and thin must be at least 1");
+    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
+    if (node0 < 0 || node1 > n || node0 >= node1)
+        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
+    if (samples_per_chain > (int64_t)1 << 40 || chains > ((int64_t)1 << 40) / samples_per_chain)
+        return fail(GML_EINVAL, "chains * samples_per_chain is too large");
+    if ((int64_t)burn_in + (samples_per_chain - 1) * (int64_t)thin > INT32_MAX)
+        return fail(GML_EINVAL, "burn_in + (samples_per_chain - 1) * thin exceeds 2^31 - 1 sweeps");
+    for (int64_t t = 0; t < nterms; ++t) {
+        if (!std::isfinite(weights[t])) return fail(GML_EINVAL, "weight of term %lld is not finite", (long long)t);
+        for (int a = 0; a < key_stride; ++a) {
+            const int32_t v = keys[t * key_stride + a];
+            if (v < -1 || v >= n) return fail(GML_EINVAL, "term %lld names spin %d outside [0,%lld)", (long long)t, v, (long long)n);
+        }
+    }
+    const int64_t M = chains * samples_per_chain;
+    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
+        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
+                    (long long)n);
+    if (histogram && n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
+    if (histogram && M >= ((int64_t)1 << 31)) return fail(GML_EUNSUPPORTED, "histogramming on the device needs fewer than 2^31 samples");
+    {   // the kernel's limits: distinct spins per term, incidences with other spins per spin
+        std::vector<int64_t> cnt((size_t)n, 0);
+        std::vector<int> sp;
+        for (int64_t t = 0; t < nterms; ++t) {
+            if (weights[t] == 0.0) continue;
+            sp.clear();
+            for (int a = 0; a < key_stride; ++a) {
+                const int32_t v = keys[t * key_stride + a];
+                if (v < 0) continue;
+                auto itv = std::find(sp.begin(), sp.end(), (int)v);
+                if (itv != sp.end()) sp.erase(itv);
+                else sp.push_back((int)v);
+            }
+            if (sp.size() > (size_t)kTermChainsMaxOthers + 1)
+                return fail(GML_EUNSUPPORTED, "term %lld names %zu distinct spins: the term-list chain kernel supports at most %d",
+                            (long long)t, sp.size(), kTermChainsMaxOthers + 1);
+            if (sp.size() > 1)
+                for (int v : sp)
+                    if (++cnt[(size_t)v] >= ((int64_t)1 << 24))
+                        return fail(GML_EUNSUPPORTED, "spin %d has 2^24 or more incidences with other spins: the term-list chain kernel "
+                                                      "supports fewer than 2^24", v);
+        }
+    }
+    Incidences inc;
+    if (int rc = build_incidences(keys, key_stride, weights, nterms, n, inc)) return rc;
+    // per spin: a_i, sigma_i, Q_i and the records grouped by arity (q_e 2^24 + j_1 as two words, then j_2 .. j_k)
+    std::vector<TermChainSpin> spin((size_t)n);
+    std::vector<unsigned> rec;
+    for (int64_t i = 0; i < n; ++i) {
+        TermChainSpin &r = spin[(size_t)i];
+        double a = 0.0, mx = 0.0;
+        for (auto &e : inc[(size_t)i]) {
+            if (e.second.empty()) a += e.first;
+            else mx = std::max(mx, std::fabs(e.first));
+        }
+        int ex = 0;
+        if (mx > 0) (void)std::frexp(mx, &ex);
+        r.a = a;
+        r.sig = std::ldexp(1.0, ex - 38);
+        long long Q = 0;
+        r.off[0] = (long long)rec.size();
+        for (int k = 1; k <= kTermChainsMaxOthers; ++k) {
+            for (auto &e : inc[(size_t)i]) {
+                if (e.second.size() != (size_t)k) continue;
+                const long long q = (long long)std::nearbyint(std::ldexp(e.first, 38 - ex));
+                Q += q;
+                const unsigned long long P = ((unsigned long long)q << 24) | (unsigned long long)e.second[0];
+                rec.push_back((unsigned)P);
+                rec.push_back((unsigned)(P >> 32));
+                for (int m = 1; m < k; ++m) rec.push_back((unsigned)e.second[(size_t)m]);
+            }
+            r.off[k] = (long long)rec.size();
+        }
+        r.Q = Q;
+    }
+    if (rec.empty()) rec.push_back(0u);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    gml_problem *p = new gml_problem();
+    p->device = device;
+    p->n = n;
+    p->K = M;
+    p->M = (double)M;
+    p->order = order;
+    p->node0 = node0;
+    p->node1 = node1;
+    hipStream_t st = nullptr;
+    const int64_t ld = round_up(M, 256);
+    int8_t *dOut = nullptr;
+    TermChainSpin *dspin = nullptr;
+    unsigned *drec = nullptr;
+    auto cleanup = [&](int rc) {
+        if (dspin) (void)dev_free(dspin);
+        if (drec) (void)dev_free(drec);
+        if (st) (void)hipStreamDestroy(st);
+        return rc;
+    };
+#define SCHK(expr)                                                                                              \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess) {                                                                                 \
+            if (dOut) (void)dev_free(dOut);                                                                      \
+            delete p;                                                                                           \
+            return cleanup(fail(e_ == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", #expr,      \
+                                hipGetErrorString(e_)));                                                        \
+        }                                                                                                       \
+    } while (0)
+    SCHK(hipStreamCreate(&st));
+    SCHK(dev_malloc(&dOut, (size_t)n * ld));
+    SCHK(dev_malloc(&dspin, sizeof(TermChainSpin) * spin.size()));
+    SCHK(dev_malloc(&drec, sizeof(unsigned) * rec.size()));
+    SCHK(hipMemcpyAsync(dspin, spin.data(), sizeof(TermChainSpin) * spin.size(), hipMemcpyHostToDevice, st));
+    SCHK(hipMemcpyAsync(drec, rec.data(), sizeof(unsigned) * rec.size(), hipMemcpyHostToDevice, st));
+    SCHK(hipMemsetAsync(dOut, 0, (size_t)n * ld, st));
+    launch_term_chains(dspin, drec, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, dOut, ld, st);
     SCHK(hipGetLastError());
     SCHK(hipStreamSynchronize(st));
 #undef SCHK

@@ -21,6 +21,7 @@ using namespace gml;
 namespace gml {
 double g_hv_sparse_ratio = 0.3; // (config 5 at the default regulariser: 25.6 s never, 23.6 s at 0.3 and at 0.6)
 std::atomic<long long> g_hv_sparse_calls{0}; // (every part of a gml_multi_learn counts from its own host thread)
+int g_term_chains_tile = 0;                   // 0: the rule of term_chains_tile (gml_term_chains.hip)
 double g_tune[GML_NTUNE] = {};               // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
 // the kernel instances the int8-limb launchers have run (gml_i8.h: kI8InstBits)
 static std::atomic<uint64_t> g_i8_inst[(kI8InstBits + 63) / 64];
@@ -43,6 +44,14 @@ extern "C" double gml_test_tune(int id, double value) {
     if (id < 0 || id >= GML_NTUNE) return NAN;
     const double old = g_tune[id];
     g_tune[id] = value;
+    return old;
+}
+// forces the chain tile of the term-list chain kernel (64, 128 or 256 chains; 0 = its rule); returns the old value, -1 for another T.
+// A forced tile whose state does not fit the kernel's LDS budget is not used.  Set between calls only
+extern "C" int gml_test_term_chains_tile(int T) {
+    if (T != 0 && T != 64 && T != 128 && T != 256) return -1;
+    const int old = g_term_chains_tile;
+    g_term_chains_tile = T;
     return old;
 }
 extern "C" double gml_test_hv_sparse_ratio(double ratio) {

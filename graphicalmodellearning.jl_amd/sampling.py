@@ -1,7 +1,9 @@
 """sample(model, N): host mirror of the reference's sampler front door (src/sampling.jl:90-106) on top of
 the on-device exact sampler (gml_problem_create_sampled / _sampled_terms).  Any interaction order; every
 connected component of the term hypergraph must have at most 22 spins (the reference enumerates all 2^n
-states of the whole model, which limits it to n ~ 25)."""
+states of the whole model, which limits it to n ~ 25).  Beyond that, Markov chains on the device: Glauber (one sample per
+chain), GlauberChains (long thinned chains of dense pairwise models) and GlauberTermChains (long thinned chains of any term
+list)."""
 import numpy as np
 
 from . import _lib
@@ -28,7 +30,19 @@ class GlauberChains(GMSampler):
     """Not in the reference: long heat-bath chains of a PAIRWISE model on the int8 matrix cores
     (gml_problem_create_mcmc_chains): N // samples_per_chain chains, each burnt in for `burn_in` sweeps and then recorded
     every `thin` sweeps, samples_per_chain times.  Its cost is n^2 per chain-sweep whatever the density, so it serves dense
-    models (SK-type glasses, learned models) at the sizes learn() handles; sparse and multi-body models stay on Glauber."""
+    models (SK-type glasses, learned models) at the sizes learn() handles; sparse and multi-body models go to GlauberTermChains."""
+
+    def __init__(self, burn_in=200, thin=10, samples_per_chain=1):
+        self.burn_in, self.thin, self.samples_per_chain = int(burn_in), int(thin), int(samples_per_chain)
+
+
+class GlauberTermChains(GMSampler):
+    """Not in the reference: long heat-bath chains of ANY term list (any order up to 8, any sparsity; n <= 16384)
+    (gml_problem_create_mcmc_terms_chains): N // samples_per_chain chains, each burnt in for `burn_in` sweeps and then recorded
+    every `thin` sweeps, samples_per_chain times.  Couplings are quantised per spin to 2^-38 of its largest one and the fields
+    summed exactly, so the draws depend only on the model, the seed and these three numbers; on a pairwise model they are the
+    draws of GlauberChains, bit for bit.  Its cost per chain-sweep follows the number of incidences (sparse models, lattices,
+    multi-body models learned by multiRISE / ISODUS)."""
 
     def __init__(self, burn_in=200, thin=10, samples_per_chain=1):
         self.burn_in, self.thin, self.samples_per_chain = int(burn_in), int(thin), int(samples_per_chain)
@@ -58,6 +72,14 @@ def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, devic
             raise ValueError(f"the number of samples ({number_sample}) must be a multiple of samples_per_chain "
                              f"({sampler.samples_per_chain})")
         args.update(burn_in=sampler.burn_in, thin=sampler.thin, samples_per_chain=sampler.samples_per_chain)
+    elif isinstance(sampler, GlauberTermChains):
+        if "model" in args:  # the chains run on term lists
+            fg = model if isinstance(model, FactorGraph) else FactorGraph(np.asarray(model, dtype=np.float64))
+            args = {"terms": fg.terms, "n": fg.varible_count, "order": 2}
+        if int(number_sample) % sampler.samples_per_chain != 0:
+            raise ValueError(f"the number of samples ({number_sample}) must be a multiple of samples_per_chain "
+                             f"({sampler.samples_per_chain})")
+        args.update(mcmc_sweeps=sampler.burn_in, mcmc_thin=sampler.thin, mcmc_samples_per_chain=sampler.samples_per_chain)
     elif isinstance(sampler, Glauber):
         if "model" in args:  # the chains run on term lists
             fg = model if isinstance(model, FactorGraph) else FactorGraph(np.asarray(model, dtype=np.float64))

@@ -251,6 +251,35 @@ int gml_problem_create_mcmc_chains(const double *model, int64_t n, int64_t chain
                                    gml_problem **out);
 
 /*
+ * gml_problem_create_mcmc_terms_chains -- long Glauber chains of ANY term list (any order up to 8, any sparsity), several recorded
+ * samples per chain, with exact integer fields.  The term list is that of gml_problem_create_mcmc_terms (keys: 0-based spins, -1 =
+ * unused slot).  Every term contributes one incidence to each of its spins; a spin named twice in a key cancels (s^2 = 1);
+ * zero-weight terms are skipped.  For spin i:
+ *   a_i       the FP64 sum, left to right in term order, of the weights of its incidences with NO other spin (0 if none);
+ *   sigma_i   2^(E - 38), where max |w_e| < 2^E over its incidences e WITH other spins (frexp; E = 0 if there are none);
+ *   q_e       rint(w_e / sigma_i) (nearbyint: to nearest, ties to even) -- the rule gml_problem_create_mcmc_chains applies to a row;
+ *   h_i       a_i + sigma_i * (double) sum_e q_e prod_{j in others(e)} s_j, the integer sum exact in int64 (|q| <= 2^38, fewer than
+ *             2^24 incidences per spin) and converted to double once.
+ * Start state, scan order, update and random stream are those of gml_problem_create_mcmc_chains:
+ *   start:    spin i of chain c is +1 iff u01(seed, 0xFFFFFFFF, c n + i) < 0.5;
+ *   sweep sw (0-based, burn-in included) updates the spins 0 .. n-1 in order (spins before i carry their new values):
+ *             pup = 1.0 / (1.0 + exp(-2.0 * h_i)),  s_i = +1 iff u01(seed, sw, c n + i) < pup.
+ * Recorded: chain c's state after burn_in + t thin completed sweeps (t = 0 .. samples_per_chain-1) is row t chains + c, count 1,
+ * M = chains samples_per_chain.  The samples depend only on (model, seed, burn_in, thin, samples_per_chain, chain index): not on the
+ * order of the terms with other spins, how incidences are grouped, the kernel's chain tile, the grid or the device.  On the term list
+ * of a pairwise matrix ({(i,j): A_ij, i < j; (i): A_ii}) h_i is the double gml_problem_create_mcmc_chains computes, and the samples
+ * are bit-identical to it.  histogram != 0 (n <= 64, M < 2^31): the handle holds the distinct configurations with their counts.
+ * Cost: one LDS read per other spin of every incidence, per chain-sweep -- it follows the model's sparsity.
+ * GML_EINVAL (checked before any HIP call): NULL pointers, key_stride < 1, a spin outside [0, n), a non-finite weight; chains,
+ * samples_per_chain, burn_in or thin below 1; burn_in + (samples_per_chain - 1) thin > 2^31 - 1 or chains samples_per_chain
+ * > 2^40; a bad order or node range.  GML_EUNSUPPORTED (before any HIP call, the limit named): n > 16384, a term with more than 8
+ * distinct spins after cancellation, 2^24 or more incidences with other spins on one spin, histogram with n > 64.
+ */
+int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                         int64_t chains, int64_t samples_per_chain, int burn_in, int thin, uint64_t seed, int histogram,
+                                         int order, int64_t node0, int64_t node1, int device, gml_problem **out);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
