@@ -233,6 +233,11 @@ def terms_rank(n, order, symmetrize, key0):
     return int(lib().gml_terms_rank(int(n), int(order), int(bool(symmetrize)), _ptr(k), len(k)))
 
 
+def _node_range(node_range, n):
+    """(node0, node1) of a handle: the given range, by default every node."""
+    return node_range if node_range is not None else (0, int(n))
+
+
 class Problem:
     """RAII wrapper of a gml_problem handle (packed spins + weights resident in HBM)."""
 
@@ -268,7 +273,7 @@ class Problem:
             if m.ndim != 2 or m.shape[0] != m.shape[1]:
                 raise GMLError(GML_EINVAL, "the model matrix must be square")
             n = m.shape[0]
-            n0, n1 = node_range if node_range is not None else (0, n)
+            n0, n1 = _node_range(node_range, n)
             check(L.gml_problem_create_mcmc_chains(_ptr(m), n, int(num_samples) // spc, spc, int(200 if burn_in is None else burn_in),
                                                    int(10 if thin is None else thin), int(seed), int(bool(histogram)), int(order), n0,
                                                    n1, int(device), C.byref(h)))
@@ -298,7 +303,7 @@ class Problem:
             if cnt is not None:
                 cnt = np.ascontiguousarray(cnt, dtype=np.float64)
             n = bits.shape[0]
-            n0, n1 = node_range if node_range is not None else (0, n)
+            n0, n1 = _node_range(node_range, n)
             check(L.gml_problem_create_packed(_ptr(bits), bits.shape[1], _ptr(cnt), int(K), n, int(order), n0, n1, int(device),
                                               C.byref(h)))
         elif terms is not None:
@@ -327,7 +332,7 @@ class Problem:
                 for t, (k, v) in enumerate(terms.items()):
                     keys[t, :len(k)] = np.asarray(k, dtype=np.int64) - 1
                     wts[t] = v
-            n0, n1 = node_range if node_range is not None else (0, int(n))
+            n0, n1 = _node_range(node_range, n)
             if term_chains:  # thinned chains with exact integer fields (any order, any sparsity)
                 check(L.gml_problem_create_mcmc_terms_chains(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples) // tc_spc,
                                                              tc_spc, int(mcmc_sweeps), int(10 if mcmc_thin is None else mcmc_thin),
@@ -346,12 +351,12 @@ class Problem:
             # sample on the device from a pairwise model (n x n, diagonal = fields): sampling.jl:34-57
             m = np.ascontiguousarray(model, dtype=np.float64)
             n = m.shape[0]
-            n0, n1 = node_range if node_range is not None else (0, n)
+            n0, n1 = _node_range(node_range, n)
             check(L.gml_problem_create_sampled(_ptr(m), n, int(num_samples), int(seed), int(order), n0, n1, int(device),
                                                C.byref(h)))
         elif samples is not None:
             s, dt, K, n, ld, cm = _hist_args(samples)
-            n0, n1 = node_range if node_range is not None else (0, n)
+            n0, n1 = _node_range(node_range, n)
             # ingest: "host" = packed on the host, bits uploaded (default); "device" = raw upload, converted on the device
             create = {"host": L.gml_problem_create, "device": L.gml_problem_create_device_convert}[ingest]
             check(create(_ptr(s), dt, K, n, ld, cm, int(order), n0, n1, int(device), C.byref(h)))
@@ -360,7 +365,7 @@ class Problem:
             K, n = spins.shape
             if counts is not None:
                 counts = np.ascontiguousarray(counts, dtype=np.float64)
-            n0, n1 = node_range if node_range is not None else (0, n)
+            n0, n1 = _node_range(node_range, n)
             check(L.gml_problem_create_spins(_ptr(counts), _ptr(spins), K, n, int(order), n0, n1, int(device),
                                              C.byref(h)))
         self._h = h

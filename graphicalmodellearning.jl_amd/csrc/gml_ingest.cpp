@@ -174,16 +174,25 @@ static int prob_images(gml_problem *p) {
     return GML_OK;
 }
 
-int gml_check_create_args(int64_t K, int64_t n, int order, int64_t node0, int64_t node1, int device) {
-    if (K <= 0 || n <= 0) return fail(GML_EINVAL, "empty histogram (K=%lld, n=%lld)", (long long)K, (long long)n);
+int gml_check_handle_args(int64_t n, int order, int64_t node0, int64_t node1) {
     if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
     if (node0 < 0 || node1 > n || node0 >= node1)
         return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
+    return GML_OK;
+}
+
+int gml_check_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
     if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
     return GML_OK;
+}
+
+int gml_check_create_args(int64_t K, int64_t n, int order, int64_t node0, int64_t node1, int device) {
+    if (K <= 0 || n <= 0) return fail(GML_EINVAL, "empty histogram (K=%lld, n=%lld)", (long long)K, (long long)n);
+    if (int rc = gml_check_handle_args(n, order, node0, node1)) return rc;
+    return gml_check_device(device);
 }
 
 gml_problem *gml_new_problem(int64_t K, int64_t n, double M, int order, int64_t node0, int64_t node1, int device) {

@@ -100,6 +100,9 @@ int gml_create_parts(const void *samples, int dtype, int64_t K, int64_t n, int64
 int64_t gml_binom(int64_t n, int64_t k);
 bool gml_next_comb(std::vector<int> &idx, int64_t n);
 void gml_node_cols(const gml_problem *p, int64_t u, std::vector<int32_t> &cols);
+// the arguments of every creator: order and node range (no HIP call), the device lookup, and both after the histogram's shape
+int gml_check_handle_args(int64_t n, int order, int64_t node0, int64_t node1);
+int gml_check_device(int device);
 int gml_check_create_args(int64_t K, int64_t n, int order, int64_t node0, int64_t node1, int device);
 gml_problem *gml_new_problem(int64_t K, int64_t n, double M, int order, int64_t node0, int64_t node1, int device);
 int gml_create_from_device_bytes(gml_problem *p, int8_t *dbytes, bool spin_major, int64_t ld, const double *counts, gml_problem **out,

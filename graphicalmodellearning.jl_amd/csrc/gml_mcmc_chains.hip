@@ -22,7 +22,7 @@
 #include "../../include/gml.h"
 #include "gml_dev.h"
 #include "gml_i8.h"
-#include "gml_rng.h"
+#include "gml_chain.h"
 
 namespace gml {
 
@@ -55,16 +55,10 @@ __global__ __launch_bounds__(256) void k_mcmc_chains(const int8_t *__restrict__ 
     const int CT = blockDim.x, tid = threadIdx.x, lane = tid & 63, lr = lane & 31, h = lane >> 5;
     const int wc = tid & ~63;                          // the wave's first chain in the tile
     const int64_t c = (int64_t)blockIdx.x * CT + tid; // the chain this lane updates (chains beyond `chains` run but are not stored)
-    for (int b = 0; b < nb; ++b) {
-        unsigned word = 0;
-        for (int i = 0; i < 32 && 32 * b + i < n; ++i)
-            if (!(u01(seed, 0xFFFFFFFFull, (unsigned long long)(c * n + 32 * b + i)) < 0.5)) word |= 1u << i;
-        bits[b * CT + tid] = word;
-    }
+    for (int b = 0; b < nb; ++b) bits[b * CT + tid] = chain_start_word(seed, c, n, b);
     const int sweeps = burn_in + (spc - 1) * thin;
     for (int sw = 0; sw < sweeps; ++sw) {
-        // the counter word of spin s in this sweep is z0 + kU01Step s  (u01(seed, sw, c n + s), gml_rng.h)
-        const unsigned long long z0 = seed + kU01Step * ((unsigned long long)(c * n) + 1ull) + kU01Stream * ((unsigned long long)sw + 1ull);
+        const unsigned long long z0 = chain_z0(seed, c, n, sw);
         for (int b = 0; b < nb; ++b) {
             v16i acc[2][5];
 #pragma unroll
@@ -119,9 +113,7 @@ __global__ __launch_bounds__(256) void k_mcmc_chains(const int8_t *__restrict__ 
                 double f = (i & 4) ? S[1][4 * (i >> 3) + (i & 3)] : S[0][4 * (i >> 3) + (i & 3)];
 #pragma unroll
                 for (int j = 0; j < i; ++j) f = fma(qb[i * 32 + j], dl[j], f);
-                const double field = diag[s] + sig[s] * f;
-                const double pup = 1.0 / (1.0 + exp(-2.0 * field));
-                const unsigned neg = u01_mix(zb + kU01Step * (unsigned long long)i) < pup ? 0u : 1u;
+                const unsigned neg = chain_heat_bath(zb, (unsigned long long)i, diag[s] + sig[s] * f);
                 const unsigned old = (word >> i) & 1u;
                 dl[i] = 2.0 * (double)((int)old - (int)neg);
                 word ^= (old ^ neg) << i;
@@ -129,14 +121,7 @@ __global__ __launch_bounds__(256) void k_mcmc_chains(const int8_t *__restrict__ 
             bits[b * CT + tid] = word;
             __syncthreads(); // not for data (every wave owns its chains): keeps the waves on the same digit fragments (L1 reuse)
         }
-        const int done = sw + 1;
-        if (done >= burn_in && (done - burn_in) % thin == 0 && c < chains) {
-            int8_t *o = out + (int64_t)((done - burn_in) / thin) * chains + c;
-            for (int b = 0; b < nb; ++b) {
-                const unsigned word = bits[b * CT + tid];
-                for (int i = 0; i < 32 && 32 * b + i < n; ++i) o[(int64_t)(32 * b + i) * ld] = (word >> i) & 1u ? (int8_t)-1 : (int8_t)1;
-            }
-        }
+        chain_record(sw + 1, burn_in, thin, c, chains, n, nb, bits + tid, CT, out, ld);
     }
 }
 

@@ -21,24 +21,24 @@ using namespace gml;
 static int64_t round_up(int64_t a, int64_t b) { return gml_round_up(a, b); }
 
 // ------------------------------------------------------------------------------------------
-// gml_problem_create_sampled: sample on the device, then build the handle from the device-resident
-// samples (the step before the path; src/sampling.jl:34-57, 94-106)
+// Argument checks shared by the creators below.  All of them come before the device lookup (gml_check_device), so a bad argument
+// is GML_EINVAL / GML_EUNSUPPORTED on every machine, with or without a GPU.
 // ------------------------------------------------------------------------------------------
-// Terms of one model: spins of term t = keys[t*stride .. +stride) (0-based, -1 = unused slot).
-static int create_sampled_terms(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n,
-                                int64_t N, uint64_t seed, int order, int64_t node0, int64_t node1, int device,
-                                gml_problem **out, bool dedupe = false) {
+static int check_out(gml_problem **out) {
     if (!out) return fail(GML_EINVAL, "out is NULL");
     *out = nullptr;
-    if ((nterms > 0 && (!keys || !weights)) || stride < 1) return fail(GML_EINVAL, "NULL or malformed term list");
-    if (n <= 0 || N <= 0) return fail(GML_EINVAL, "n and N must be positive");
-    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
-    if (node0 < 0 || node1 > n || node0 >= node1)
-        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    return GML_OK;
+}
+
+// Terms of one model: spins of term t = keys[t*stride .. +stride) (0-based, -1 = unused slot).  strict (the term chains): NULL
+// pointers and a negative count are refused for an empty list too.
+static int check_term_pointers(const int32_t *keys, int stride, const double *weights, int64_t nterms, bool strict = false) {
+    const bool null = !keys || !weights;
+    if (stride < 1 || (null && (strict || nterms > 0)) || (strict && nterms < 0)) return fail(GML_EINVAL, "NULL or malformed term list");
+    return GML_OK;
+}
+
+static int check_term_values(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n) {
     for (int64_t t = 0; t < nterms; ++t) {
         if (!std::isfinite(weights[t])) return fail(GML_EINVAL, "weight of term %lld is not finite", (long long)t);
         for (int a = 0; a < stride; ++a) {
@@ -46,6 +46,142 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
             if (v < -1 || v >= n) return fail(GML_EINVAL, "term %lld names spin %d outside [0,%lld)", (long long)t, v, (long long)n);
         }
     }
+    return GML_OK;
+}
+
+// The distinct spins of one key after cancellation (a spin named twice cancels: s^2 = 1), in the order that fixes the record stream
+// of the term chains and the FP64 summation order of k_glauber.  Returns a spin the key names (cancelled or not), -1 for the empty key.
+static int reduce_key(const int32_t *key, int stride, std::vector<int> &sp) {
+    sp.clear();
+    int named = -1;
+    for (int a = 0; a < stride; ++a) {
+        const int v = key[a];
+        if (v < 0) continue;
+        named = v;
+        auto itv = std::find(sp.begin(), sp.end(), v);
+        if (itv != sp.end()) sp.erase(itv);
+        else sp.push_back(v);
+    }
+    return named;
+}
+
+// the shape of a run of thinned chains; the handle arguments sit where both chain creators have always checked them
+static int check_chain_args(int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in, int thin, int order, int64_t node0,
+                            int64_t node1) {
+    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
+    if (chains < 1 || samples_per_chain < 1 || burn_in < 1 || thin < 1)
+        return fail(GML_EINVAL, "chains, samples_per_chain, burn_in and thin must be at least 1");
+    if (int rc = gml_check_handle_args(n, order, node0, node1)) return rc;
+    if (samples_per_chain > (int64_t)1 << 40 || chains > ((int64_t)1 << 40) / samples_per_chain)
+        return fail(GML_EINVAL, "chains * samples_per_chain is too large");
+    if ((int64_t)burn_in + (samples_per_chain - 1) * (int64_t)thin > INT32_MAX)
+        return fail(GML_EINVAL, "burn_in + (samples_per_chain - 1) * thin exceeds 2^31 - 1 sweeps");
+    return GML_OK;
+}
+
+static int check_hist_spins(int64_t n) {
+    if (n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
+    return GML_OK;
+}
+static int check_hist_limits(int64_t n, int64_t M) {
+    if (int rc = check_hist_spins(n)) return rc;
+    if (M >= ((int64_t)1 << 31)) return fail(GML_EUNSUPPORTED, "histogramming on the device needs fewer than 2^31 samples");
+    return GML_OK;
+}
+
+static int check_symmetric_finite(const double *model, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j <= i; ++j) {
+            const double v = model[i * n + j];
+            if (!std::isfinite(v)) return fail(GML_EINVAL, "the model matrix is not finite at (%lld,%lld)", (long long)i, (long long)j);
+            if (v != model[j * n + i])
+                return fail(GML_EINVAL, "the model matrix is not symmetric at (%lld,%lld)", (long long)i, (long long)j);
+        }
+    return GML_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// What a creator holds on the device while its sampler runs: the stream, the handle under construction, the sampler's output bytes
+// and every temporary buffer.  begin, upload / alloc, the launches, finish; the destructor frees whatever finish has not handed on,
+// on every path.  The first failed call is kept in rc (codes and texts as HIPCHK) and makes the later ones no-ops.
+// ------------------------------------------------------------------------------------------
+struct SamplerStaging {
+    hipStream_t st = nullptr;
+    gml_problem *p = nullptr;
+    int8_t *out = nullptr; // the draws as +-1 bytes
+    std::vector<void *> tmp;
+    int rc = GML_OK;
+
+    SamplerStaging() = default;
+    SamplerStaging(const SamplerStaging &) = delete;
+    SamplerStaging &operator=(const SamplerStaging &) = delete;
+    ~SamplerStaging() {
+        release();
+        if (out) (void)dev_free(out);
+        delete p;
+    }
+    bool ok(hipError_t e, const char *call) {
+        if (rc == GML_OK && e != hipSuccess)
+            rc = fail(e == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", call, hipGetErrorString(e));
+        return rc == GML_OK;
+    }
+    // the handle's K rows of n spins; out_bytes of output, cleared if the sampler does not write all of them
+    int begin(int device, int64_t K, int64_t n, int order, int64_t node0, int64_t node1, size_t out_bytes, bool clear) {
+        if (!ok(hipSetDevice(device), "hipSetDevice")) return rc;
+        p = gml_new_problem(K, n, (double)K, order, node0, node1, device);
+        if (ok(hipStreamCreate(&st), "hipStreamCreate") && ok(dev_malloc(&out, out_bytes), "dev_malloc") && clear)
+            ok(hipMemsetAsync(out, 0, out_bytes, st), "hipMemsetAsync");
+        return rc;
+    }
+    template <class T> T *alloc(size_t count) {
+        T *d = nullptr;
+        if (rc != GML_OK || !ok(dev_malloc(&d, sizeof(T) * count), "dev_malloc")) return nullptr;
+        tmp.push_back(d);
+        return d;
+    }
+    template <class T> void copy(T *dst, const std::vector<T> &v) {
+        if (rc == GML_OK && !v.empty()) ok(hipMemcpyAsync(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+    }
+    template <class T> T *upload(const std::vector<T> &v) {
+        T *d = alloc<T>(v.size());
+        copy(d, v);
+        return rc == GML_OK ? d : nullptr;
+    }
+    // after the launches: their errors, and the stream drained (the host vectors behind the uploads may go)
+    int sync() {
+        if (ok(hipGetLastError(), "the sampler's launch")) ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+        return rc;
+    }
+    void release() {
+        for (void *q : tmp) (void)dev_free(q);
+        tmp.clear();
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr;
+    }
+    // the handle from the output bytes (sample-major [K][n] or, spin_major, [n][ld]); gml_create_from_device_bytes owns both from here
+    int finish(bool spin_major, int64_t ld, bool dedupe, gml_problem **result) {
+        if (sync()) return rc;
+        release();
+        gml_problem *q = p;
+        int8_t *bytes = out;
+        p = nullptr;
+        out = nullptr;
+        return gml_create_from_device_bytes(q, bytes, spin_major, ld, nullptr, result, dedupe);
+    }
+};
+
+// ------------------------------------------------------------------------------------------
+// gml_problem_create_sampled: sample on the device, then build the handle from the device-resident
+// samples (the step before the path; src/sampling.jl:34-57, 94-106)
+// ------------------------------------------------------------------------------------------
+static int create_sampled_terms(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n,
+                                int64_t N, uint64_t seed, int order, int64_t node0, int64_t node1, int device,
+                                gml_problem **out, bool dedupe = false) {
+    if (int rc = check_out(out)) return rc;
+    if (int rc = check_term_pointers(keys, stride, weights, nterms)) return rc;
+    if (n <= 0 || N <= 0) return fail(GML_EINVAL, "n and N must be positive");
+    if (int rc = gml_check_handle_args(n, order, node0, node1)) return rc;
+    if (int rc = check_term_values(keys, stride, weights, nterms, n)) return rc;
     // connected components of the term hypergraph
     std::vector<int64_t> parent((size_t)n);
     for (int64_t i = 0; i < n; ++i) parent[i] = i;
@@ -85,96 +221,46 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
     std::vector<std::vector<unsigned>> bmask(blocks.size());
     std::vector<std::vector<double>> bwt(blocks.size());
     size_t maxnt = 1;
+    std::vector<int> sp;
     for (int64_t t = 0; t < nterms; ++t) {
         if (weights[t] == 0.0) continue;
+        const int named = reduce_key(keys + t * stride, stride, sp);
+        if (named < 0) continue; // the empty term: a constant energy
         unsigned mask = 0;
-        int64_t any = -1;
-        for (int a = 0; a < stride; ++a) {
-            const int32_t v = keys[t * stride + a];
-            if (v < 0) continue;
-            mask ^= 1u << local[(size_t)v];
-            any = v;
-        }
-        if (any < 0) continue; // the empty term: a constant energy
-        const size_t b = (size_t)id[find(any)];
+        for (int v : sp) mask |= 1u << local[(size_t)v];
+        const size_t b = (size_t)id[find(named)];
         bmask[b].push_back(mask);
         bwt[b].push_back(weights[t]);
         maxnt = std::max(maxnt, bmask[b].size());
     }
-    HIPCHK(hipSetDevice(device));
-    gml_problem *p = new gml_problem();
-    p->device = device;
-    p->n = n;
-    p->K = N;
-    p->M = (double)N;
-    p->order = order;
-    p->node0 = node0;
-    p->node1 = node1;
-    hipStream_t st = nullptr;
-    int8_t *dS = nullptr;
-    double *dwt = nullptr, *den = nullptr, *dcdf = nullptr;
-    unsigned *dmask = nullptr;
-    int *dmem = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dwt) (void)dev_free(dwt);
-        if (dmask) (void)dev_free(dmask);
-        if (den) (void)dev_free(den);
-        if (dcdf) (void)dev_free(dcdf);
-        if (dmem) (void)dev_free(dmem);
-        if (st) (void)hipStreamDestroy(st);
-        return rc;
-    };
-#define SCHK(expr)                                                                                              \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) {                                                                                 \
-            if (dS) (void)dev_free(dS);                                                                          \
-            delete p;                                                                                           \
-            return cleanup(fail(e_ == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", #expr,      \
-                                hipGetErrorString(e_)));                                                        \
-        }                                                                                                       \
-    } while (0)
-    SCHK(hipStreamCreate(&st));
-    SCHK(dev_malloc(&dS, (size_t)N * n));
-    SCHK(dev_malloc(&dwt, sizeof(double) * maxnt));
-    SCHK(dev_malloc(&dmask, sizeof(unsigned) * maxnt));
-    SCHK(dev_malloc(&den, sizeof(double) * ((size_t)1 << maxsb)));
-    SCHK(dev_malloc(&dcdf, sizeof(double) * ((size_t)1 << maxsb)));
-    SCHK(dev_malloc(&dmem, sizeof(int) * maxsb));
+    if (int rc = gml_check_device(device)) return rc;
+    SamplerStaging s;
+    if (int rc = s.begin(device, N, n, order, node0, node1, (size_t)N * n, false)) return rc;
+    double *dwt = s.alloc<double>(maxnt);
+    unsigned *dmask = s.alloc<unsigned>(maxnt);
+    double *den = s.alloc<double>((size_t)1 << maxsb), *dcdf = s.alloc<double>((size_t)1 << maxsb);
+    int *dmem = s.alloc<int>(maxsb);
     for (size_t b = 0; b < blocks.size(); ++b) {
-        const auto &mem = blocks[b];
-        const int sb = (int)mem.size(), nt = (int)bmask[b].size();
-        if (nt > 0) {
-            SCHK(hipMemcpyAsync(dmask, bmask[b].data(), sizeof(unsigned) * nt, hipMemcpyHostToDevice, st));
-            SCHK(hipMemcpyAsync(dwt, bwt[b].data(), sizeof(double) * nt, hipMemcpyHostToDevice, st));
-        }
-        SCHK(hipMemcpyAsync(dmem, mem.data(), sizeof(int) * sb, hipMemcpyHostToDevice, st));
-        launch_block_sampler(dmask, dwt, nt, sb, dmem, N, n, (unsigned long long)seed, (int)b, den, dcdf, dS, st);
-        SCHK(hipGetLastError());
-        SCHK(hipStreamSynchronize(st)); // the staging buffers are reused by the next block
+        s.copy(dmask, bmask[b]);
+        s.copy(dwt, bwt[b]);
+        s.copy(dmem, blocks[b]);
+        if (s.rc) break;
+        launch_block_sampler(dmask, dwt, (int)bmask[b].size(), (int)blocks[b].size(), dmem, N, n, (unsigned long long)seed, (int)b, den,
+                             dcdf, s.out, s.st);
+        if (s.sync()) break; // (the staging buffers are reused by the next block)
     }
-#undef SCHK
-    cleanup(0);
-    return gml_create_from_device_bytes(p, dS, false, 0, nullptr, out, dedupe);
+    return s.finish(false, 0, dedupe, out);
 }
 
 // Incidence lists of a term list (create_mcmc_terms, gml_problem_create_mcmc_terms_chains): for every spin the terms it belongs
 // to, in term order (weight + the other spins; a spin named twice cancels, zero-weight terms are skipped).
 using Incidences = std::vector<std::vector<std::pair<double, std::vector<int>>>>;
-static int build_incidences(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, Incidences &inc) {
-    inc.assign((size_t)n, {});
+static Incidences build_incidences(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n) {
+    Incidences inc((size_t)n);
+    std::vector<int> sp;
     for (int64_t t = 0; t < nterms; ++t) {
-        if (!std::isfinite(weights[t])) return fail(GML_EINVAL, "weight of term %lld is not finite", (long long)t);
-        std::vector<int> sp;
-        for (int a = 0; a < key_stride; ++a) {
-            const int32_t v = keys[t * key_stride + a];
-            if (v < -1 || v >= n) return fail(GML_EINVAL, "term %lld names spin %d outside [0,%lld)", (long long)t, v, (long long)n);
-            if (v < 0) continue;
-            auto itv = std::find(sp.begin(), sp.end(), (int)v);
-            if (itv != sp.end()) sp.erase(itv); // s^2 = 1
-            else sp.push_back((int)v);
-        }
         if (weights[t] == 0.0) continue;
+        reduce_key(keys + t * key_stride, key_stride, sp);
         for (size_t a = 0; a < sp.size(); ++a) {
             std::vector<int> others;
             for (size_t b = 0; b < sp.size(); ++b)
@@ -182,24 +268,18 @@ static int build_incidences(const int32_t *keys, int key_stride, const double *w
             inc[(size_t)sp[a]].emplace_back(weights[t], std::move(others));
         }
     }
-    return GML_OK;
+    return inc;
 }
 
 static int create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t N, uint64_t seed,
                              int sweeps, int order, int64_t node0, int64_t node1, int device, gml_problem **out, bool dedupe) {
-    if (!out) return fail(GML_EINVAL, "out is NULL");
-    *out = nullptr;
-    if ((nterms > 0 && (!keys || !weights)) || key_stride < 1) return fail(GML_EINVAL, "NULL or malformed term list");
+    if (int rc = check_out(out)) return rc;
+    if (int rc = check_term_pointers(keys, key_stride, weights, nterms)) return rc;
     if (n <= 0 || N <= 0 || sweeps < 1) return fail(GML_EINVAL, "n, N and sweeps must be positive");
-    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
-    if (node0 < 0 || node1 > n || node0 >= node1)
-        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    Incidences inc;
-    if (int rc = build_incidences(keys, key_stride, weights, nterms, n, inc)) return rc;
+    if (int rc = gml_check_handle_args(n, order, node0, node1)) return rc;
+    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
+    if (int rc = gml_check_device(device)) return rc;
+    const Incidences inc = build_incidences(keys, key_stride, weights, nterms, n);
     std::vector<int> ioff((size_t)n + 1, 0), ooff(1, 0), oth;
     std::vector<double> iw;
     for (int64_t i = 0; i < n; ++i) {
@@ -212,96 +292,28 @@ static int create_mcmc_terms(const int32_t *keys, int key_stride, const double *
     }
     if (iw.empty()) iw.push_back(0.0);
     if (oth.empty()) oth.push_back(0);
-    HIPCHK(hipSetDevice(device));
-    gml_problem *p = new gml_problem();
-    p->device = device;
-    p->n = n;
-    p->K = N;
-    p->M = (double)N;
-    p->order = order;
-    p->node0 = node0;
-    p->node1 = node1;
-    hipStream_t st = nullptr;
     const int64_t Np = round_up(N, 256);
-    int8_t *dSt = nullptr;
-    int *dioff = nullptr, *dooff = nullptr, *doth = nullptr;
-    double *diw = nullptr;
-    auto cleanup = [&](int rc) {
-        void *ptrs[] = {dioff, dooff, doth, diw};
-        for (void *q : ptrs)
-            if (q) (void)dev_free(q);
-        if (st) (void)hipStreamDestroy(st);
-        return rc;
-    };
-#define SCHK(expr)                                                                                              \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) {                                                                                 \
-            if (dSt) (void)dev_free(dSt);                                                                        \
-            delete p;                                                                                           \
-            return cleanup(fail(e_ == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", #expr,      \
-                                hipGetErrorString(e_)));                                                        \
-        }                                                                                                       \
-    } while (0)
-    SCHK(hipStreamCreate(&st));
-    SCHK(dev_malloc(&dSt, (size_t)n * Np));
-    SCHK(dev_malloc(&dioff, sizeof(int) * ioff.size()));
-    SCHK(dev_malloc(&dooff, sizeof(int) * ooff.size()));
-    SCHK(dev_malloc(&doth, sizeof(int) * oth.size()));
-    SCHK(dev_malloc(&diw, sizeof(double) * iw.size()));
-    SCHK(hipMemcpyAsync(dioff, ioff.data(), sizeof(int) * ioff.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(dooff, ooff.data(), sizeof(int) * ooff.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(doth, oth.data(), sizeof(int) * oth.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(diw, iw.data(), sizeof(double) * iw.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemsetAsync(dSt, 0, (size_t)n * Np, st));
-    launch_glauber(dioff, diw, dooff, doth, n, N, Np, sweeps, (unsigned long long)seed, dSt, st);
-    SCHK(hipGetLastError());
-    SCHK(hipStreamSynchronize(st));
-#undef SCHK
-    cleanup(0);
-    return gml_create_from_device_bytes(p, dSt, true, Np, nullptr, out, dedupe); // the chains' final states, spin-major
+    SamplerStaging s;
+    if (int rc = s.begin(device, N, n, order, node0, node1, (size_t)n * Np, true)) return rc;
+    const int *dioff = s.upload(ioff), *dooff = s.upload(ooff), *doth = s.upload(oth);
+    const double *diw = s.upload(iw);
+    if (s.rc) return s.rc;
+    launch_glauber(dioff, diw, dooff, doth, n, N, Np, sweeps, (unsigned long long)seed, s.out, s.st);
+    return s.finish(true, Np, dedupe, out); // the chains' final states, spin-major
 }
 
-// gml_problem_create_mcmc_chains: Glauber chains of a dense pairwise model on the int8 matrix cores (gml_mcmc_chains.hip).  The
-// model is quantised here, row by row: sigma_i = 2^(e - 38) with max_{j != i} |A_ij| < 2^e, q_ij = rint(A_ij / sigma_i), q_ii = 0,
-// held in 5 balanced base-256 digit planes (include/gml.h).
-extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in,
-                                              int thin, uint64_t seed, int histogram, int order, int64_t node0, int64_t node1, int device,
-                                              gml_problem **out) {
-    if (!out) return fail(GML_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (!model) return fail(GML_EINVAL, "model is NULL");
-    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
-    if (chains < 1 || samples_per_chain < 1 || burn_in < 1 || thin < 1)
-        return fail(GML_EINVAL, "chains, samples_per_chain, burn_in and thin must be at least 1");
-    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
-    if (node0 < 0 || node1 > n || node0 >= node1)
-        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
-    if (samples_per_chain > (int64_t)1 << 40 || chains > ((int64_t)1 << 40) / samples_per_chain)
-        return fail(GML_EINVAL, "chains * samples_per_chain is too large");
-    if ((int64_t)burn_in + (samples_per_chain - 1) * (int64_t)thin > INT32_MAX)
-        return fail(GML_EINVAL, "burn_in + (samples_per_chain - 1) * thin exceeds 2^31 - 1 sweeps");
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t j = 0; j <= i; ++j) {
-            const double v = model[i * n + j];
-            if (!std::isfinite(v)) return fail(GML_EINVAL, "the model matrix is not finite at (%lld,%lld)", (long long)i, (long long)j);
-            if (v != model[j * n + i])
-                return fail(GML_EINVAL, "the model matrix is not symmetric at (%lld,%lld)", (long long)i, (long long)j);
-        }
-    const int64_t M = chains * samples_per_chain;
-    if (n > kMcmcChainsMaxN || mcmc_chains_tile(n) == 0)
-        return fail(GML_EUNSUPPORTED, "the int8 chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN, (long long)n);
-    if (histogram && n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
-    if (histogram && M >= ((int64_t)1 << 31)) return fail(GML_EUNSUPPORTED, "histogramming on the device needs fewer than 2^31 samples");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    // quantisation; the digit planes pre-tiled as the kernel reads them: fragment (b, kt, l) = [64 lanes][16 B], lane (il, hh) byte t
-    // = digit l of q[32 b + il][32 kt + 16 hh + t]
+// The model of gml_problem_create_mcmc_chains, quantised row by row: sigma_i = 2^(e - 38) with max_{j != i} |A_ij| < 2^e, q_ij =
+// rint(A_ij / sigma_i), q_ii = 0, held in 5 balanced base-256 digit planes (include/gml.h).  The digit planes are pre-tiled as the
+// kernel reads them: fragment (b, kt, l) = [64 lanes][16 B], lane (il, hh) byte t = digit l of q[32 b + il][32 kt + 16 hh + t].
+struct QuantisedRows {
+    std::vector<int8_t> dg;
+    std::vector<double> qblk, diag, sig, qsum;
+};
+static QuantisedRows quantise_rows(const double *model, int64_t n) {
     const int64_t nb = (n + 31) / 32, np = 32 * nb;
-    std::vector<int8_t> dg((size_t)(5 * np * np), 0);
-    std::vector<double> qblk((size_t)(nb * 1024), 0.0), diag((size_t)np, 0.0), sig((size_t)np, 0.0), qsum((size_t)np, 0.0);
+    const std::vector<double> zero((size_t)np, 0.0);
+    QuantisedRows r{std::vector<int8_t>((size_t)(5 * np * np), 0), std::vector<double>((size_t)(nb * 1024), 0.0), zero, zero, zero};
+    auto &[dg, qblk, diag, sig, qsum] = r;
     for (int64_t i = 0; i < n; ++i) {
         const double *row = model + i * n;
         double mx = 0.0;
@@ -328,117 +340,40 @@ extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, in
         }
         qsum[(size_t)i] = (double)qs;
     }
-    HIPCHK(hipSetDevice(device));
-    gml_problem *p = new gml_problem();
-    p->device = device;
-    p->n = n;
-    p->K = M;
-    p->M = (double)M;
-    p->order = order;
-    p->node0 = node0;
-    p->node1 = node1;
-    hipStream_t st = nullptr;
-    const int64_t ld = round_up(M, 256);
-    int8_t *dOut = nullptr, *dDg = nullptr;
-    double *dq = nullptr, *dd = nullptr, *ds = nullptr, *dsum = nullptr;
-    auto cleanup = [&](int rc) {
-        void *ptrs[] = {dDg, dq, dd, ds, dsum};
-        for (void *q : ptrs)
-            if (q) (void)dev_free(q);
-        if (st) (void)hipStreamDestroy(st);
-        return rc;
-    };
-#define SCHK(expr)                                                                                              \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) {                                                                                 \
-            if (dOut) (void)dev_free(dOut);                                                                      \
-            delete p;                                                                                           \
-            return cleanup(fail(e_ == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", #expr,      \
-                                hipGetErrorString(e_)));                                                        \
-        }                                                                                                       \
-    } while (0)
-    SCHK(hipStreamCreate(&st));
-    SCHK(dev_malloc(&dOut, (size_t)n * ld));
-    SCHK(dev_malloc(&dDg, dg.size()));
-    SCHK(dev_malloc(&dq, sizeof(double) * qblk.size()));
-    SCHK(dev_malloc(&dd, sizeof(double) * np));
-    SCHK(dev_malloc(&ds, sizeof(double) * np));
-    SCHK(dev_malloc(&dsum, sizeof(double) * np));
-    SCHK(hipMemcpyAsync(dDg, dg.data(), dg.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(dq, qblk.data(), sizeof(double) * qblk.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(dd, diag.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(ds, sig.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(dsum, qsum.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
-    SCHK(hipMemsetAsync(dOut, 0, (size_t)n * ld, st));
-    launch_mcmc_chains(dDg, dq, dd, ds, dsum, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, dOut, ld, st);
-    SCHK(hipGetLastError());
-    SCHK(hipStreamSynchronize(st));
-#undef SCHK
-    cleanup(0);
-    return gml_create_from_device_bytes(p, dOut, true, ld, nullptr, out, histogram != 0); // the recorded states, spin-major
+    return r;
 }
 
-// gml_problem_create_mcmc_terms_chains: thinned Glauber chains of any term list with exact integer fields (gml_term_chains.hip).
-// The couplings of every spin are quantised here: sigma_i = 2^(E - 38) with max_e |w_e| < 2^E over its incidences with other spins,
-// q_e = rint(w_e / sigma_i), and the incidences grouped by arity into the record stream of TermChainSpin (gml_dev.h).
-extern "C" int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                                    int64_t chains, int64_t samples_per_chain, int burn_in, int thin, uint64_t seed,
-                                                    int histogram, int order, int64_t node0, int64_t node1, int device, gml_problem **out) {
-    if (!out) return fail(GML_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (!keys || !weights || key_stride < 1 || nterms < 0) return fail(GML_EINVAL, "NULL or malformed term list");
-    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
-    if (chains < 1 || samples_per_chain < 1 || burn_in < 1 || thin < 1)
-        return fail(GML_EINVAL, "chains, samples_per_chain, burn_in and thin must be at least 1");
-    if (order < 1 || order > 8) return fail(GML_EINVAL, "interaction order %d out of range [1,8]", order);
-    if (node0 < 0 || node1 > n || node0 >= node1)
-        return fail(GML_EINVAL, "bad node range [%lld,%lld) for n=%lld", (long long)node0, (long long)node1, (long long)n);
-    if (samples_per_chain > (int64_t)1 << 40 || chains > ((int64_t)1 << 40) / samples_per_chain)
-        return fail(GML_EINVAL, "chains * samples_per_chain is too large");
-    if ((int64_t)burn_in + (samples_per_chain - 1) * (int64_t)thin > INT32_MAX)
-        return fail(GML_EINVAL, "burn_in + (samples_per_chain - 1) * thin exceeds 2^31 - 1 sweeps");
-    for (int64_t t = 0; t < nterms; ++t) {
-        if (!std::isfinite(weights[t])) return fail(GML_EINVAL, "weight of term %lld is not finite", (long long)t);
-        for (int a = 0; a < key_stride; ++a) {
-            const int32_t v = keys[t * key_stride + a];
-            if (v < -1 || v >= n) return fail(GML_EINVAL, "term %lld names spin %d outside [0,%lld)", (long long)t, v, (long long)n);
-        }
-    }
+// gml_problem_create_mcmc_chains: Glauber chains of a dense pairwise model on the int8 matrix cores (gml_mcmc_chains.hip).
+extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in,
+                                              int thin, uint64_t seed, int histogram, int order, int64_t node0, int64_t node1, int device,
+                                              gml_problem **out) {
+    if (int rc = check_out(out)) return rc;
+    if (!model) return fail(GML_EINVAL, "model is NULL");
+    if (int rc = check_chain_args(n, chains, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
+    if (int rc = check_symmetric_finite(model, n)) return rc;
     const int64_t M = chains * samples_per_chain;
-    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
-        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
-                    (long long)n);
-    if (histogram && n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
-    if (histogram && M >= ((int64_t)1 << 31)) return fail(GML_EUNSUPPORTED, "histogramming on the device needs fewer than 2^31 samples");
-    {   // the kernel's limits: distinct spins per term, incidences with other spins per spin
-        std::vector<int64_t> cnt((size_t)n, 0);
-        std::vector<int> sp;
-        for (int64_t t = 0; t < nterms; ++t) {
-            if (weights[t] == 0.0) continue;
-            sp.clear();
-            for (int a = 0; a < key_stride; ++a) {
-                const int32_t v = keys[t * key_stride + a];
-                if (v < 0) continue;
-                auto itv = std::find(sp.begin(), sp.end(), (int)v);
-                if (itv != sp.end()) sp.erase(itv);
-                else sp.push_back((int)v);
-            }
-            if (sp.size() > (size_t)kTermChainsMaxOthers + 1)
-                return fail(GML_EUNSUPPORTED, "term %lld names %zu distinct spins: the term-list chain kernel supports at most %d",
-                            (long long)t, sp.size(), kTermChainsMaxOthers + 1);
-            if (sp.size() > 1)
-                for (int v : sp)
-                    if (++cnt[(size_t)v] >= ((int64_t)1 << 24))
-                        return fail(GML_EUNSUPPORTED, "spin %d has 2^24 or more incidences with other spins: the term-list chain kernel "
-                                                      "supports fewer than 2^24", v);
-        }
-    }
-    Incidences inc;
-    if (int rc = build_incidences(keys, key_stride, weights, nterms, n, inc)) return rc;
-    // per spin: a_i, sigma_i, Q_i and the records grouped by arity (q_e 2^24 + j_1 as two words, then j_2 .. j_k)
-    std::vector<TermChainSpin> spin((size_t)n);
-    std::vector<unsigned> rec;
+    if (n > kMcmcChainsMaxN || mcmc_chains_tile(n) == 0)
+        return fail(GML_EUNSUPPORTED, "the int8 chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN, (long long)n);
+    if (histogram)
+        if (int rc = check_hist_limits(n, M)) return rc;
+    if (int rc = gml_check_device(device)) return rc;
+    const QuantisedRows q = quantise_rows(model, n);
+    const int64_t ld = round_up(M, 256);
+    SamplerStaging s;
+    if (int rc = s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true)) return rc;
+    const int8_t *dDg = s.upload(q.dg);
+    const double *dq = s.upload(q.qblk), *dd = s.upload(q.diag), *ds = s.upload(q.sig), *dsum = s.upload(q.qsum);
+    if (s.rc) return s.rc;
+    launch_mcmc_chains(dDg, dq, dd, ds, dsum, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, s.out, ld, s.st);
+    return s.finish(true, ld, histogram != 0, out); // the recorded states, spin-major
+}
+
+// The model of gml_problem_create_mcmc_terms_chains.  The couplings of every spin are quantised: sigma_i = 2^(E - 38) with
+// max_e |w_e| < 2^E over its incidences with other spins, q_e = rint(w_e / sigma_i), and the incidences grouped by arity into the
+// record stream of TermChainSpin (gml_dev.h): per spin a_i, sigma_i, Q_i and the records (q_e 2^24 + j_1 as two words, then j_2 .. j_k).
+static void build_spin_records(const Incidences &inc, std::vector<TermChainSpin> &spin, std::vector<unsigned> &rec) {
+    const int64_t n = (int64_t)inc.size();
+    spin.assign((size_t)n, TermChainSpin{});
     for (int64_t i = 0; i < n; ++i) {
         TermChainSpin &r = spin[(size_t)i];
         double a = 0.0, mx = 0.0;
@@ -467,53 +402,54 @@ extern "C" int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key
         r.Q = Q;
     }
     if (rec.empty()) rec.push_back(0u);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GML_EHIP, "no HIP device available (libgml_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(GML_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
-    gml_problem *p = new gml_problem();
-    p->device = device;
-    p->n = n;
-    p->K = M;
-    p->M = (double)M;
-    p->order = order;
-    p->node0 = node0;
-    p->node1 = node1;
-    hipStream_t st = nullptr;
+}
+
+// the term-chain kernel's limits: distinct spins per term, incidences with other spins per spin
+static int check_term_chain_limits(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n) {
+    std::vector<int64_t> cnt((size_t)n, 0);
+    std::vector<int> sp;
+    for (int64_t t = 0; t < nterms; ++t) {
+        if (weights[t] == 0.0) continue;
+        reduce_key(keys + t * key_stride, key_stride, sp);
+        if (sp.size() > (size_t)kTermChainsMaxOthers + 1)
+            return fail(GML_EUNSUPPORTED, "term %lld names %zu distinct spins: the term-list chain kernel supports at most %d",
+                        (long long)t, sp.size(), kTermChainsMaxOthers + 1);
+        if (sp.size() > 1)
+            for (int v : sp)
+                if (++cnt[(size_t)v] >= ((int64_t)1 << 24))
+                    return fail(GML_EUNSUPPORTED, "spin %d has 2^24 or more incidences with other spins: the term-list chain kernel "
+                                                  "supports fewer than 2^24", v);
+    }
+    return GML_OK;
+}
+
+// gml_problem_create_mcmc_terms_chains: thinned Glauber chains of any term list with exact integer fields (gml_term_chains.hip).
+extern "C" int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                                    int64_t chains, int64_t samples_per_chain, int burn_in, int thin, uint64_t seed,
+                                                    int histogram, int order, int64_t node0, int64_t node1, int device, gml_problem **out) {
+    if (int rc = check_out(out)) return rc;
+    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
+    if (int rc = check_chain_args(n, chains, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
+    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
+    const int64_t M = chains * samples_per_chain;
+    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
+        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
+                    (long long)n);
+    if (histogram)
+        if (int rc = check_hist_limits(n, M)) return rc;
+    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
+    std::vector<TermChainSpin> spin;
+    std::vector<unsigned> rec;
+    build_spin_records(build_incidences(keys, key_stride, weights, nterms, n), spin, rec);
+    if (int rc = gml_check_device(device)) return rc;
     const int64_t ld = round_up(M, 256);
-    int8_t *dOut = nullptr;
-    TermChainSpin *dspin = nullptr;
-    unsigned *drec = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dspin) (void)dev_free(dspin);
-        if (drec) (void)dev_free(drec);
-        if (st) (void)hipStreamDestroy(st);
-        return rc;
-    };
-#define SCHK(expr)                                                                                              \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) {                                                                                 \
-            if (dOut) (void)dev_free(dOut);                                                                      \
-            delete p;                                                                                           \
-            return cleanup(fail(e_ == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", #expr,      \
-                                hipGetErrorString(e_)));                                                        \
-        }                                                                                                       \
-    } while (0)
-    SCHK(hipStreamCreate(&st));
-    SCHK(dev_malloc(&dOut, (size_t)n * ld));
-    SCHK(dev_malloc(&dspin, sizeof(TermChainSpin) * spin.size()));
-    SCHK(dev_malloc(&drec, sizeof(unsigned) * rec.size()));
-    SCHK(hipMemcpyAsync(dspin, spin.data(), sizeof(TermChainSpin) * spin.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(drec, rec.data(), sizeof(unsigned) * rec.size(), hipMemcpyHostToDevice, st));
-    SCHK(hipMemsetAsync(dOut, 0, (size_t)n * ld, st));
-    launch_term_chains(dspin, drec, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, dOut, ld, st);
-    SCHK(hipGetLastError());
-    SCHK(hipStreamSynchronize(st));
-#undef SCHK
-    cleanup(0);
-    return gml_create_from_device_bytes(p, dOut, true, ld, nullptr, out, histogram != 0); // the recorded states, spin-major
+    SamplerStaging s;
+    if (int rc = s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true)) return rc;
+    const TermChainSpin *dspin = s.upload(spin);
+    const unsigned *drec = s.upload(rec);
+    if (s.rc) return s.rc;
+    launch_term_chains(dspin, drec, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, s.out, ld, s.st);
+    return s.finish(true, ld, histogram != 0, out); // the recorded states, spin-major
 }
 
 extern "C" int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,
@@ -525,7 +461,7 @@ extern "C" int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride
 extern "C" int gml_problem_create_sampled_hist(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
                                                int64_t N, uint64_t seed, int mcmc_sweeps, int order, int64_t node0, int64_t node1,
                                                int device, gml_problem **out) {
-    if (n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
+    if (int rc = check_hist_spins(n)) return rc; // (N < 2^31 is left to gml_create_from_device_bytes)
     if (mcmc_sweeps > 0) return create_mcmc_terms(keys, key_stride, weights, nterms, n, N, seed, mcmc_sweeps, order, node0, node1, device, out, true);
     return create_sampled_terms(keys, key_stride, weights, nterms, n, N, seed, order, node0, node1, device, out, true);
 }
@@ -550,14 +486,13 @@ extern "C" int gml_problem_create_sampled(const double *model, int64_t n, int64_
     if (!model || !out) return fail(GML_EINVAL, "NULL argument");
     *out = nullptr;
     if (n <= 0) return fail(GML_EINVAL, "n and N must be positive");
+    if (int rc = check_symmetric_finite(model, n)) return rc;
     // the matrix as terms: 1/2 s^T A s = sum_{i<j} A_ij s_i s_j (sampling.jl:40), prior = diagonal (:41)
     std::vector<int32_t> keys;
     std::vector<double> wts;
     for (int64_t i = 0; i < n; ++i)
         for (int64_t j = 0; j <= i; ++j) {
             const double v = model[i * n + j];
-            if (j < i && v != model[j * n + i])
-                return fail(GML_EINVAL, "the model matrix is not symmetric at (%lld,%lld)", (long long)i, (long long)j);
             if (v == 0.0) continue;
             keys.push_back((int32_t)j);
             keys.push_back(j < i ? (int32_t)i : -1);
@@ -586,4 +521,3 @@ extern "C" int gml_problem_get_spins(gml_problem *p, int8_t *spins) {
     (void)dev_free(dT);
     return rc;
 }
-

@@ -8,7 +8,7 @@
 // PCIe upload).  Random numbers: a counter-based splitmix64 hash of (seed, block, sample).
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_rng.h"
+#include "gml_chain.h"
 
 namespace gml {
 
@@ -109,8 +109,9 @@ __global__ __launch_bounds__(256) void k_glauber(const int *__restrict__ ioff, c
                                                  int8_t *__restrict__ St) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= N) return;
-    for (int64_t i = 0; i < n; ++i) St[i * Np + k] = u01(seed, 0xFFFFFFFFull, (unsigned long long)(k * n + i)) < 0.5 ? (int8_t)1 : (int8_t)-1;
+    for (int64_t i = 0; i < n; ++i) St[i * Np + k] = chain_start_bit(seed, k, n, i) ? (int8_t)-1 : (int8_t)1;
     for (int sw = 0; sw < sweeps; ++sw) {
+        const unsigned long long z0 = chain_z0(seed, k, n, (unsigned long long)sw);
         for (int64_t i = 0; i < n; ++i) {
             double field = 0.0;
             for (int e = ioff[i]; e < ioff[i + 1]; ++e) {
@@ -118,9 +119,7 @@ __global__ __launch_bounds__(256) void k_glauber(const int *__restrict__ ioff, c
                 for (int a = ooff[e]; a < ooff[e + 1]; ++a) pr *= (int)St[(int64_t)oth[a] * Np + k];
                 field += iw[e] * (double)pr;
             }
-            const double pup = 1.0 / (1.0 + exp(-2.0 * field));
-            const double u = u01(seed, (unsigned long long)sw, (unsigned long long)(k * n + i));
-            St[i * Np + k] = u < pup ? (int8_t)1 : (int8_t)-1;
+            St[i * Np + k] = chain_heat_bath(z0, (unsigned long long)i, field) ? (int8_t)-1 : (int8_t)1;
         }
     }
 }

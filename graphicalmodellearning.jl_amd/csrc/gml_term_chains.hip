@@ -14,7 +14,7 @@
 // +-1 bytes, spin-major [n][ld], row t * chains + c.
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_rng.h"
+#include "gml_chain.h"
 
 namespace gml {
 
@@ -72,16 +72,10 @@ __global__ __launch_bounds__(256) void k_term_chains(const TermChainSpin *__rest
     const int T = blockDim.x, tid = threadIdx.x, nw = (n + 31) >> 5;
     const int64_t c = (int64_t)blockIdx.x * T + tid; // the chain this lane updates (chains beyond `chains` run but are not stored)
     unsigned *my = bits + tid;
-    for (int b = 0; b < nw; ++b) {
-        unsigned word = 0;
-        for (int i = 0; i < 32 && 32 * b + i < n; ++i)
-            if (!(u01(seed, 0xFFFFFFFFull, (unsigned long long)(c * n + 32 * b + i)) < 0.5)) word |= 1u << i;
-        my[b * T] = word;
-    }
+    for (int b = 0; b < nw; ++b) my[b * T] = chain_start_word(seed, c, n, b);
     const int sweeps = burn_in + (spc - 1) * thin;
     for (int sw = 0; sw < sweeps; ++sw) {
-        // the counter word of spin s in this sweep is z0 + kU01Step s  (u01(seed, sw, c n + s), gml_rng.h)
-        const unsigned long long z0 = seed + kU01Step * ((unsigned long long)(c * n) + 1ull) + kU01Stream * ((unsigned long long)sw + 1ull);
+        const unsigned long long z0 = chain_z0(seed, c, n, sw);
         for (int i = 0; i < n; ++i) {
             const TermChainSpin &r = spin[i];
             long long odd = odd_sum<1>(rec, r.off[0], r.off[1], my, T);
@@ -92,20 +86,11 @@ __global__ __launch_bounds__(256) void k_term_chains(const TermChainSpin *__rest
             odd += odd_sum<6>(rec, r.off[5], r.off[6], my, T);
             odd += odd_sum<7>(rec, r.off[6], r.off[7], my, T);
             const double f = (double)(r.Q - 2 * odd);
-            const double field = r.a + r.sig * f;
-            const double pup = 1.0 / (1.0 + exp(-2.0 * field));
-            const unsigned neg = u01_mix(z0 + kU01Step * (unsigned long long)i) < pup ? 0u : 1u;
+            const unsigned neg = chain_heat_bath(z0, (unsigned long long)i, r.a + r.sig * f);
             unsigned *wp = my + (i >> 5) * T;
             *wp = (*wp & ~(1u << (i & 31))) | (neg << (i & 31));
         }
-        const int done = sw + 1;
-        if (done >= burn_in && (done - burn_in) % thin == 0 && c < chains) {
-            int8_t *o = out + (int64_t)((done - burn_in) / thin) * chains + c;
-            for (int b = 0; b < nw; ++b) {
-                const unsigned word = my[b * T];
-                for (int i = 0; i < 32 && 32 * b + i < n; ++i) o[(int64_t)(32 * b + i) * ld] = (word >> i) & 1u ? (int8_t)-1 : (int8_t)1;
-            }
-        }
+        chain_record(sw + 1, burn_in, thin, c, chains, n, nw, my, T, out, ld);
     }
 }
 

@@ -61,6 +61,20 @@ def _problem_args(model):
     return {"model": np.asarray(model, dtype=np.float64)}
 
 
+def _term_list_args(model, args):
+    """The arguments of a pairwise model as a term list: the chains of Glauber and GlauberTermChains run on term lists."""
+    if "model" not in args:
+        return args
+    fg = model if isinstance(model, FactorGraph) else FactorGraph(np.asarray(model, dtype=np.float64))
+    return {"terms": fg.terms, "n": fg.varible_count, "order": 2}
+
+
+def _check_whole_chains(number_sample, sampler):
+    if int(number_sample) % sampler.samples_per_chain != 0:
+        raise ValueError(f"the number of samples ({number_sample}) must be a multiple of samples_per_chain "
+                         f"({sampler.samples_per_chain})")
+
+
 def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, device=0):
     """sample(gm, N) -> histogram matrix [count, s_1..s_n], one row per observed configuration
     (sampling.jl:52-54); sample(gm, N, replicates) -> list of such matrices (:91)."""
@@ -68,22 +82,14 @@ def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, devic
     if isinstance(sampler, GlauberChains):
         if "model" not in args:
             raise ValueError("GlauberChains samples pairwise models (order <= 2) only; use Glauber for multi-body models")
-        if int(number_sample) % sampler.samples_per_chain != 0:
-            raise ValueError(f"the number of samples ({number_sample}) must be a multiple of samples_per_chain "
-                             f"({sampler.samples_per_chain})")
+        _check_whole_chains(number_sample, sampler)
         args.update(burn_in=sampler.burn_in, thin=sampler.thin, samples_per_chain=sampler.samples_per_chain)
     elif isinstance(sampler, GlauberTermChains):
-        if "model" in args:  # the chains run on term lists
-            fg = model if isinstance(model, FactorGraph) else FactorGraph(np.asarray(model, dtype=np.float64))
-            args = {"terms": fg.terms, "n": fg.varible_count, "order": 2}
-        if int(number_sample) % sampler.samples_per_chain != 0:
-            raise ValueError(f"the number of samples ({number_sample}) must be a multiple of samples_per_chain "
-                             f"({sampler.samples_per_chain})")
+        args = _term_list_args(model, args)
+        _check_whole_chains(number_sample, sampler)
         args.update(mcmc_sweeps=sampler.burn_in, mcmc_thin=sampler.thin, mcmc_samples_per_chain=sampler.samples_per_chain)
     elif isinstance(sampler, Glauber):
-        if "model" in args:  # the chains run on term lists
-            fg = model if isinstance(model, FactorGraph) else FactorGraph(np.asarray(model, dtype=np.float64))
-            args = {"terms": fg.terms, "n": fg.varible_count, "order": 2}
+        args = _term_list_args(model, args)
         args["mcmc_sweeps"] = sampler.sweeps
     reps = 1 if replicates is None else int(replicates)
     nspins = args["model"].shape[0] if "model" in args else args["n"] if "n" in args else max(max(k) for k in args["terms"] if len(k))

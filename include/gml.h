@@ -218,7 +218,9 @@ int gml_problem_create_sampled_terms(const int32_t *keys, int key_stride, const 
 
 /* Beyond the reference (whose only sampler is exact enumeration): N independent Glauber (heat-bath) chains of
  * `sweeps` sequential sweeps from a random start, for models whose components exceed 22 spins (lattices, ...).
- * Same term-list arguments as above; the final states of the chains become the handle's samples. */
+ * Same term-list arguments as above; the final states of the chains become the handle's samples.
+ * Both term-list entry points (and gml_problem_create_sampled_hist) check every argument and limit, the 22-spin component limit
+ * included, before they look for the device: a bad term list is GML_EINVAL / GML_EUNSUPPORTED with or without a GPU. */
 int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,
                                   int64_t n, int64_t N, uint64_t seed, int sweeps, int order, int64_t node0,
                                   int64_t node1, int device, gml_problem **out);
