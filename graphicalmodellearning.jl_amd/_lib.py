@@ -90,6 +90,8 @@ def lib():
     L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
+    L.gml_problem_moments.argtypes = [p, p, p]
+    L.gml_problem_term_moments.argtypes = [p, p, i32, i64, p]
     L.gml_problem_destroy.argtypes = [p]
     L.gml_problem_destroy.restype = None
     L.gml_problem_info.argtypes = [p] + [p] * 6
@@ -236,6 +238,29 @@ def terms_rank(n, order, symmetrize, key0):
 def _node_range(node_range, n):
     """(node0, node1) of a handle: the given range, by default every node."""
     return node_range if node_range is not None else (0, int(n))
+
+
+def moment_key_windows(terms, chunk=1 << 22):
+    """The keys of `terms` as the C ABI takes them, window by window: int32 arrays [count, stride], 0-based spins, -1 = unused slot.
+    terms: what Problem(terms=...) takes for keys -- a dict of 1-based tuples (its values are not looked at), any iterable of
+    1-based tuples, a FactorGraph (its terms), or a TermArray, whose key table is generated window by window through keys_array
+    and never held whole.  Host only."""
+    terms = getattr(terms, "terms", terms)  # a FactorGraph
+    if hasattr(terms, "keys_array"):
+        for a in range(0, len(terms), chunk):
+            yield np.ascontiguousarray(terms.keys_array(a, min(chunk, len(terms) - a)) - 1, dtype=np.int32)
+        return
+    klist = [tuple(int(i) for i in k) for k in terms]
+    if not klist:
+        return
+    for k in klist:
+        if any(i < 1 for i in k):
+            raise GMLError(GML_EINVAL, f"term {k}: spins are numbered from 1")
+    stride = max(1, max(len(k) for k in klist))
+    keys = np.full((len(klist), stride), -1, dtype=np.int32)
+    for t, k in enumerate(klist):
+        keys[t, :len(k)] = np.asarray(k, dtype=np.int64) - 1
+    yield keys
 
 
 class Problem:
@@ -404,6 +429,29 @@ class Problem:
         check(lib().gml_problem_get_counts(self._h, _ptr(out)))
         return out
 
+    def moments(self, pairs=True, raw=False):
+        """(m [n], C [n, n]): the sample magnetisations <s_i> and pair correlations <s_i s_j> of the handle (float64 = the exact integer
+        sums of gml_problem_moments over M; raw=True: the int64 sums themselves).  pairs=False: C is None and only m is computed.
+        Integer counts and M <= 2^50 (GMLError GML_EUNSUPPORTED otherwise); independent of the handle's order and node range."""
+        s1 = np.zeros(self.n, dtype=np.int64)
+        s2 = np.zeros((self.n, self.n), dtype=np.int64) if pairs else None
+        check(lib().gml_problem_moments(self._h, _ptr(s1), _ptr(s2)))
+        if raw:
+            return s1, s2
+        return s1 / self.M, (s2 / self.M if pairs else None)
+
+    def term_moments(self, terms, raw=False):
+        """<prod_{i in t} s_i> of every term t of `terms`, in the caller's order (gml_problem_term_moments; raw=True: the int64 sums).
+        terms: a dict of 1-based tuples, a list of tuples, a FactorGraph or a TermArray (moment_key_windows).  A spin named twice
+        cancels; the empty key gives 1 (raw: M)."""
+        out = []
+        for keys in moment_key_windows(terms):
+            sums = np.zeros(len(keys), dtype=np.int64)
+            check(lib().gml_problem_term_moments(self._h, _ptr(keys), keys.shape[1], len(keys), _ptr(sums)))
+            out.append(sums)
+        sums = np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+        return sums if raw else sums / self.M
+
     def sign_bits(self):
         """the packed form of the handle's samples: [n][gml_packed_words(K)] uint32, bit set <=> spin -1"""
         out = np.zeros((self.n, lib().gml_packed_words(self.K)), dtype=np.uint32)
@@ -536,6 +584,16 @@ class Problem:
                                             int(warmup), _ptr(ms), _ptr(f), _ptr(g), _ptr(step)))
         out = {"fwd_ms": ms[0], "bwd_ms": ms[1], "pass_ms": ms[2], "device_ms_per_pass": ms[3], "step_ms": step}
         return (out, f, g) if want_output else out
+
+
+def moments(samples_or_problem, terms=None, raw=False, device=0):
+    """Sample moments of a K x (1+n) histogram matrix (a handle is built and closed) or of an open Problem: (m, C) as
+    Problem.moments, or with terms= the per-term expectations of Problem.term_moments."""
+    if isinstance(samples_or_problem, Problem):
+        p = samples_or_problem
+        return p.moments(raw=raw) if terms is None else p.term_moments(terms, raw=raw)
+    with Problem(samples_or_problem, device=device) as p:
+        return p.moments(raw=raw) if terms is None else p.term_moments(terms, raw=raw)
 
 
 class MultiProblem:

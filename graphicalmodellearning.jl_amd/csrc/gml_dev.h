@@ -185,6 +185,17 @@ int dedupe_samples(const int8_t *dS, bool spin_major, int64_t ld, int64_t N, int
                    int **dcounts_out, int64_t *K_out, std::string *err);
 void launch_bits_from_keys(const unsigned long long *dkeys, int64_t K, int64_t n, int64_t Kp, unsigned *Sb, hipStream_t st);
 
+// Exact sample moments from the sign bits (gml_moments.hip): XOR of sign rows + population counts, integer sums throughout.
+// planes [nplanes][Kp / 32]: bit b of every count c_k = rint(w_k M), packed like a sign row (launch_count_planes); nplanes = 0:
+// all counts equal (the common count is applied by the caller / the finishing kernel).
+void launch_count_planes(const DevProblem &d, double M, int nplanes, unsigned *planes, hipStream_t st);
+// S2 [n][n] (zeroed by the caller) -> sum2 = M - 2 c N, N_ij = sum_k c_k [s_ki != s_kj] (c = 1 with planes)
+void launch_moments_pairs(const DevProblem &d, const unsigned *planes, int nplanes, long long M, long long c, long long *S2, hipStream_t st);
+// Nt [nterms] (zeroed by the caller) += sum_k c_k [prod of the key's spins at k is -1] (nplanes = 0: every c_k taken as 1).
+// keys [nterms][L]: distinct spins of every key, -1 = unused slot
+void launch_moments_terms(const DevProblem &d, const int32_t *keys, int L, int64_t nterms, const unsigned *planes, int nplanes,
+                          unsigned long long *Nt, hipStream_t st);
+
 // Glauber dynamics (N independent chains, `sweeps` sweeps) on incidence lists; St [n][Np] spin-major.
 void launch_glauber(const int *dioff, const double *diw, const int *dooff, const int *doth, int64_t n, int64_t N, int64_t Np,
                     int sweeps, unsigned long long seed, int8_t *dSt, hipStream_t st);

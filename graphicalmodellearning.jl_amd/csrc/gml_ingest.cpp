@@ -140,13 +140,16 @@ static int prob_layout(gml_problem *p) {
 struct WeightInfo {
     std::vector<double> w, wblk;
     double wmax = 0, wuni = 0;
+    bool counts_int = true; // the caller's counts are all integers
 };
 static void weight_info(const double *counts /* NULL: all ones */, int64_t K, int64_t Kp, double M, WeightInfo &wi) {
     wi.w.assign((size_t)Kp, 0.0); // 0 on the padding configurations
     wi.wmax = 0;
+    wi.counts_int = true;
     for (int64_t k = 0; k < K; ++k) {
         wi.w[k] = (counts ? counts[k] : 1.0) / M; // w_k = counts[k]/M  (:170)
         wi.wmax = std::max(wi.wmax, wi.w[k]);
+        if (counts && counts[k] != std::nearbyint(counts[k])) wi.counts_int = false;
     }
     wi.wuni = wi.w[0];
     for (int64_t k = 1; k < K; ++k)
@@ -161,6 +164,7 @@ static int prob_weights(gml_problem *p, const WeightInfo &wi) {
     DevProblem &d = p->d;
     d.wmax = wi.wmax;
     d.wuni = wi.wuni;
+    p->counts_int = wi.counts_int;
     p->wblk = wi.wblk;
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipMemcpyAsync(d.w, wi.w.data(), sizeof(double) * d.Kp, hipMemcpyHostToDevice, p->st));

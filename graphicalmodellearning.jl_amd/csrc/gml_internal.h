@@ -33,6 +33,7 @@ struct gml_problem {
     int64_t n = 0, K = 0, P = 0, node0 = 0, node1 = 0;
     int order = 2;
     double M = 0;
+    bool counts_int = false; // every count the handle was created from was an integer (the moments' exactness contract, gml.h)
     gml::DevProblem d{};
     std::vector<int32_t> gkeys; // [Q][ko] subsets of spins (feature keys), -1 padded
     int ko = 1;

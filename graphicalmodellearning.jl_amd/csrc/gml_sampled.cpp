@@ -471,8 +471,127 @@ extern "C" int gml_problem_get_counts(gml_problem *p, double *counts) {
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipMemcpyAsync(counts, p->d.w, sizeof(double) * p->K, hipMemcpyDeviceToHost, p->st));
     HIPCHK(hipStreamSynchronize(p->st));
-    for (int64_t k = 0; k < p->K; ++k) counts[k] = std::nearbyint(counts[k] * p->M * 1e6) / 1e6; // w_k = counts_k / M (:170)
+    // w_k = counts_k / M (:170): integer counts come back exactly (M <= 2^50: two roundings of 2^-53 each stay below 1/2)
+    const double unit = p->counts_int ? 1.0 : 1e6;
+    for (int64_t k = 0; k < p->K; ++k) counts[k] = std::nearbyint(counts[k] * p->M * unit) / unit;
     return GML_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// gml_problem_moments, gml_problem_term_moments: exact integer sums over the handle's configurations (gml_moments.hip)
+// ------------------------------------------------------------------------------------------
+// Device blocks of one moments call: freed on every path.
+struct MomentsBlocks {
+    std::vector<void *> blocks;
+    ~MomentsBlocks() {
+        for (void *q : blocks) (void)dev_free(q);
+    }
+    template <class T> hipError_t alloc(T **out, size_t count) {
+        const hipError_t e = dev_malloc(out, sizeof(T) * std::max<size_t>(count, 1));
+        if (e == hipSuccess) blocks.push_back(*out);
+        return e;
+    }
+};
+
+// The exactness contract (gml.h): integer counts and M <= 2^50, so that c_k = rint(w_k M) on the device.
+static int check_moments_handle(const gml_problem *p) {
+    if (!p->counts_int)
+        return fail(GML_EUNSUPPORTED, "the handle was created with a fractional count: exact moments need integer counts");
+    if (!(p->M <= 1125899906842624.0))
+        return fail(GML_EUNSUPPORTED, "the sum of the counts M = %.17g exceeds 2^50: exact moments need M <= 2^50", p->M);
+    return GML_OK;
+}
+
+// The count planes of a handle whose counts differ (none, *nplanes = 0, when they are all equal: *c is the common count).
+static int moments_planes(gml_problem *p, MomentsBlocks &mb, unsigned **planes, int *nplanes, long long *c) {
+    *planes = nullptr;
+    *nplanes = 0;
+    *c = 1;
+    if (p->d.wuni != 0.0) {
+        *c = (long long)std::nearbyint(p->d.wuni * p->M);
+        return GML_OK;
+    }
+    const unsigned long long cmax = (unsigned long long)std::nearbyint(p->d.wmax * p->M);
+    int nb = 1;
+    while (nb < 64 && (cmax >> nb) != 0) ++nb;
+    HIPCHK(mb.alloc(planes, (size_t)nb * (size_t)(p->d.Kp / 32)));
+    launch_count_planes(p->d, p->M, nb, *planes, p->st);
+    *nplanes = nb;
+    return GML_OK;
+}
+
+// sums[t] = M - 2 c Nt[t] of the reduced keys (host vectors), through the term kernel
+static int term_sums(gml_problem *p, MomentsBlocks &mb, const std::vector<int32_t> &rkeys, int L, int64_t nterms, const unsigned *planes,
+                     int nplanes, long long c, int64_t *sums) {
+    int32_t *dkeys = nullptr;
+    unsigned long long *dNt = nullptr;
+    HIPCHK(mb.alloc(&dkeys, rkeys.size()));
+    HIPCHK(mb.alloc(&dNt, (size_t)nterms));
+    HIPCHK(hipMemcpyAsync(dkeys, rkeys.data(), sizeof(int32_t) * rkeys.size(), hipMemcpyHostToDevice, p->st));
+    HIPCHK(hipMemsetAsync(dNt, 0, sizeof(unsigned long long) * nterms, p->st));
+    launch_moments_terms(p->d, dkeys, L, nterms, planes, nplanes, dNt, p->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums, dNt, sizeof(int64_t) * nterms, hipMemcpyDeviceToHost, p->st));
+    HIPCHK(hipStreamSynchronize(p->st));
+    const int64_t M = (int64_t)p->M;
+    for (int64_t t = 0; t < nterms; ++t) sums[t] = M - 2 * c * sums[t];
+    return GML_OK;
+}
+
+extern "C" int gml_problem_moments(gml_problem *p, int64_t *sum1, int64_t *sum2) {
+    if (!p || !sum1) return fail(GML_EINVAL, "NULL argument");
+    if (int rc = check_moments_handle(p)) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    MomentsBlocks mb;
+    unsigned *planes = nullptr;
+    int nplanes = 0;
+    long long c = 1;
+    if (int rc = moments_planes(p, mb, &planes, &nplanes, &c)) return rc;
+    std::vector<int32_t> keys((size_t)p->n);
+    for (int64_t i = 0; i < p->n; ++i) keys[(size_t)i] = (int32_t)i;
+    if (int rc = term_sums(p, mb, keys, 1, p->n, planes, nplanes, c, sum1)) return rc;
+    if (!sum2) return GML_OK;
+    long long *dS2 = nullptr;
+    const size_t bytes = sizeof(long long) * (size_t)p->n * (size_t)p->n;
+    HIPCHK(mb.alloc(&dS2, (size_t)p->n * (size_t)p->n));
+    HIPCHK(hipMemsetAsync(dS2, 0, bytes, p->st));
+    launch_moments_pairs(p->d, planes, nplanes, (long long)p->M, c, dS2, p->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sum2, dS2, bytes, hipMemcpyDeviceToHost, p->st));
+    HIPCHK(hipStreamSynchronize(p->st));
+    return GML_OK;
+}
+
+extern "C" int gml_problem_term_moments(gml_problem *p, const int32_t *keys, int key_stride, int64_t nterms, int64_t *sums) {
+    if (!p || !keys || !sums) return fail(GML_EINVAL, "NULL argument");
+    if (key_stride < 1 || nterms < 0) return fail(GML_EINVAL, "key_stride must be at least 1 and nterms non-negative");
+    for (int64_t t = 0; t < nterms; ++t)
+        for (int a = 0; a < key_stride; ++a) {
+            const int32_t v = keys[t * key_stride + a];
+            if (v < -1 || v >= p->n) return fail(GML_EINVAL, "term %lld names spin %d outside [0,%lld)", (long long)t, v, (long long)p->n);
+        }
+    if (nterms == 0) return GML_OK;
+    if (int rc = check_moments_handle(p)) return rc;
+    // the distinct spins of every key (a spin named twice cancels), padded to the longest
+    std::vector<int> sp;
+    std::vector<int32_t> tmp((size_t)nterms * key_stride, -1);
+    int L = 1;
+    for (int64_t t = 0; t < nterms; ++t) {
+        reduce_key(keys + t * key_stride, key_stride, sp);
+        std::copy(sp.begin(), sp.end(), tmp.begin() + t * key_stride);
+        L = std::max(L, (int)sp.size());
+    }
+    if (L < key_stride) {
+        for (int64_t t = 1; t < nterms; ++t) std::copy(tmp.begin() + t * key_stride, tmp.begin() + t * key_stride + L, tmp.begin() + t * L);
+        tmp.resize((size_t)nterms * L);
+    }
+    HIPCHK(hipSetDevice(p->device));
+    MomentsBlocks mb;
+    unsigned *planes = nullptr;
+    int nplanes = 0;
+    long long c = 1;
+    if (int rc = moments_planes(p, mb, &planes, &nplanes, &c)) return rc;
+    return term_sums(p, mb, tmp, L, nterms, planes, nplanes, c, sums);
 }
 
 extern "C" int gml_problem_create_sampled_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,

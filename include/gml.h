@@ -293,8 +293,38 @@ int gml_problem_create_sampled_hist(const int32_t *keys, int key_stride, const d
                                     int64_t N, uint64_t seed, int mcmc_sweeps, int order, int64_t node0, int64_t node1,
                                     int device, gml_problem **out);
 
-/* The counts of a handle's K rows (host pointer, K doubles): column 1 of the histogram (sampling.jl:54). */
+/* The counts of a handle's K rows (host pointer, K doubles): column 1 of the histogram (sampling.jl:54).  A handle created from
+ * integer counts returns them exactly (M <= 2^50); fractional counts come back rounded to 1e-6. */
 int gml_problem_get_counts(gml_problem *p, double *counts);
+
+/*
+ * gml_problem_moments, gml_problem_term_moments -- the exact sample moments of a handle, computed on the device from its sign bits
+ * (a product of spins is the XOR of their sign rows, a sum over configurations a population count; gml_moments.hip).  Host
+ * pointers.  With c_k the count of row k and s_ki = +-1:
+ *   sum1[i]    = sum_k c_k s_ki                         [n]
+ *   sum2[i][j] = sum_k c_k s_ki s_kj                    [n][n] row-major, the full symmetric matrix, diagonal = M; NULL: not computed
+ *   sums[t]    = sum_k c_k prod_{i in key t} s_ki       [nterms]
+ * keys as everywhere in this header: spins of term t = keys[t*key_stride .. +key_stride), 0-based, -1 = unused slot, any
+ * key_stride >= 1 (no limit on the order); a spin named twice in a key cancels (s^2 = 1); the empty key gives M.  The moments are
+ * these sums divided by M (gml_problem_info).  They do not depend on the handle's order or node range (every handle holds all n
+ * spins), and padding rows contribute nothing.
+ * Exactness: for a handle whose counts are all integers and whose M <= 2^50, every output is the exact integer above -- all sums
+ * are integer additions, so the result does not depend on the kernels' tiles, their split over K, the grid or the device.  Every
+ * sampled handle (exact, Glauber, both chain kinds, histogram or not) and every histogram with integer counts (the reference's
+ * Matrix{Int64}) is such a handle; whether the counts were integers is decided from the caller's values when the handle is
+ * created, on every creation route.  (The device keeps w_k = c_k / M; M <= 2^50 is what makes rint(w_k M) = c_k: two roundings of
+ * relative 2^-53 each stay below 1/2.)  gml_problem_get_counts returns the counts of such a handle exactly.
+ * Cost: sum2 is a binary GEMM on the vector ALU, n^2 / 2 pairs x K bits as xor + popcount; handles whose counts are not all equal
+ * (histograms) run it once per bit of the largest count -- the cost grows with log2(max c_k), acceptable because a histogram
+ * handle has few rows.  sum1 and the term sums stream (key length) x K / 8 bytes per term.  Device memory beyond the outputs
+ * (8 n^2 bytes for sum2): the count planes (K / 8 bytes per bit of the largest count) and the reduced keys; all of it is released
+ * before the call returns.
+ * GML_EINVAL (checked before any device work): NULL p / sum1 / keys / sums, key_stride < 1, nterms < 0, a spin outside [0, n)
+ * (the text names the term).  nterms = 0 is a no-op.  GML_EUNSUPPORTED: a handle created with a fractional count, or M > 2^50 (the
+ * text says which); there is no floating-point fallback.  Handles of gml_multi are not covered.
+ */
+int gml_problem_moments(gml_problem *p, int64_t *sum1 /* [n] */, int64_t *sum2 /* [n][n] row-major, or NULL */);
+int gml_problem_term_moments(gml_problem *p, const int32_t *keys, int key_stride, int64_t nterms, int64_t *sums /* [nterms] */);
 
 /* The +-1 configurations held by a handle, K x n row-major (host pointer). */
 int gml_problem_get_spins(gml_problem *p, int8_t *spins);
