@@ -109,6 +109,35 @@ __device__ __forceinline__ void ring_wait_ahead(int ahead) {
 }
 
 
+// One LDS-DMA instruction with the address split the way the hardware takes it: a wave-uniform 64-bit base in scalar registers,
+// a 32-bit per-lane offset, the (wave-uniform) LDS destination in M0.  (Through __builtin_amdgcn_global_load_lds the compiler
+// folds the lane offset into loop-invariant 64-bit VECTOR pointers, one pair per instruction of the stage, and counts the DMA as a
+// pending LDS write: in a loop that is one basic block it then puts s_waitcnt vmcnt(0) in front of the first plain LDS read,
+// which drains the ring.  The kernels count their DMA themselves.)
+__device__ __forceinline__ void dma16(const int8_t *ubase, int voff, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(ubase), "s"(lds_addr) : "memory"); // (M0 is reserved: the compiler never keeps a value in it)
+}
+
+// Fragment reads of an int8 GEMM loop (k_bwd_i8), kept ahead of their MFMAs.  Written as plain loads, the compiler gives a loop's
+// fragments two registers and re-reads them in place: read, wait for it, multiply, a full LDS round trip in front of every few
+// MFMAs.  Pinned as assembly, a read is issued into a rotating set of fragment registers several MFMAs before its use, and the
+// wait in front of the use counts the reads that may still be in flight behind it (LDS reads return in order).  The compiler
+// neither counts these reads nor orders register-only instructions against them, so: the wait names the fragment as an operand
+// and is followed by a scheduling barrier (no MFMA moves above it), a scheduling barrier precedes the read that refills a
+// fragment (no MFMA that reads the old value moves below it), and no scalar load may sit between a read and its wait (scalar
+// loads share the counter and return out of order).  -DGML_I8_PLAIN_FRAGS builds the loop with plain loads (A/B, tests).
+#define FRAG_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
+#define FRAG_WAIT(frag, behind)                                                       \
+    do {                                                                              \
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(frag) : "n"(behind) : "memory"); \
+        __builtin_amdgcn_sched_barrier(0);                                            \
+    } while (0)
+#ifdef GML_I8_PLAIN_FRAGS
+constexpr bool PINNED_FRAGS = false;
+#else
+constexpr bool PINNED_FRAGS = true;
+#endif
+
 // exp(x) for |x| < 700 to ~1e-15 relative: 2^(n/64) table (in LDS) times a degree-6 polynomial
 __device__ __forceinline__ double exp_tab(double x, const double *__restrict__ tab) {
     const double t = rint(x * 92.33248261689366);      // 64/ln2

@@ -53,9 +53,12 @@ __global__ __launch_bounds__(256 * TM, 2) void k_bwd_i8(
     // NL = 6: the twelve pieces of six planes + the bits: waves 0 and 1 load four, the others three.
     constexpr int NJ = NL == 6 ? 4 : 3;               // loads of the waves that carry one more
     const bool three = (NL == 4 || NL == 6) && wave < 2; // ... which are these
+    // one DMA instruction = a wave-uniform source (scalar registers) + one of two per-lane offsets: 16 rows x 64 B of Vq with the
+    // XOR swizzle of lds_off() applied to the SOURCE (pieces of 16 rows: (row >> 2) & 3 = (lane >> 4) & 3), or 1 KB of bits
     const int8_t *src[NJ];
-    int adv[NJ], dst[NJ];
+    int adv[NJ], dst[NJ], voff[NJ];
     const int img = lbt * 2048; // bytes of a Vq image
+    const int voffV = (lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4), voffX = lane * 16;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         int pc = wave + NW * j; // piece of the full stage image: 0 .. AP - 1 rows of Vq, then the bits
@@ -65,22 +68,22 @@ __global__ __launch_bounds__(256 * TM, 2) void k_bwd_i8(
         if (pc < AP) {
             int tl = tiles[NL == 6 ? 0 : pc >> 3];
             if (tl < 0) tl = tiles[0];
-            const int row = (NL == 6 ? pc : (pc & 7)) * 16 + (lane >> 2);
-            const int slot = (lane & 3) ^ ((row >> 2) & 3);
-            src[j] = Vq + ((int64_t)tl * nkk + kt0) * img + (pl0 * 32 + row) * 64 + slot * 16;
+            const int row0 = (NL == 6 ? pc : (pc & 7)) * 16;
+            src[j] = Vq + ((int64_t)tl * nkk + kt0) * img + (pl0 * 32 + row0) * 64;
             adv[j] = img;
+            voff[j] = voffV;
         } else {
             const int pb = pc < NPIECE ? pc - AP : 0;
-            src[j] = reinterpret_cast<const int8_t *>(Xtb) + ((int64_t)(2 * nt + pb) * nkk + kt0) * 1024 + lane * 16;
+            src[j] = reinterpret_cast<const int8_t *>(Xtb) + ((int64_t)(2 * nt + pb) * nkk + kt0) * 1024;
             adv[j] = 1024;
+            voff[j] = voffX;
         }
     }
-    auto issue = [&](int kt) {
-        int8_t *stage_base = lds + (kt & (NS - 1)) * STAGE;
+    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) int8_t *)lds;
+    auto issue = [&](int kt, auto np) { // np: the loads of this wave per stage
+        const unsigned stage_base = lds0 + (kt & (NS - 1)) * STAGE;
 #pragma unroll
-        for (int j = 0; j < NJ - 1; ++j)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src[j] + (int64_t)kt * adv[j]), (lptr_t)(stage_base + dst[j]), 16, 0, 0);
-        if (three) __builtin_amdgcn_global_load_lds((gptr_t)(src[NJ - 1] + (int64_t)kt * adv[NJ - 1]), (lptr_t)(stage_base + dst[NJ - 1]), 16, 0, 0);
+        for (int j = 0; j < decltype(np)::value; ++j) dma16(src[j] + (int64_t)kt * adv[j], voff[j], stage_base + dst[j]);
     };
     v16i acc[WMT][WNT];
 #pragma unroll
@@ -90,37 +93,98 @@ __global__ __launch_bounds__(256 * TM, 2) void k_bwd_i8(
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][jn][e] = 0;
 
-    const int nk = (int)((ke - kb) / 64);
-#pragma unroll
-    for (int s = 0; s < NS - 1; ++s)
-        if (s < nk) issue(s);
-    for (int kt = 0; kt < nk; ++kt) {
-        if (three) ring_wait_ahead<NJ>(nk - 1 - kt);
-        else ring_wait_ahead<NJ - 1>(nk - 1 - kt);
-        if (kt + NS - 1 < nk) issue(kt + NS - 1);
-        const int8_t *cur = lds + (kt & (NS - 1)) * STAGE;
+    // The 2 NL limb fragments of a step, in the order of their use: x = t NL + i, half-step t, limb plane i.  Row i * 32 + lr, slot
+    // 2 t + h: the swizzle depends on lr only, so a plane is +2048 bytes and a half-step flips bit 5 of the address: two address
+    // registers per lane and immediates.  NF fragments rotate: the read of fragment x + NF goes out behind the MFMAs of
+    // fragment x, NF - 1 fragments (6 MFMAs at NF = 4) ahead of its own.
+    constexpr int NR = 2 * WMT, NF = 4;
+    const unsigned fa_lane = lds0 + (unsigned)lds_off(wm * 128 + lr, h);
+    // the bits: lane (lr, h) needs dword h of its column's 8 bytes.  One ds_read_b64 per lane reads both: the 32 lanes of a half-wave
+    // cover 256 contiguous bytes, one bank each (a ds_read_b32 of dword 2 lr + h banks modulo 32 dwords: lanes lr and lr + 16 collide)
+    const int vb_lane = AR * 64 + (wn >> 1) * 1024 + ((wn & 1) * 64 + lr) * 8;
+    auto compute = [&](int kt) {
+        const int stage = (kt & (NS - 1)) * STAGE;
+        const int8_t *cur = lds + stage;
+        uint2 vb2[WNT];
         unsigned vb[WNT];
 #pragma unroll
         for (int jn = 0; jn < WNT; ++jn) {
-            const int cw = wn * 64 + jn * 32 + lr;
-            vb[jn] = *reinterpret_cast<const unsigned *>(cur + AR * 64 + (cw >> 7) * 1024 + (((cw & 127) * 2 + h) << 2));
+            vb2[jn] = *reinterpret_cast<const uint2 *>(cur + vb_lane + jn * 256);
+            asm volatile("" ::: "memory"); // (two reads: merged into one ds_read2_b64 they would bank modulo 32 dwords again)
         }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            v4i fa[WMT], fb[WNT];
-#pragma unroll
-            for (int i = 0; i < WMT; ++i)
-                fa[i] = *reinterpret_cast<const v4i *>(cur + lds_off(wm * 128 + i * 32 + lr, 2 * t + h));
-#pragma unroll
-            for (int jn = 0; jn < WNT; ++jn)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) fb[jn][e] = (int)((vb[jn] >> (4 * t + e)) & 0x01010101u);
-#pragma unroll
-            for (int i = 0; i < WMT; ++i)
-#pragma unroll
-                for (int jn = 0; jn < WNT; ++jn) acc[i][jn] = MFMA_I8(fa[i], fb[jn], acc[i][jn]);
-        }
+        if constexpr (PINNED_FRAGS) {
+            const unsigned a0 = fa_lane + (unsigned)stage, a1 = a0 ^ 32u;
+            v4i fa[NF], fb[2][WNT];
+            // the first NF reads go out behind the read of the bits, whose wait (the compiler's, lgkmcnt(0)) then covers them too: one
+            // round trip per step; the expansion of the bits for both half-steps runs under it
+#define BWD_FRAG_READ(x) FRAG_READ(fa[(x) % NF], (x) / WMT ? a1 : a0, ((x) % WMT) * 2048)
+#define BWD_FRAG_USE(x)                                                                                     \
+    if constexpr ((x) < NR) {                                                                               \
+        FRAG_WAIT(fa[(x) % NF], NR - 1 - (x) < NF - 1 ? NR - 1 - (x) : NF - 1);                             \
+        _Pragma("unroll") for (int jn = 0; jn < WNT; ++jn)                                                  \
+            acc[(x) % WMT][jn] = MFMA_I8(fa[(x) % NF], fb[(x) / WMT][jn], acc[(x) % WMT][jn]);              \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        if constexpr ((x) + NF < NR) BWD_FRAG_READ((x) + NF);                                               \
     }
+            BWD_FRAG_READ(0); BWD_FRAG_READ(1); BWD_FRAG_READ(2); BWD_FRAG_READ(3);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int jn = 0; jn < WNT; ++jn) vb[jn] = h ? vb2[jn].y : vb2[jn].x;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int jn = 0; jn < WNT; ++jn)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) fb[t][jn][e] = (int)((vb[jn] >> (4 * t + e)) & 0x01010101u);
+            BWD_FRAG_USE(0) BWD_FRAG_USE(1) BWD_FRAG_USE(2) BWD_FRAG_USE(3) BWD_FRAG_USE(4) BWD_FRAG_USE(5)
+            BWD_FRAG_USE(6) BWD_FRAG_USE(7) BWD_FRAG_USE(8) BWD_FRAG_USE(9) BWD_FRAG_USE(10) BWD_FRAG_USE(11)
+#undef BWD_FRAG_USE
+#undef BWD_FRAG_READ
+        } else {
+#pragma unroll
+            for (int jn = 0; jn < WNT; ++jn) vb[jn] = h ? vb2[jn].y : vb2[jn].x;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                v4i fa[WMT], fb[WNT];
+#pragma unroll
+                for (int i = 0; i < WMT; ++i)
+                    fa[i] = *reinterpret_cast<const v4i *>(cur + lds_off(wm * 128 + i * 32 + lr, 2 * t + h));
+#pragma unroll
+                for (int jn = 0; jn < WNT; ++jn)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) fb[jn][e] = (int)((vb[jn] >> (4 * t + e)) & 0x01010101u);
+#pragma unroll
+                for (int i = 0; i < WMT; ++i)
+#pragma unroll
+                    for (int jn = 0; jn < WNT; ++jn) acc[i][jn] = MFMA_I8(fa[i], fb[jn], acc[i][jn]);
+            }
+        }
+    };
+
+    const int nk = (int)((ke - kb) / 64);
+    // The ring, for a wave of NP loads per stage.  Steady state: stage kt has landed once at most the two stages behind it are in
+    // flight; one fixed wait, the barrier, the next stage's loads.  The last NS - 1 steps, which issue nothing and wait for less each
+    // time, are peeled off.
+    auto sweep = [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+#pragma unroll
+        for (int s = 0; s < NS - 1; ++s)
+            if (s < nk) issue(s, np);
+        int kt = 0;
+        for (; kt + NS - 1 < nk; ++kt) {
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            issue(kt + NS - 1, np);
+            compute(kt);
+        }
+        for (; kt < nk; ++kt) {
+            ring_wait_ahead<NP>(nk - 1 - kt);
+            compute(kt);
+        }
+    };
+    if (three) sweep(std::integral_constant<int, NJ>{});
+    else sweep(std::integral_constant<int, NJ - 1>{});
     // C layout: column (lane&31) <-> column c, register e <-> Vq row (e&3)+8*(e>>2)+4*h
 #pragma unroll
     for (int i = 0; i < WMT; ++i)

@@ -65,14 +65,6 @@ __device__ __forceinline__ void digits6(double yr, unsigned &dl, unsigned &dh) {
     dh = (unsigned)(v >> 32);
 }
 
-// One LDS-DMA instruction with the address split the way the hardware takes it: a wave-uniform 64-bit base in scalar registers,
-// a 32-bit per-lane offset, the (wave-uniform) LDS destination in M0.  (Through __builtin_amdgcn_global_load_lds the compiler
-// folds the lane offset into loop-invariant 64-bit VECTOR pointers, one pair per instruction of the stage: 18 registers this
-// kernel does not have.)
-__device__ __forceinline__ void dma16(const int8_t *ubase, int voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(ubase), "s"(lds_addr) : "memory"); // (M0 is reserved: the compiler never keeps a value in it)
-}
-
 } // namespace
 
 // ------------------------------------------------------------------------------------------
