@@ -43,6 +43,18 @@ double gml_now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+bool gml_is_device_ptr(const void *q, int *dev) {
+    if (!q) return false;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, q) != hipSuccess) {
+        (void)hipGetLastError(); // (a plain host pointer the runtime has never seen)
+        return false;
+    }
+    if (attr.type != hipMemoryTypeDevice) return false;
+    if (dev) *dev = attr.device;
+    return true;
+}
+
 // persistent worker pool for the host-side per-node loops (thread creation per call would cost
 // more than most of these loops)
 namespace {

@@ -21,6 +21,7 @@ int gml_fail(int code, const char *fmt, ...);
     } while (0)
 
 double gml_now_s();
+bool gml_is_device_ptr(const void *q, int *dev = nullptr); // q points into HBM (its device to *dev); NULL and host pointers: false
 void gml_parallel_for(int64_t n, const std::function<void(int64_t)> &fn); // persistent host worker pool
 inline int64_t gml_round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 

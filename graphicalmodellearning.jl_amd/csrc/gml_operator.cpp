@@ -346,14 +346,6 @@ static int device_pass(gml_problem *p, int64_t R, const int64_t *nodes, const do
 // scattered into the internal layout by a kernel, the pass runs, a kernel gathers the results back -- no staging, no PCIe.
 // The only host round trip is the one the dynamic-range check needs (two small per-row arrays).
 // ------------------------------------------------------------------------------------------
-static bool is_device_ptr(const void *q) {
-    if (!q) return false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, q) == hipSuccess) return attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    return false;
-}
-
 // slot -> column table of a multi-body node list on the device (NULL for pairwise: closed form in the kernels)
 static int dev_cols(gml_problem *p, int64_t nrows, const int64_t *nodes, const int32_t **out) {
     *out = nullptr;
@@ -447,7 +439,7 @@ static int check_rows(gml_problem *p, int formulation, int64_t nrows, const int6
     for (int64_t r = 0; r < nrows; ++r)
         if (nodes[r] < 0 || nodes[r] >= p->n) return fail(GML_EINVAL, "node id %lld out of range", (long long)nodes[r]);
     HIPCHK(hipSetDevice(p->device));
-    const bool td = is_device_ptr(theta), ad = is_device_ptr(a), bd = b ? is_device_ptr(b) : td;
+    const bool td = gml_is_device_ptr(theta), ad = gml_is_device_ptr(a), bd = b ? gml_is_device_ptr(b) : td;
     if (td != ad || td != bd) return fail(GML_EINVAL, "%s must be all host or all device pointers", names);
     *dev = td;
     return GML_OK;

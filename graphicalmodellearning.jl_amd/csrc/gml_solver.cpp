@@ -21,6 +21,7 @@
 // after the trial points, and after each pass (whose acceptance scalars ride along).  On small node shards these round
 // trips, not the kernels, are what an iteration costs.
 #include "gml_internal.h"
+#include "gml_slots.h"
 #include "gml_solver.h"
 
 #include <algorithm>
@@ -170,24 +171,11 @@ struct Solver {
     gml_opts o;
     gml_stats stats{};
     hipStream_t st;
-    // (experiment, gml_test_tune GML_TUNE_DUAL_STREAMS: the passes on a stream of the lowest priority, everything else on one of the highest,
-    // so that another handle's pass running on the same GPU lets this handle's short direction-phase kernels in as workgroups retire)
-    hipStream_t st_pass = nullptr, st_own_hi = nullptr, st_own_lo = nullptr;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    bool dual = false;
     const double *x0 = nullptr; // warm start (gml_learn_warm): the rows to start from, reference layout [R][P], host or device; NULL = zeros
     int32_t *dColsRef = nullptr; // multi-body: column of every parameter slot of every local row (:94-104), built once (warm start, finish)
     int compact_skip = 0, compact_backoff = 0; // passes that do not try the column compaction after one that came out dense (run_pass)
     bool underflow = false; // the solve ended because a row's weights left the fixed-point range at an iterate (gml_learn: auto -> FP64)
     bool at_zero = false; // the pass being queued evaluates X = 0 (the first pass of a solve; also its rescaled re-runs)
-    ~Solver() { // (each handle by itself: init may have returned between two of the four creations)
-        if (st_own_hi) (void)hipStreamSynchronize(st_own_hi);
-        if (st_own_lo) (void)hipStreamSynchronize(st_own_lo);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-        if (st_own_hi) (void)hipStreamDestroy(st_own_hi);
-        if (st_own_lo) (void)hipStreamDestroy(st_own_lo);
-    }
     double tune[GML_NTUNE] = {}; // the experiment knobs as they stood when the solve began (gml_test_tune may be called meanwhile)
     Stage stg;
     Arena A;
@@ -197,7 +185,8 @@ struct Solver {
     const size_t nd;
     int capW = 0, capP = 0;
     double lambda = 0;
-    int64_t Smain = 0, Scap = 0; // slots of the int8-limb workspace: main range (V planes feed the Hessians) + scratch range
+    int64_t Scap = 0;  // slots of the int8-limb workspace
+    PlaneSlots slots;  // ... and which row owns which V planes in them (gml_slots.h)
     double viol_frac = 0.5, cg_eta = 0.05, eta_admit = 0.25;
     int maxcg = 16, hv_lf = 2, hv_lb = 2;
     int64_t dbg_row = 0, worst_row = 0;
@@ -215,7 +204,6 @@ struct Solver {
     double *Rv = nullptr, *Pv = nullptr, *Hp = nullptr, *Zv = nullptr; // CG vectors, on first use
     uint8_t *Wm = nullptr;                                             // ... and the mask of the system's coordinates
     FaceOut *dFaces = nullptr;
-    bool use_secant = true;
     int face_rounds = 2;      // re-solves of a CG system without the coordinates its step would push through zero
     double face_share = 0.05; // ... for the rows where those carry more than this share of the predicted decrease
     uint8_t *kind = nullptr;
@@ -230,7 +218,7 @@ struct Solver {
     TrialOut *dTrial = nullptr;
     int64_t dH_elems = 0;
     // pointers into dHctl (set by direction_blocks)
-    int *dMt = nullptr, *dVslot = nullptr;
+    int *dMt = nullptr, *dPlane = nullptr;
     long long *dHoff = nullptr;
     double *dS1 = nullptr, *dS1cg = nullptr;
     // secant pairs of the Cholesky rows (k_secant): previous working set, x and g on it, the last two (s, y)
@@ -247,15 +235,13 @@ struct Solver {
     int *dNw = nullptr;              // |W| by local row
     void *dHvsBuf = nullptr;
     size_t hvs_bytes = 0;
-    bool hv_sparse = true;
     double hv_sparse_ratio = g_hv_sparse_ratio; // sparse when sum |W| of the live rows < ratio * columns * node tiles of the GEMM pass
-    int64_t n_hv_sparse = 0;
     int64_t tile_cap = 0, ntiles = 0, tile_base = 0; // capacity of dFV / dgV in tiles; tiles of this iteration; offset of the first in dH
 
     // ---- host state (scalars per row) ------------------------------------------------------------------------------------
     std::vector<double> f, ft, Fobj, kkt, best, Z, Zt, alpha, dd, fn, fnt, l1t, Fbest;
-    std::vector<uint8_t> done, vstale, atfloor, nreg, accepted_fwd, need, iscg;
-    std::vector<int> stall, msz, nW, vslot, vprev, owner, pslot;
+    std::vector<uint8_t> done, atfloor, nreg, accepted_fwd, need, iscg;
+    std::vector<int> stall, msz, nW;
     // per-row results of k_select / k_trial + k_back / the passes' last kernels: written by the kernels straight into pinned host
     // memory (Stage::persist) and read here after the stream has been waited for; device arrays + one download each when the
     // pinned arena is too small for them (tens of thousands of local rows)
@@ -267,12 +253,16 @@ struct Solver {
     std::vector<SlotResult> res_v;
     bool zc = false;
     double *dStepn = nullptr; // |trial - x|_1 by row, left on the device by k_trial: scales the weights' unit of the trial pass (k_quant_theta)
-    int64_t slot_next = 0;
     // Scale of the fixed-point V (int8 path): instead of the worst-case bound w_max exp(sum|theta|) every pass after a row's
     // first uses vref = max_k |V_rk| measured by its previous pass, times exp(||theta - theta_ref||_1), which bounds the new
     // weights rigorously (|E_k' - E_k| <= ||theta' - theta||_1).  Near the optimum the steps are tiny, so V keeps all 31 bits
     // relative to its actual maximum and the noise floor of f and grad drops by the bits the bound would have wasted.
     std::vector<double> vref, dref, stepn;
+    // where a pass leaves its results, by row: f (or log Z), Z (logRISE), the noise of f -- at the iterates, at the trial points
+    struct PassOut {
+        std::vector<double> &f, &Z, &noise;
+    };
+    const PassOut at_x{f, Z, fn}, at_xt{ft, Zt, fnt};
     // sub-sampled Newton: Hessians over Kh configurations -- every kstride-th block of 512 (set_kh)
     int64_t Kh_base = 0, nblk512 = 0, Kh = 0, kstride = 1;
     double hscale = 1.0;
@@ -291,6 +281,11 @@ struct Solver {
     // still building its support: violators at the scale of the support itself (k_select admits them by halves of the largest
     // violation; once they are few next to the support, all at once)
     bool admitting(int64_t r) const { return (int64_t)sel[r].nviol * 16 > sel[r].nsupp; }
+    void reopen(int r) { // a finished row is solved on (other arithmetic): its best-iterate record and its stall count start over
+        done[r] = atfloor[r] = 0;
+        stall[r] = 0;
+        best[r] = Fbest[r] = INFINITY;
+    }
     int upload_rows(const std::vector<int> &rows, int *dst) {
         if (!rows.empty()) HIPCHK(stg.h2d(dst, rows.data(), sizeof(int) * rows.size()));
         return GML_OK;
@@ -298,13 +293,9 @@ struct Solver {
     // a row list (or any small control array) for kernels queued before the next wait: read from the pinned arena where it fits,
     // else uploaded to `fallback`
     template <typename T> int ctl(const std::vector<T> &v, T *fallback, const T **out) {
-        *out = fallback;
-        if (v.empty()) return GML_OK;
-        if (const T *q = stg.put(v.data(), v.size())) {
-            *out = q;
-            return GML_OK;
-        }
-        HIPCHK(stg.h2d(fallback, v.data(), sizeof(T) * v.size()));
+        const T *q = v.empty() ? nullptr : stg.put(v.data(), v.size());
+        *out = q ? q : fallback;
+        if (!q && !v.empty()) HIPCHK(stg.h2d(fallback, v.data(), sizeof(T) * v.size()));
         return GML_OK;
     }
     int fetch(void *host, const void *dev, size_t bytes) { // results the kernels left in device arrays (not zero-copy)
@@ -313,14 +304,27 @@ struct Solver {
     }
 
     int init();
-    void set_kh(int64_t nactive, int maxm = 512);
-    // One objective(/gradient) pass over the listed rows.  src: X or Xt; dst: G or Gt (want_grad); results per row: fo (f,
-    // or log Z), zo (Z, logRISE), no (noise of f).  pp: the arithmetic of this pass (the solver's current precision; the
-    // FP64 phase borrows int8 passes for the V planes its matrix-free rows need).  after: queued on the stream right behind
-    // the pass and before the host waits for it (the acceptance scalars of a trial ride along with the pass results).
-    int run_pass(const std::vector<int> &rows, const double *src, double *dst, bool want_grad, bool at_trial, std::vector<double> &fo,
-                 std::vector<double> &zo, std::vector<double> &no, const std::vector<double> *ovr_in, int depth, int pp,
+    void set_kh(int64_t nactive);
+    // One objective(/gradient) pass over the listed rows.  src: X or Xt; dst: G or Gt (want_grad); out: where the results per row
+    // go.  pp: the arithmetic of this pass (< 0: the solver's current precision; the FP64 phase borrows int8 passes for the V planes
+    // its matrix-free rows need).  after: queued on the stream right behind the pass and before the host waits for it (the
+    // acceptance scalars of a trial ride along with the pass results).  step_on_device: a trial whose |trial - x|_1 is still on
+    // the device (dStepn) and comes down with the results.
+    int run_pass(const std::vector<int> &rows, const double *src, double *dst, bool want_grad, bool at_trial, const PassOut &out, int pp = -1,
                  const std::function<int()> *after = nullptr, bool step_on_device = false);
+    struct PassArgs { // what every round of one run_pass call shares
+        const double *src;
+        double *dst;
+        bool want_grad, at_trial;
+        int pp;
+        const std::function<int()> *after;
+    };
+    using PassRaw = std::vector<SlotResult>; // per listed row, as the kernels left it: f (or Z); on the int8 path also tau and mmax
+    int pass_i8(const PassArgs &q, const std::vector<int> &rows, const std::vector<double> *ovr_in, bool step_on_device, PassRaw &raw);
+    int pass_f64(const PassArgs &q, const std::vector<int> &rows, PassRaw &raw);
+    void compaction_backoff(const std::vector<int> &ctab);
+    void judge_rows(const PassArgs &q, const std::vector<int> &rows, const PassRaw &raw, const PassOut &out, std::vector<int> &again,
+                    std::vector<double> &ovr2);
     int select(int it, int64_t *nactive);
     int start_polish(bool *started);
     int refresh_stale();
@@ -377,19 +381,6 @@ int Solver::init() {
         for (int i = 0; i < GML_NTUNE; ++i) tune[i] = g_tune[i];
         if (tune[GML_TUNE_NO_ZEROCOPY] > 0) stg.mapped = false; // (tests: the copy path that very large handles take)
     }
-    st_pass = st;
-    if (tune[GML_TUNE_DUAL_STREAMS] > 0 && gml_is_i8(o.precision)) {
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamSynchronize(st)); // (what the handle's own stream still holds: the samples' images)
-        HIPCHK(hipStreamCreateWithPriority(&st_own_hi, hipStreamNonBlocking, greatest));
-        HIPCHK(hipStreamCreateWithPriority(&st_own_lo, hipStreamNonBlocking, tune[GML_TUNE_DUAL_STREAMS] > 1 ? greatest : least));
-        HIPCHK(hipEventCreateWithFlags(&ev_a, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming));
-        st = st_own_hi;
-        st_pass = st_own_lo;
-        dual = true;
-    }
     stg.base = p->stage;
     stg.cap = p->stage_bytes;
     stg.st = st;
@@ -408,8 +399,9 @@ int Solver::init() {
     // slots of the int8-limb workspace: every active row of a pass in its own slot, the passes of one iteration in
     // disjoint ranges (their V planes feed the next Hessians).  Objective-only passes (line-search trials whose V planes
     // nobody reads) run in a scratch range above the main one.
-    Smain = gml_is_i8(o.precision) ? Rp + gml_round_up(std::max<int64_t>(R / 2, 96), 32) + 64 : Rp + 64;
+    const int64_t Smain = gml_is_i8(o.precision) ? Rp + gml_round_up(std::max<int64_t>(R / 2, 96), 32) + 64 : Rp + 64;
     Scap = Smain + Rp;
+    if (!slots.reset(R, Smain, Scap)) return fail(GML_EHIP, "internal: %lld rows do not fit the slot ranges %lld + %lld", (long long)R, (long long)Smain, (long long)(Scap - Smain));
     {
         size_t freeb = 0, totalb = 0;
         HIPCHK(dev_mem_info(&freeb, &totalb));
@@ -491,30 +483,11 @@ int Solver::init() {
     }
     launch_kind(d, p->order, dNode, (int)Rp, kind, st);
 
-    f.assign((size_t)R, 0.0);
-    ft.assign((size_t)R, 0.0);
-    Fobj.assign((size_t)R, 0.0);
-    kkt.assign((size_t)R, INFINITY);
-    best.assign((size_t)R, INFINITY);
-    Z.assign((size_t)R, 1.0);
-    Zt.assign((size_t)R, 1.0);
-    alpha.assign((size_t)R, 1.0);
-    dd.assign((size_t)R, 0.0);
-    fn.assign((size_t)R, 0.0);
-    fnt.assign((size_t)R, 0.0);
-    l1t.assign((size_t)R, 0.0);
-    Fbest.assign((size_t)R, INFINITY);
-    for (auto *v : {&done, &vstale, &atfloor, &nreg, &accepted_fwd, &need, &iscg}) v->assign((size_t)R, 0);
-    stall.assign((size_t)R, 0);
-    msz.assign((size_t)R, 0);
-    nW.assign((size_t)R, 0);
-    vslot.assign((size_t)R, -1);
-    vprev.assign((size_t)R, -1);
-    pslot.assign((size_t)R, -1);
-    owner.assign((size_t)Scap, -1);
-    vref.assign((size_t)R, 0.0);
-    dref.assign((size_t)R, 0.0);
-    stepn.assign((size_t)R, 0.0);
+    for (auto *v : {&f, &ft, &Fobj, &dd, &fn, &fnt, &l1t, &vref, &dref, &stepn}) v->assign((size_t)R, 0.0);
+    for (auto *v : {&Z, &Zt, &alpha}) v->assign((size_t)R, 1.0);
+    for (auto *v : {&kkt, &best, &Fbest}) v->assign((size_t)R, INFINITY);
+    for (auto *v : {&done, &atfloor, &nreg, &accepted_fwd, &need, &iscg}) v->assign((size_t)R, 0);
+    for (auto *v : {&stall, &msz, &nW}) v->assign((size_t)R, 0);
 
     if (gml_is_i8(o.precision) && o.polish >= 0) {
         size_t freeb = 0, totalb = 0;
@@ -544,10 +517,9 @@ int Solver::init() {
     return GML_OK;
 }
 
-void Solver::set_kh(int64_t nactive, int maxm) {
+void Solver::set_kh(int64_t nactive) {
     // (a budget scaled to the working-set size -- 64 configurations per entry, 8192 at least -- was measured and dropped: the
     // headline problem then needs 20-22 iterations instead of 14)
-    (void)maxm;
     int64_t want = Kh_base;
     if (o.hess_samples == 0 && nactive > 0) want = Kh_base * std::max<int64_t>(1, R / nactive);
     int64_t nb = std::min(nblk512, std::max<int64_t>(2, (want + 511) / 512));
@@ -565,267 +537,232 @@ void Solver::set_kh(int64_t nactive, int maxm) {
     hscale = nb == nblk512 ? 1.0 : 1.0 / wsum; // rescaled by the weight of the sub-sample
 }
 
-int Solver::run_pass(const std::vector<int> &rows, const double *src, double *dst, bool want_grad, bool at_trial, std::vector<double> &fo,
-                     std::vector<double> &zo, std::vector<double> &no, const std::vector<double> *ovr_in, int depth, int pp,
+int Solver::run_pass(const std::vector<int> &rows, const double *src, double *dst, bool want_grad, bool at_trial, const PassOut &out, int pp,
                      const std::function<int()> *after, bool step_on_device) {
-    const int64_t n = (int64_t)rows.size();
-    if (n == 0) return GML_OK;
+    if (rows.empty()) return GML_OK;
     const double t0 = gml_now_s();
-    trace(want_grad ? "pass" : "fwd pass");
-    const int64_t np = gml_round_up(n, 32);
-    std::vector<double> fh, tauh;
-    std::vector<unsigned> mmh;
-    const bool track = gml_is_i8(pp) && formulation != GML_RPLE;
-    const bool wide = pp == GML_PREC_I8W;
-    if (gml_is_i8(pp)) {
-        // slots of this pass: a fresh consecutive range, or (re-run of some rows of a pass with a tighter scale: ovr_in)
-        // the slots those rows already hold -- a re-run must not claim new slots, it could wrap around and overwrite
-        // planes of its own pass
-        std::vector<int64_t> slot((size_t)n);
-        int64_t lo, hi;
-        if (ovr_in) {
-            lo = Scap;
-            hi = 0;
-            for (int64_t a = 0; a < n; ++a) {
-                slot[a] = pslot[rows[a]];
-                lo = std::min(lo, slot[a] / 32 * 32);
-                hi = std::max(hi, slot[a] / 32 * 32 + 32);
+    const PassArgs q{src, dst, want_grad, at_trial, pp < 0 ? prec : pp, after};
+    // Round 0 evaluates the listed rows.  Rows whose weights turn out to use less of the fixed-point range than their scale allowed
+    // (judge_rows) run again with a tighter one, up to six times: in the slots they hold, with the host's stepn (round 0 brought it
+    // down), and with `after` repeated -- what it queued for these rows was computed from the first run's gradient.
+    std::vector<int> cur = rows, again;
+    std::vector<double> ovr, ovr2;
+    int rc = GML_OK;
+    for (int round = 0; rc == GML_OK && !cur.empty(); ++round) {
+        trace(want_grad ? "pass" : "fwd pass");
+        PassRaw raw;
+        rc = gml_is_i8(q.pp) ? pass_i8(q, cur, round ? &ovr : nullptr, step_on_device && round == 0, raw) : pass_f64(q, cur, raw);
+        if (rc) break;
+        if (step_on_device && round == 0) // (the trial's scalars came down with the pass)
+            for (int r : cur) stepn[r] = trial[r].stepn;
+        judge_rows(q, cur, raw, out, again, ovr2);
+        stats.node_evals += (int64_t)cur.size();
+        if (want_grad) ++stats.passes;
+        else ++stats.forward_passes;
+        if (!again.empty() && round >= 6) {
+            // the weights exp(-E) of these rows underflow the fixed-point range even after six rescalings (|theta|_1 in the
+            // hundreds): a trial point that far out is simply rejected; at the iterate itself it is an error
+            if (!at_trial) {
+                underflow = true;
+                rc = fail(GML_EUNSUPPORTED, "precision %s: the weights exp(-E) of a row underflow its fixed-point range at an iterate; use precision f64 "
+                                            "(or auto, which does so by itself)", q.pp == GML_PREC_I8W ? "i8w" : "i8x");
+                break;
             }
-        } else if (!want_grad && at_trial) {
-            // objective-only trial: scratch slots, the rows keep the V planes of their iterates
-            lo = Smain;
-            hi = Smain + np;
-            for (int64_t a = 0; a < n; ++a) slot[a] = Smain + a;
-        } else {
-            int64_t base = gml_round_up(slot_next, 32);
-            if (base + np > Smain) base = 0; // wrap: the rows whose V planes are overwritten become stale below
-            slot_next = base + np;
-            lo = base;
-            hi = base + np;
-            for (int64_t a = 0; a < np; ++a) {
-                const int64_t s = base + a;
-                const int prev = owner[s];
-                if (prev >= 0 && vslot[prev] == s) {
-                    vslot[prev] = -1;
-                    vstale[prev] = 1;
-                }
-                owner[s] = a < n ? rows[a] : -1;
+            for (int r : again) {
+                out.f[r] = INFINITY;
+                out.noise[r] = 0.0;
             }
-            for (int64_t a = 0; a < n; ++a) {
-                const int r = rows[a];
-                slot[a] = base + a;
-                vprev[r] = at_trial ? vslot[r] : -1; // a rejected trial goes back to the planes of the iterate, if they survive
-                vslot[r] = (int)(base + a);
-                vstale[r] = 0;
-            }
+            break;
         }
-        for (int64_t a = 0; a < n; ++a) pslot[rows[a]] = (int)slot[a];
-        const int64_t ns = hi - lo;
-        // control block of the pass, one upload: srow [ns] | rowcol [ns] | tiles, padded with -1 to a multiple of 4 | tau [ns]
-        std::vector<uint8_t> tile((size_t)(ns / 32), 0);
-        for (int64_t a = 0; a < n; ++a) tile[(slot[a] - lo) / 32] = 1;
-        int ng = 0;
-        for (int64_t g = 0; g < ns / 32; ++g) ng += tile[g];
-        const int ng4 = (int)gml_round_up(ng, 4);
-        const size_t ints = (size_t)(2 * ns + ng4), ioff = (ints * sizeof(int) + 7) & ~(size_t)7;
-        std::vector<char> blk(ioff + sizeof(double) * ns, 0);
-        int *srow = reinterpret_cast<int *>(blk.data()), *rowcol = srow + ns, *groups = rowcol + ns;
-        double *ovr = reinterpret_cast<double *>(blk.data() + ioff);
-        for (int64_t q = 0; q < ns; ++q) rowcol[q] = -1;
-        for (int64_t a = 0; a < n; ++a) {
-            const int64_t q = slot[a] - lo;
-            const int r = rows[a];
-            srow[q] = r;
-            rowcol[q] = (int)(p->node0 + r);
-            if (ovr_in) ovr[q] = (*ovr_in)[r];
-            else if (track && vref[r] > 0.0) // (step_on_device: times exp(|trial - x|_1), which k_trial left in dStepn)
-                ovr[q] = vref[r] * std::exp(dref[r] + (at_trial && !step_on_device ? stepn[r] : 0.0)) * (1.0 + 1e-6) / i8_vdiv(wide);
-        }
-        {
-            int k = 0;
-            for (int64_t g = 0; g < ns / 32; ++g)
-                if (tile[g]) groups[k++] = (int)(lo / 32 + g);
-            for (; k < ng4; ++k) groups[k] = -1;
-        }
-        HIPCHK(stg.h2d(dPass, blk.data(), blk.size()));
-        const int *dsrow = reinterpret_cast<const int *>(dPass);
-        I8Pass a{};
-        a.theta = src;
-        a.srow = rebase(dsrow, lo); // indexed by slot on the device
-        a.rowcol = rebase(dsrow + ns, lo);
-        a.groups = dsrow + 2 * ns;
-        a.ngroups = ng;
-        a.slot0 = (int)lo;
-        a.slot1 = (int)hi;
-        a.form = formulation;
-        a.want_grad = want_grad;
-        a.F = dFs;
-        a.G = dst;
-        a.tauovr = rebase(reinterpret_cast<const double *>(dPass + ioff), lo);
-        a.tauovr_lnrow = !ovr_in && track && step_on_device ? dStepn : nullptr;
-        a.res = kRes;
-        a.lf = o.limbs_fwd;
-        a.wide = wide;
-        a.coarse = coarse_on;
-        a.zero_theta = at_zero && tune[GML_TUNE_NO_ZERO_SHORTCUT] == 0; // the first pass of a solve: X = 0 for every row
-        // Column compaction of the forward GEMM.  It pays where the rows are sparse RELATIVE TO THE COLUMN COUNT: multi-body
-        // statistics, thousands of spins (config 5 at c = 1.2: 25 non-zeros of 130 817 per node, learn() 3.5 -> 2.2 s).  With the
-        // 1 024 columns of the headline problem a tile's 32 rows cover every column after the third pass and the two extra launches
-        // cost a 128-node shard 5 %: problems below 4 096 columns do not try.  A pass whose tiles came out (mostly) dense makes the
-        // next 2, 4, ... 16 passes skip the attempt.
-        const bool may_compact = tune[GML_TUNE_NO_COMPACT] == 0 && (tune[GML_TUNE_SOLVER_COMPACT] > 0 || d.Qfp >= 4096);
-        if (may_compact && compact_skip > 0) --compact_skip;
-        else a.compact = may_compact;
-        std::string err;
-        if (dual) { // the pass behind what this handle has queued so far, on the low-priority stream
-            HIPCHK(hipEventRecord(ev_a, st));
-            HIPCHK(hipStreamWaitEvent(st_pass, ev_a, 0));
-        }
-        int rc = i8_pass(&p->i8ws, d, Scap, a, st_pass, nullptr, &err);
-        if (rc) return fail(rc, "%s", err.c_str());
-        if (dual) { // ... and everything that follows behind the pass
-            HIPCHK(hipEventRecord(ev_b, st_pass));
-            HIPCHK(hipStreamWaitEvent(st, ev_b, 0));
-        }
-        if (formulation == GML_LOGRISE && want_grad) // grad log Z = grad Z / Z (:279), Z from the pass results on the device
-            launch_scale_slots_inv(a.srow, a.rowcol, (int)lo, (int)ns, kRes, Qp, dst, st);
-        RCCHK(fetch(res + lo, dRes + lo, sizeof(SlotResult) * ns));
-        if (after) RCCHK((*after)());
-        HIPCHK(hipGetLastError());
-        std::vector<int> ctab;
-        if (a.compact) { // what the compaction made of this pass comes down with its results
-            const int *dcnk = nullptr;
-            int cs = 0;
-            i8_compact_table(p->i8ws, &dcnk, &cs);
-            if (dcnk) {
-                ctab.assign((size_t)(hi - lo) / 32, 0);
-                HIPCHK(stg.d2h(ctab.data(), dcnk + lo / 32, sizeof(int) * ctab.size()));
-            }
-        }
-        HIPCHK(stg.sync());
-        if (!ctab.empty()) {
-            const int nk_all = (int)(d.Qfp / 64);
-            long long swept = 0;
-            for (int v : ctab) swept += v < 0 ? nk_all : v;
-            if ((double)swept > 0.6 * (double)nk_all * (double)ctab.size()) {
-                compact_backoff = std::min(16, std::max(2, 2 * compact_backoff));
-                compact_skip = compact_backoff;
-            } else {
-                compact_backoff = 0;
-            }
-            if (o.verbose >= 2)
-                fprintf(stderr, "[gml]   compaction: %lld of %lld column steps swept over %zu tiles%s\n", swept, (long long)nk_all * (long long)ctab.size(),
-                        ctab.size(), compact_skip ? " (the next passes do not try)" : "");
-        }
-        if (step_on_device) // (the trial's scalars came down with the pass)
-            for (int64_t a2 = 0; a2 < n; ++a2) stepn[rows[a2]] = trial[rows[a2]].stepn;
-        fh.resize((size_t)n);
-        tauh.resize((size_t)n);
-        mmh.resize((size_t)n);
-        for (int64_t a2 = 0; a2 < n; ++a2) {
-            const SlotResult &q = res[(size_t)slot[a2]];
-            fh[a2] = q.f;
-            tauh[a2] = q.tau;
-            mmh[a2] = q.mmax;
-        }
-    } else {
-        // FP64 path: slot = row; a tile's backward GEMM writes every row of the tile, so the gradient goes to a
-        // scratch array first and only the listed rows are copied out
-        int rc = gml_ensure_f64(p, Rp);
-        if (rc) return rc;
-        if (!Gs) HIPCHK(A.get(&Gs, nd));
-        std::vector<int> ctl((size_t)(Rp + Rp / 32 + 8), -1);
-        std::vector<uint8_t> tile((size_t)(Rp / 32), 0);
-        for (int64_t a = 0; a < n; ++a) {
-            ctl[rows[a]] = (int)(p->node0 + rows[a]);
-            tile[rows[a] >> 5] = 1;
-        }
-        int ng = 0;
-        for (int64_t g = 0; g < Rp / 32; ++g)
-            if (tile[g]) ctl[Rp + ng++] = (int)g;
-        const int ng4 = (int)gml_round_up(ng, 4);
-        int *dctl = reinterpret_cast<int *>(dPass);
-        HIPCHK(stg.h2d(dctl, ctl.data(), sizeof(int) * (Rp + ng4)));
-        HIPCHK(hipMemsetAsync(dFs, 0, sizeof(double) * Rp, st));
-        launch_fwd_f64(d, src, dctl, dctl + Rp, ng4, formulation, p->dV, dFs, st);
-        if (want_grad) {
-            HIPCHK(hipMemsetAsync(Gs, 0, sizeof(double) * nd, st));
-            launch_bwd_f64(d, p->dV, dctl + Rp, ng, Gs, st);
-            RCCHK(upload_rows(rows, dRowsP));
-            launch_copy_rows(dRowsP, (int)n, Qp, Gs, dst, nullptr, nullptr, st);
-            if (formulation == GML_LOGRISE) launch_scale_rows_inv(dRowsP, (int)n, dFs, Qp, dst, st);
-        }
-        fh.resize((size_t)Rp);
-        HIPCHK(stg.d2h(fh.data(), dFs, sizeof(double) * Rp));
-        for (int64_t a = 0; a < n; ++a) { // (V [row][Kp] of the FP64 path is indexed by row)
-            vstale[rows[a]] = 0;
-            if (vslot[rows[a]] < 0) vslot[rows[a]] = 0;
-        }
-        if (after) RCCHK((*after)());
-        HIPCHK(hipGetLastError());
-        HIPCHK(stg.sync());
-        if (step_on_device)
-            for (int64_t a2 = 0; a2 < n; ++a2) stepn[rows[a2]] = trial[rows[a2]].stepn;
+        cur.swap(again);
+        ovr.swap(ovr2);
     }
-    std::vector<int> again;
-    std::vector<double> ovr2;
+    stats.t_pass += gml_now_s() - t0;
+    return rc;
+}
+
+// One round on the int8-limb kernels: the rows' slots, the control block (one upload), the pass, and one wait for its results.
+// ovr_in: by row, the scales of a re-run (run_pass), which keeps the slots its rows hold.
+int Solver::pass_i8(const PassArgs &q, const std::vector<int> &rows, const std::vector<double> *ovr_in, bool step_on_device, PassRaw &raw) {
+    const int64_t n = (int64_t)rows.size();
+    const bool track = formulation != GML_RPLE, wide = q.pp == GML_PREC_I8W;
+    // objective-only trial: scratch slots, the rows keep the V planes of their iterates; else a fresh range of the main slots
+    const PlaneSlots::Range g = ovr_in ? slots.held(rows) : !q.want_grad && q.at_trial ? slots.scratch(rows) : slots.claim(rows, q.at_trial);
+    const int64_t lo = g.lo, hi = g.hi, ns = hi - lo;
+    // control block of the pass, one upload: srow [ns] | rowcol [ns] | tiles, padded with -1 to a multiple of 4 | tau [ns]
+    std::vector<uint8_t> tile((size_t)(ns / 32), 0);
+    for (int64_t a = 0; a < n; ++a) tile[(g.slot[a] - lo) / 32] = 1;
+    int ng = 0;
+    for (int64_t t = 0; t < ns / 32; ++t) ng += tile[t];
+    const int ng4 = (int)gml_round_up(ng, 4);
+    const size_t ints = (size_t)(2 * ns + ng4), ioff = (ints * sizeof(int) + 7) & ~(size_t)7;
+    std::vector<char> blk(ioff + sizeof(double) * ns, 0);
+    int *srow = reinterpret_cast<int *>(blk.data()), *rowcol = srow + ns, *groups = rowcol + ns;
+    double *ovr = reinterpret_cast<double *>(blk.data() + ioff);
+    for (int64_t s = 0; s < ns; ++s) rowcol[s] = -1;
     for (int64_t a = 0; a < n; ++a) {
+        const int64_t s = g.slot[a] - lo;
         const int r = rows[a];
-        const double fv = gml_is_i8(pp) ? fh[a] : fh[r];
+        srow[s] = r;
+        rowcol[s] = (int)(p->node0 + r);
+        if (ovr_in) ovr[s] = (*ovr_in)[r];
+        else if (track && vref[r] > 0.0) // (step_on_device: times exp(|trial - x|_1), which k_trial left in dStepn)
+            ovr[s] = vref[r] * std::exp(dref[r] + (q.at_trial && !step_on_device ? stepn[r] : 0.0)) * (1.0 + 1e-6) / i8_vdiv(wide);
+    }
+    {
+        int k = 0;
+        for (int64_t t = 0; t < ns / 32; ++t)
+            if (tile[t]) groups[k++] = (int)(lo / 32 + t);
+        for (; k < ng4; ++k) groups[k] = -1;
+    }
+    HIPCHK(stg.h2d(dPass, blk.data(), blk.size()));
+    const int *dsrow = reinterpret_cast<const int *>(dPass);
+    I8Pass a{};
+    a.theta = q.src;
+    a.srow = rebase(dsrow, lo); // indexed by slot on the device
+    a.rowcol = rebase(dsrow + ns, lo);
+    a.groups = dsrow + 2 * ns;
+    a.ngroups = ng;
+    a.slot0 = (int)lo;
+    a.slot1 = (int)hi;
+    a.form = formulation;
+    a.want_grad = q.want_grad;
+    a.F = dFs;
+    a.G = q.dst;
+    a.tauovr = rebase(reinterpret_cast<const double *>(dPass + ioff), lo);
+    a.tauovr_lnrow = !ovr_in && track && step_on_device ? dStepn : nullptr;
+    a.res = kRes;
+    a.lf = o.limbs_fwd;
+    a.wide = wide;
+    a.coarse = coarse_on;
+    a.zero_theta = at_zero && tune[GML_TUNE_NO_ZERO_SHORTCUT] == 0; // the first pass of a solve: X = 0 for every row
+    // Column compaction of the forward GEMM.  It pays where the rows are sparse RELATIVE TO THE COLUMN COUNT: multi-body
+    // statistics, thousands of spins (config 5 at c = 1.2: 25 non-zeros of 130 817 per node, learn() 3.5 -> 2.2 s).  With the
+    // 1 024 columns of the headline problem a tile's 32 rows cover every column after the third pass and the two extra launches
+    // cost a 128-node shard 5 %: problems below 4 096 columns do not try.  A pass whose tiles came out (mostly) dense makes the
+    // next 2, 4, ... 16 passes skip the attempt.
+    const bool may_compact = tune[GML_TUNE_NO_COMPACT] == 0 && (tune[GML_TUNE_SOLVER_COMPACT] > 0 || d.Qfp >= 4096);
+    if (may_compact && compact_skip > 0) --compact_skip;
+    else a.compact = may_compact;
+    std::string err;
+    const int rc = i8_pass(&p->i8ws, d, Scap, a, st, nullptr, &err);
+    if (rc) return fail(rc, "%s", err.c_str());
+    if (formulation == GML_LOGRISE && q.want_grad) // grad log Z = grad Z / Z (:279), Z from the pass results on the device
+        launch_scale_slots_inv(a.srow, a.rowcol, (int)lo, (int)ns, kRes, Qp, q.dst, st);
+    RCCHK(fetch(res + lo, dRes + lo, sizeof(SlotResult) * ns));
+    if (q.after) RCCHK((*q.after)());
+    HIPCHK(hipGetLastError());
+    std::vector<int> ctab;
+    if (a.compact) { // what the compaction made of this pass comes down with its results
+        const int *dcnk = nullptr;
+        int cs = 0;
+        i8_compact_table(p->i8ws, &dcnk, &cs);
+        if (dcnk) {
+            ctab.assign((size_t)ns / 32, 0);
+            HIPCHK(stg.d2h(ctab.data(), dcnk + lo / 32, sizeof(int) * ctab.size()));
+        }
+    }
+    HIPCHK(stg.sync());
+    if (!ctab.empty()) compaction_backoff(ctab);
+    raw.resize((size_t)n);
+    for (int64_t a2 = 0; a2 < n; ++a2) raw[a2] = res[(size_t)g.slot[a2]];
+    return GML_OK;
+}
+
+// ctab: per tile of the pass just waited for, the column steps its compacted forward GEMM swept (< 0: all of them)
+void Solver::compaction_backoff(const std::vector<int> &ctab) {
+    const int nk_all = (int)(d.Qfp / 64);
+    long long swept = 0;
+    for (int v : ctab) swept += v < 0 ? nk_all : v;
+    if ((double)swept > 0.6 * (double)nk_all * (double)ctab.size()) {
+        compact_backoff = std::min(16, std::max(2, 2 * compact_backoff));
+        compact_skip = compact_backoff;
+    } else {
+        compact_backoff = 0;
+    }
+    if (o.verbose >= 2)
+        fprintf(stderr, "[gml]   compaction: %lld of %lld column steps swept over %zu tiles%s\n", swept, (long long)nk_all * (long long)ctab.size(),
+                ctab.size(), compact_skip ? " (the next passes do not try)" : "");
+}
+
+// One round on the FP64 path: slot = row; a tile's backward GEMM writes every row of the tile, so the gradient goes to a
+// scratch array first and only the listed rows are copied out
+int Solver::pass_f64(const PassArgs &q, const std::vector<int> &rows, PassRaw &raw) {
+    const int64_t n = (int64_t)rows.size();
+    RCCHK(gml_ensure_f64(p, Rp));
+    if (!Gs) HIPCHK(A.get(&Gs, nd));
+    std::vector<int> ctl((size_t)(Rp + Rp / 32 + 8), -1);
+    std::vector<uint8_t> tile((size_t)(Rp / 32), 0);
+    for (int r : rows) {
+        ctl[r] = (int)(p->node0 + r);
+        tile[r >> 5] = 1;
+    }
+    int ng = 0;
+    for (int64_t t = 0; t < Rp / 32; ++t)
+        if (tile[t]) ctl[Rp + ng++] = (int)t;
+    const int ng4 = (int)gml_round_up(ng, 4);
+    int *dctl = reinterpret_cast<int *>(dPass);
+    HIPCHK(stg.h2d(dctl, ctl.data(), sizeof(int) * (Rp + ng4)));
+    HIPCHK(hipMemsetAsync(dFs, 0, sizeof(double) * Rp, st));
+    launch_fwd_f64(d, q.src, dctl, dctl + Rp, ng4, formulation, p->dV, dFs, st);
+    if (q.want_grad) {
+        HIPCHK(hipMemsetAsync(Gs, 0, sizeof(double) * nd, st));
+        launch_bwd_f64(d, p->dV, dctl + Rp, ng, Gs, st);
+        RCCHK(upload_rows(rows, dRowsP));
+        launch_copy_rows(dRowsP, (int)n, Qp, Gs, q.dst, nullptr, nullptr, st);
+        if (formulation == GML_LOGRISE) launch_scale_rows_inv(dRowsP, (int)n, dFs, Qp, q.dst, st);
+    }
+    std::vector<double> fh((size_t)Rp);
+    HIPCHK(stg.d2h(fh.data(), dFs, sizeof(double) * Rp));
+    for (int r : rows) slots.set_row_indexed(r); // (V [row][Kp] of the FP64 path is indexed by row)
+    if (q.after) RCCHK((*q.after)());
+    HIPCHK(hipGetLastError());
+    HIPCHK(stg.sync());
+    raw.assign((size_t)n, SlotResult{});
+    for (int64_t a = 0; a < n; ++a) raw[a].f = fh[rows[a]];
+    return GML_OK;
+}
+
+// What the round's results are worth: f and its noise by row into `out`, and on the int8 path the scale the rows' next passes
+// start from (vref, dref).  again / ovr2: the rows that must run once more, and (by row) the tighter scale they run with.
+void Solver::judge_rows(const PassArgs &q, const std::vector<int> &rows, const PassRaw &raw, const PassOut &out, std::vector<int> &again,
+                        std::vector<double> &ovr2) {
+    const bool track = gml_is_i8(q.pp) && formulation != GML_RPLE, wide = q.pp == GML_PREC_I8W;
+    again.clear();
+    ovr2.clear();
+    for (size_t a = 0; a < rows.size(); ++a) {
+        const int r = rows[a];
+        const double fv = raw[a].f;
         // f64: summation rounding.  int8 limbs: every V_rk is rounded to a multiple of tau_r with a dither that is
         // equidistributed over the samples, so the errors (each within one unit, standard deviation 0.41 tau) add like a
         // random walk: 8 sigma of sqrt(K) terms (the worst case K * tau is never approached).
         double noise = 1e-13 * std::max(1.0, std::fabs(fv));
         if (track) {
-            noise += 3.3 * std::sqrt((double)p->K) * tauh[a] * (coarse_on ? i8_coarse_unit(wide) : 1.0); // (coarse: multiples of 2^24 / 2^8 tau)
+            noise += 3.3 * std::sqrt((double)p->K) * raw[a].tau * (coarse_on ? i8_coarse_unit(wide) : 1.0); // (coarse: multiples of 2^24 / 2^8 tau)
             // i8x exp forms: the FP32 expm1 of the forward epilogue (vq_exp) is off by up to 1e-9 of every |V_k| before the rounding
             // (three FP32 roundings of about 2^-24 |r| each, |r| <= ln2/128: 3 * 2^-24 * ln2/128 / (1 - ln2/128) = 9.74e-10; 7.7e-10
             // measured) -- one error for all the samples that share an energy, so it adds up with f, not like a random walk
             if (!wide && formulation != GML_RPLE) noise += 1e-9 * std::fabs(fv);
-            const double vmax = ((double)mmh[a] + 1.0) * i8_mmax_unit(wide) * tauh[a]; // rigorous bound on max_k |V_rk|
+            const double vmax = ((double)raw[a].mmax + 1.0) * i8_mmax_unit(wide) * raw[a].tau; // rigorous bound on max_k |V_rk|
             vref[r] = vmax;
-            dref[r] = at_trial ? stepn[r] : 0.0; // distance from the current iterate to the point just evaluated
+            dref[r] = q.at_trial ? stepn[r] : 0.0; // distance from the current iterate to the point just evaluated
             // Dynamic range: tau_r was derived from a bound; when the largest |V_rk| actually seen is more than 8 bits
             // below it (dense theta), the row is re-run with tau_r taken from that maximum
-            if (mmh[a] < (1u << 23)) {
+            if (raw[a].mmax < (1u << 23)) {
                 if (ovr2.empty()) ovr2.assign((size_t)R, 0.0);
                 again.push_back(r);
                 ovr2[r] = vmax * (1.0 + 1e-12) / i8_vdiv(wide);
             }
         }
         if (formulation == GML_LOGRISE) { // f = log Z, g = grad Z / Z   (:279)
-            zo[r] = fv;
-            fo[r] = std::log(fv);
-            no[r] = noise / fv;
+            out.Z[r] = fv;
+            out.f[r] = std::log(fv);
+            out.noise[r] = noise / fv;
         } else {
-            fo[r] = fv;
-            no[r] = noise;
+            out.f[r] = fv;
+            out.noise[r] = noise;
         }
     }
-    stats.node_evals += n;
-    if (want_grad) ++stats.passes;
-    else ++stats.forward_passes;
-    if (!again.empty()) {
-        stats.t_pass += gml_now_s() - t0;
-        if (depth >= 6) {
-            // the weights exp(-E) of these rows underflow the fixed-point range even after six rescalings (|theta|_1 in the
-            // hundreds): a trial point that far out is simply rejected; at the iterate itself it is an error
-            if (!at_trial) {
-                underflow = true;
-                return fail(GML_EUNSUPPORTED, "precision %s: the weights exp(-E) of a row underflow its fixed-point range at an iterate; use precision f64 "
-                                              "(or auto, which does so by itself)", wide ? "i8w" : "i8x");
-            }
-            for (int r : again) {
-                fo[r] = INFINITY;
-                no[r] = 0.0;
-            }
-            return GML_OK;
-        }
-        // (the re-run repeats `after`: what it queued for these rows was computed from the first run's gradient)
-        RCCHK(run_pass(again, src, dst, want_grad, at_trial, fo, zo, no, &ovr2, depth + 1, pp, after));
-    }
-    if (again.empty()) stats.t_pass += gml_now_s() - t0;
-    return GML_OK;
 }
 
 // KKT residuals and working sets (device); decides which rows are done.
@@ -912,15 +849,9 @@ int Solver::start_polish(bool *started) {
     launch_copy_rows(dRows, (int)fl.size(), Qp, Xb, X, nullptr, nullptr, st); // back to the best iterate
     std::vector<double> inf((size_t)Rp, INFINITY);
     HIPCHK(stg.h2d(dBest, inf.data(), sizeof(double) * Rp));
-    for (int r : fl) {
-        done[r] = 0;
-        atfloor[r] = 0;
-        stall[r] = 0;
-        best[r] = INFINITY;
-        Fbest[r] = INFINITY;
-    }
+    for (int r : fl) reopen(r);
     if (o.verbose) fprintf(stderr, "[gml] polish: %zu rows continue on the FP64 path\n", fl.size());
-    RCCHK(run_pass(fl, X, G, true, false, f, Z, fn, nullptr, 0, prec));
+    RCCHK(run_pass(fl, X, G, true, false, at_x));
     set_kh((int64_t)fl.size());
     stats.polished = 1;
     *started = true;
@@ -934,15 +865,15 @@ int Solver::refresh_stale() {
     for (int round = 0; round < 3; ++round) {
         std::vector<int> stale;
         for (int64_t r = 0; r < R; ++r)
-            if (!done[r] && (vstale[r] || vslot[r] < 0)) stale.push_back((int)r);
+            if (!done[r] && slots.needs_refresh((int)r)) stale.push_back((int)r);
         if (stale.empty()) break;
         if (round == 2) {
             stale.clear();
             for (int64_t r = 0; r < R; ++r)
                 if (!done[r]) stale.push_back((int)r);
-            slot_next = 0;
+            slots.start_over();
         }
-        RCCHK(run_pass(stale, X, G, true, false, f, Z, fn, nullptr, 0, prec));
+        RCCHK(run_pass(stale, X, G, true, false, at_x));
     }
     return GML_OK;
 }
@@ -956,9 +887,9 @@ int Solver::direction_blocks(const std::vector<int> &cg_rows) {
         // an int8-limb objective pass at the same iterate (those run on the int8 cores either way; only the curvature is
         // approximate)
         std::vector<double> tf((size_t)R), tz((size_t)R, 1.0), tn((size_t)R);
-        RCCHK(run_pass(cg_rows, X, nullptr, false, false, tf, tz, tn, nullptr, 0, gml_is_i8(o.precision) ? o.precision : GML_PREC_I8X));
+        RCCHK(run_pass(cg_rows, X, nullptr, false, false, PassOut{tf, tz, tn}, gml_is_i8(o.precision) ? o.precision : GML_PREC_I8X));
     }
-    // layout of the block: mt [R] | node [R] | msz of the Cholesky rows [R] | (unused) [R] | vslot [R] | hoff [R+1] |
+    // layout of the block: mt [R] | node [R] | msz of the Cholesky rows [R] | (unused) [R] | plane slot [R] | hoff [R+1] |
     // s1 [Rp] | ynoise [Rp] | s1cg [Rp]
     const size_t ibytes = (sizeof(int) * 5 * R + 7) & ~(size_t)7, lbytes = sizeof(long long) * (R + 1);
     std::vector<char> blk(ibytes + lbytes + sizeof(double) * 3 * Rp, 0);
@@ -973,7 +904,7 @@ int Solver::direction_blocks(const std::vector<int> &cg_rows) {
         mt2[r] = (m + 31) / 32;
         mt2[R + r] = (int)(p->node0 + r);
         mt2[2 * R + r] = m; // the Cholesky step solves these
-        vs[r] = vslot[r];
+        vs[r] = slots.slot((int)r);
         hoff[r + 1] = hoff[r] + (long long)mt2[r] * 32 * mt2[r] * 32;
         const double zi = formulation == GML_LOGRISE ? 1.0 / Z[r] : 1.0; // Hess log Z = Hess Z / Z - g g^T
         s1[r] = hscale * zi; // sub-sampled blocks
@@ -1030,13 +961,13 @@ int Solver::direction_blocks(const std::vector<int> &cg_rows) {
     }
     for (int64_t r = 0; r < R; ++r) {
         const bool needs_planes = (gml_is_i8(prec) && mt2[r] > 0) || (ntiles > 0 && iscg[r] && !done[r]);
-        if (needs_planes && (vslot[r] < 0 || vslot[r] >= Scap || owner[vslot[r]] != r || vstale[r]))
+        if (needs_planes && !slots.valid((int)r))
             return fail(GML_EHIP, "internal: row %lld enters the Hessian without valid V planes (slot %d, owner %d, stale %d)", (long long)r,
-                        vslot[r], vslot[r] >= 0 && vslot[r] < Scap ? owner[vslot[r]] : -2, (int)vstale[r]);
+                        slots.slot((int)r), slots.slot_owner((int)r), (int)slots.stale((int)r));
     }
     HIPCHK(stg.h2d(dHctl, blk.data(), blk.size()));
     dMt = reinterpret_cast<int *>(dHctl);
-    dVslot = dMt + 4 * R;
+    dPlane = dMt + 4 * R;
     dHoff = reinterpret_cast<long long *>(dHctl + ibytes);
     dS1 = reinterpret_cast<double *>(dHctl + ibytes + lbytes);
     dYnoise = dS1 + Rp;
@@ -1089,7 +1020,7 @@ int Solver::direction_blocks(const std::vector<int> &cg_rows) {
     trace("hessian");
     if (gml_is_i8(prec) || ntiles > 0) {
         std::string err;
-        const int hrc = i8_hessian(p->i8ws, d, dMt + R, dVslot, dFidx, dMtV, ntiles > 0 ? mtV.data() : mt2, dHoffV, htotal, (int)R, capP, formulation, Kh,
+        const int hrc = i8_hessian(p->i8ws, d, dMt + R, dPlane, dFidx, dMtV, ntiles > 0 ? mtV.data() : mt2, dHoffV, htotal, (int)R, capP, formulation, Kh,
                                    kstride, dH, st, &err, ntiles > 0 ? &tl : nullptr);
         if (hrc) return fail(hrc, "%s", err.empty() ? "int8 Hessian: working set above 512 entries" : err.c_str());
     }
@@ -1113,7 +1044,7 @@ int Solver::newton_blocks(const std::vector<int> &chol_rows) {
     const int *rows_k = nullptr;
     RCCHK(ctl(chol_rows, dRows, &rows_k));
     // (a block over every configuration is the Hessian itself: nothing to correct -- and a secant over a finite step would spoil it)
-    const bool secant = use_secant && Kh < d.Kp;
+    const bool secant = Kh < d.Kp;
     if (secant)
         launch_secant(rows_k, (int)chol_rows.size(), dFidx, dMt + 2 * R, capP, X, Qp, dgF, dH, dHoff, dMt, dS1, s2, dYnoise, dFprev, dMprev, dXprev, dGprev,
                       dSec, dSec + 2 * Rp * capP, dNpairs, Rp * (int64_t)capP, kCholLds, st);
@@ -1182,10 +1113,15 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         HIPCHK(A.get(&dFaces, (size_t)Rp));
         HIPCHK(A.get(&dHv, (size_t)(3 * Rp + Rp / 32 + 8)));
     }
-    RCCHK(upload_rows(cg_rows, dRows2));
     std::vector<int> liveflag((size_t)Rp, 0);
-    for (int r : cg_rows) liveflag[r] = 1;
-    HIPCHK(stg.h2d(dLive, liveflag.data(), sizeof(int) * Rp));
+    auto set_live = [&](const std::vector<int> &rows) -> int { // the rows of the kernels that follow: their list, and a flag by row
+        RCCHK(upload_rows(rows, dRows2));
+        std::fill(liveflag.begin(), liveflag.end(), 0);
+        for (int r : rows) liveflag[r] = 1;
+        HIPCHK(stg.h2d(dLive, liveflag.data(), sizeof(int) * Rp));
+        return GML_OK;
+    };
+    RCCHK(set_live(cg_rows));
     // the rows' lists of W (k_cg_tiles, direction_blocks): the per-step vector kernels walk them instead of the 131 k columns
     if (!dNw) HIPCHK(A.get(&dNw, (size_t)Rp));
     HIPCHK(stg.h2d(dNw, nW.data(), sizeof(int) * R));
@@ -1239,7 +1175,7 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         }
     // The GEMM pass costs the same for a tile of 32 rows whatever the number of live ones in it; few rows go entry by entry
     // instead (same integers, gml_hv_sparse.hip: their iterates do not depend on the path)
-    const bool sparse_ok = hv_sparse && p->i8ws != nullptr && formulation != GML_RPLE && hv_lf == 2 && hv_lb == 2 && d.ko <= 2 && maxW <= 65536 &&
+    const bool sparse_ok = p->i8ws != nullptr && formulation != GML_RPLE && hv_lf == 2 && hv_lb == 2 && d.ko <= 2 && maxW <= 65536 &&
                            dT0m != nullptr;
     // Hout = (sum_k h_k x_k x_k^T) theta for the listed rows: an hv pass over slots [0, n) of the u-plane workspace
     auto hv_pass = [&](const std::vector<int> &rows, const double *theta, double *Hout) -> int {
@@ -1252,10 +1188,12 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         for (int64_t a = 0; a < np; ++a) {
             ctl[a] = a < n ? rows[a] : 0;
             ctl[np + a] = a < n ? (int)(p->node0 + rows[a]) : -1;
-            ctl[2 * np + a] = a < n ? vslot[rows[a]] : 0;
+            ctl[2 * np + a] = a < n ? slots.slot(rows[a]) : 0;
         }
         for (int64_t g = 0; g < np / 32; ++g) ctl[3 * np + g] = (int)g;
         HIPCHK(stg.h2d(dHv, ctl.data(), sizeof(int) * ctl.size()));
+        std::string err;
+        int rc;
         if (sparse) {
             const size_t need = i8_hv_sparse_bytes(d, (int)n, maxW);
             if (need > hvs_bytes) {
@@ -1268,45 +1206,29 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
                 dHvsBuf = b;
                 if (o.verbose) fprintf(stderr, "[gml]   scratch of the entry-by-entry products: %.0f MB (%.1f ms)\n", hvs_bytes / 1048576.0, 1e3 * (gml_now_s() - tr));
             }
-            std::string err;
-            const int rc = i8_hv_sparse(p->i8ws, d, (int)n, dHv, dHv + np, dHv + 2 * np, dT0m, dNw, dFV, kTile, maxW, theta, Hout, kchunk, kpart, dHvsBuf,
-                                        st, &err);
-            if (rc) return fail(rc, "%s", err.c_str());
-            ++stats.hessian_passes;
-            ++n_hv_sparse;
-            ++g_hv_sparse_calls;
-            stats.hv_evals += n;
-            return GML_OK;
+            rc = i8_hv_sparse(p->i8ws, d, (int)n, dHv, dHv + np, dHv + 2 * np, dT0m, dNw, dFV, kTile, maxW, theta, Hout, kchunk, kpart, dHvsBuf, st, &err);
+            if (!rc) ++g_hv_sparse_calls;
+        } else {
+            I8Pass a{}; // (slots [0, np); no F)
+            a.theta = theta;
+            a.srow = dHv;
+            a.rowcol = dHv + np;
+            a.vmap = dHv + 2 * np;
+            a.groups = dHv + 3 * np;
+            a.ngroups = (int)(np / 32);
+            a.slot1 = (int)np;
+            a.form = formulation;
+            a.want_grad = true;
+            a.G = Hout;
+            a.hv = hv_lb == 2 ? 2 : 1;
+            a.lf = hv_lf;
+            a.kchunk = kchunk;
+            a.kpart = kpart;
+            rc = i8_pass(&p->i8ws, d, Scap, a, st, nullptr, &err);
         }
-        I8Pass a{};
-        a.theta = theta;
-        a.srow = dHv;
-        a.rowcol = dHv + np;
-        a.vmap = dHv + 2 * np;
-        a.groups = dHv + 3 * np;
-        a.ngroups = (int)(np / 32);
-        a.slot0 = 0;
-        a.slot1 = (int)np;
-        a.form = formulation;
-        a.want_grad = true;
-        a.F = nullptr;
-        a.G = Hout;
-        a.hv = hv_lb == 2 ? 2 : 1;
-        a.lf = hv_lf;
-        a.kchunk = kchunk;
-        a.kpart = kpart;
-        std::string err;
-        const int rc = i8_pass(&p->i8ws, d, Scap, a, st, nullptr, &err);
         if (rc) return fail(rc, "%s", err.c_str());
         ++stats.hessian_passes;
         stats.hv_evals += n;
-        return GML_OK;
-    };
-    auto set_live = [&](const std::vector<int> &rows) -> int {
-        RCCHK(upload_rows(rows, dRows2));
-        std::fill(liveflag.begin(), liveflag.end(), 0);
-        for (int r : rows) liveflag[r] = 1;
-        HIPCHK(stg.h2d(dLive, liveflag.data(), sizeof(int) * Rp));
         return GML_OK;
     };
     std::vector<CgState> cgs((size_t)Rp);
@@ -1379,7 +1301,7 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
 //    to an overshoot allowance): F is convex, so such a trial cannot have increased F.
 // The passes of this iteration use fresh slot ranges: the V planes of the previous ones are no longer needed.
 int Solver::line_search() {
-    slot_next = 0;
+    slots.start_over();
     for (int64_t r = 0; r < R; ++r) {
         need[r] = !done[r];
         alpha[r] = 1.0;
@@ -1425,7 +1347,7 @@ int Solver::line_search() {
             RCCHK(fetch(trial, dTrial, sizeof(TrialOut) * Rp));
             return GML_OK;
         };
-        RCCHK(run_pass(rows, Xt, Gt, full, true, ft, Zt, fnt, nullptr, 0, prec, full ? &back : nullptr, !early));
+        RCCHK(run_pass(rows, Xt, Gt, full, true, at_xt, -1, full ? &back : nullptr, !early));
         if (!early) read_trial();
         std::vector<int> acc;
         for (int r : rows) {
@@ -1449,13 +1371,8 @@ int Solver::line_search() {
                 if (!full) accepted_fwd[r] = 1; // (its V planes still belong to the old iterate)
                 need[r] = 0;
             } else {
-                if (!gml_is_i8(prec)) {
-                    vstale[r] = 1; // the FP64 path's V is indexed by row: every trial overwrites it
-                } else if (full) { // the planes just written belong to the rejected point: back to those of the iterate, if they survive
-                    const int pv = vprev[r];
-                    if (pv >= 0 && owner[pv] == r) vslot[r] = pv;
-                    else vstale[r] = 1;
-                }
+                if (!gml_is_i8(prec)) slots.mark_stale(r); // the FP64 path's V is indexed by row: every trial overwrites it
+                else if (full) slots.reject_trial(r);      // the planes just written belong to the rejected point
                 alpha[r] *= 0.5;
                 if (nreg[r] && alpha[r] < 1.0 / 64) {
                     need[r] = 0;   // cannot improve along this direction: the stall counter ends the row,
@@ -1477,7 +1394,7 @@ int Solver::line_search() {
     std::vector<int> rows;
     for (int64_t r = 0; r < R; ++r)
         if (accepted_fwd[r]) rows.push_back((int)r);
-    if (!rows.empty()) RCCHK(run_pass(rows, X, G, true, false, f, Z, fn, nullptr, 0, prec));
+    if (!rows.empty()) RCCHK(run_pass(rows, X, G, true, false, at_x));
     // rows whose line search failed entirely stay where they are; the stall counter ends them
     return GML_OK;
 }
@@ -1503,14 +1420,9 @@ int Solver::finish(double *out, double *kkt_out, int iterations) {
     // `out` a device pointer (gml_multi_learn's dev_out blocks, device-side callers) -- device to device
     double *dres = D; // [R][P], P <= Qp
     RCCHK(ref_cols());
-    const int32_t *dcols = dColsRef;
-    launch_rows_to_reference(Xt, R, Qp, P, p->node0, d.cconst, dcols, dres, st);
+    launch_rows_to_reference(Xt, R, Qp, P, p->node0, d.cconst, dColsRef, dres, st);
     HIPCHK(hipGetLastError());
-    hipPointerAttribute_t attr;
-    bool dev_out = false;
-    if (hipPointerGetAttributes(&attr, out) == hipSuccess) dev_out = (attr.type == hipMemoryTypeDevice);
-    else (void)hipGetLastError();
-    HIPCHK(hipMemcpyAsync(out, dres, sizeof(double) * R * P, dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out, dres, sizeof(double) * R * P, gml_is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     HIPCHK(stg.sync());
     stats.iterations = iterations;
     stats.max_kkt = maxk;
@@ -1542,12 +1454,8 @@ int Solver::ref_cols() {
 // warm start: X <- the caller's rows (reference layout, host or device pointer)
 int Solver::load_x0() {
     RCCHK(ref_cols());
-    hipPointerAttribute_t attr;
-    bool on_dev = false;
-    if (hipPointerGetAttributes(&attr, x0) == hipSuccess) on_dev = (attr.type == hipMemoryTypeDevice);
-    else (void)hipGetLastError();
     const double *src = x0;
-    if (!on_dev) {
+    if (!gml_is_device_ptr(x0)) {
         double *tmp = nullptr;
         HIPCHK(A.get(&tmp, (size_t)R * P));
         HIPCHK(hipMemcpyAsync(tmp, x0, sizeof(double) * R * P, hipMemcpyHostToDevice, st));
@@ -1572,7 +1480,7 @@ int Solver::iterate(double *out, double *kkt_out) {
     for (int64_t r = 0; r < R; ++r) rows_all[r] = (int)r;
     if (x0) RCCHK(load_x0());
     at_zero = x0 == nullptr;
-    const int rc0 = run_pass(rows_all, X, G, true, false, f, Z, fn, nullptr, 0, prec);
+    const int rc0 = run_pass(rows_all, X, G, true, false, at_x);
     at_zero = false;
     RCCHK(rc0);
     int it = 0;
@@ -1599,14 +1507,10 @@ int Solver::iterate(double *out, double *kkt_out) {
                             dense ? "rows have gone matrix-free (dense optimum)" : "rows have come within the coarse threshold of their optimum", low.size());
                 const double inf = INFINITY;
                 for (int r : low) {
-                    done[r] = 0;
-                    atfloor[r] = 0;
-                    stall[r] = 0;
-                    best[r] = INFINITY;
-                    Fbest[r] = INFINITY;
+                    reopen(r);
                     HIPCHK(stg.h2d(dBest + r, &inf, sizeof(double)));
                 }
-                RCCHK(run_pass(low, X, G, true, false, f, Z, fn, nullptr, 0, prec));
+                RCCHK(run_pass(low, X, G, true, false, at_x));
                 RCCHK(select(it, &nactive));
             }
         }
@@ -1616,12 +1520,7 @@ int Solver::iterate(double *out, double *kkt_out) {
             if (!polishing) break;
             continue;
         }
-        {
-            int maxm = 32;
-            for (int64_t r = 0; r < R; ++r)
-                if (!done[r]) maxm = std::max(maxm, msz[r]);
-            set_kh(nactive, maxm);
-        }
+        set_kh(nactive);
         trace("refresh");
         RCCHK(refresh_stale());
         trace("refreshed");
@@ -1641,6 +1540,23 @@ int Solver::iterate(double *out, double *kkt_out) {
     return finish(out, kkt_out, it);
 }
 
+// one solve of gml_learn_warm at precision prec, from x0 (NULL: zeros) to out / kkt_out; *st: its stats, the wall-clock columns filled
+int solve_once(gml_problem *p, int formulation, gml_opts o, int prec, double lambda, const double *x0, double t_start, double *out, double *kkt_out,
+               gml_stats *st, bool *underflow = nullptr) {
+    o.precision = prec;
+    Solver s(p, formulation, o, lambda);
+    s.x0 = x0;
+    int rc = s.init();
+    if (rc == GML_OK) rc = s.iterate(out, kkt_out);
+    s.stats.t_total = gml_now_s() - t_start;
+    s.stats.t_pack = p->t_ingest[3];
+    // everything that is neither a pass nor the direction phase: selection, trial points, bookkeeping
+    s.stats.t_host = std::max(0.0, s.stats.t_total - s.stats.t_pass - s.stats.t_hess);
+    *st = s.stats;
+    if (underflow) *underflow = s.underflow;
+    return rc;
+}
+
 } // namespace
 
 extern "C" int gml_learn(gml_problem *p, int formulation, double regularizer_c, const gml_opts *opts_in, double *out,
@@ -1658,82 +1574,49 @@ extern "C" int gml_learn_warm(gml_problem *p, int formulation, double regularize
     gml_opts o;
     if (opts_in) o = *opts_in;
     else gml_default_opts(&o);
-    bool asked_auto = false;
-    {
-        // (auto: gml_internal.h -- the 38/31-bit limbs, the FP64-grade ones for tight tolerances and for small problems)
-        const int asked = o.precision;
-        asked_auto = asked == GML_PREC_AUTO;
-        o.precision = gml_resolve_precision(p, asked, o.tol > 0 ? o.tol : 1e-9);
-        if (o.precision < 0) return fail(GML_EINVAL, "unknown precision %d", asked);
-    }
+    // (auto: gml_internal.h -- the 38/31-bit limbs, the FP64-grade ones for tight tolerances and for small problems)
+    const int asked = o.precision;
+    const bool asked_auto = asked == GML_PREC_AUTO;
+    o.precision = gml_resolve_precision(p, asked, o.tol > 0 ? o.tol : 1e-9);
+    if (o.precision < 0) return fail(GML_EINVAL, "unknown precision %d", asked);
     HIPCHK(hipSetDevice(p->device));
     const double t_start = gml_now_s();
-    int rc;
+    const double lambda = gml_lambda(regularizer_c, p->n, p->M);
     bool underflow = false;
-    {
-        Solver s(p, formulation, o, gml_lambda(regularizer_c, p->n, p->M));
-        s.x0 = x0;
-        rc = s.init();
-        if (rc == GML_OK) rc = s.iterate(out, kkt_out);
-        s.stats.t_total = gml_now_s() - t_start;
-        s.stats.t_pack = p->t_ingest[3];
-        // everything that is neither a pass nor the direction phase: selection, trial points, bookkeeping
-        s.stats.t_host = std::max(0.0, s.stats.t_total - s.stats.t_pass - s.stats.t_hess);
-        if (stats_out && (rc == GML_OK || rc == GML_ENOTCONV)) *stats_out = s.stats;
-        underflow = s.underflow;
-    }
+    gml_stats st{};
+    int rc = solve_once(p, formulation, o, o.precision, lambda, x0, t_start, out, kkt_out, &st, &underflow);
+    if (stats_out && (rc == GML_OK || rc == GML_ENOTCONV)) *stats_out = st;
     if (rc == GML_EUNSUPPORTED && underflow && asked_auto) {
         // `auto` is the reference's Float64 solve (:164-181) by other means: a histogram whose optimum lies where exp(-E) spreads over
         // hundreds of units (c = 0 on near-separable data, |theta|_1 in the hundreds) cannot be held by the int8 limbs at an iterate;
         // the reference returns a result there, so `auto` runs the solve again on the FP64-MFMA path.  A caller who named an
         // int8-limb precision keeps the error.
         const std::string first = gml_last_error();
-        gml_opts o64 = o;
-        o64.precision = GML_PREC_F64;
-        Solver s(p, formulation, o64, gml_lambda(regularizer_c, p->n, p->M));
-        s.x0 = x0;
-        rc = s.init();
-        if (rc == GML_OK) rc = s.iterate(out, kkt_out);
+        rc = solve_once(p, formulation, o, GML_PREC_F64, lambda, x0, t_start, out, kkt_out, &st);
         if (rc != GML_OK && rc != GML_ENOTCONV)
             return fail(rc, "%s; the FP64 path, which precision auto falls back to, then failed: %s", first.c_str(), std::string(gml_last_error()).c_str());
-        s.stats.t_total = gml_now_s() - t_start;
-        s.stats.t_pack = p->t_ingest[3];
-        s.stats.t_host = std::max(0.0, s.stats.t_total - s.stats.t_pass - s.stats.t_hess);
-        s.stats.polished = 1; // (finished on the FP64 path)
-        if (stats_out) *stats_out = s.stats;
+        st.polished = 1; // (finished on the FP64 path)
+        if (stats_out) *stats_out = st;
     } else if (rc == GML_ENOTCONV && asked_auto && gml_is_i8(o.precision) && (double)p->K * (double)p->P * (double)p->n <= 268435456.0) {
         // The other way an int8-limb solve can differ from the Float64 solve `auto` stands for: no row leaves the fixed-point range,
         // but the iterates wander along a nearly flat direction on the noise of the limbs and never certify (RPLE at c = 0 on
         // near-separable data: profiles/r6_robust_sweep.txt; the FP64 path converges there in 22 iterations).  On SMALL problems --
         // every kernel launch-bound, the FP64 solve a few milliseconds -- `auto` therefore tries the FP64 path before it reports
         // "not converged", and keeps whichever solve ended with fewer unconverged rows (then the smaller residual).  Host `out` only.
-        hipPointerAttribute_t attr;
-        bool dev_out = false;
-        if (hipPointerGetAttributes(&attr, out) == hipSuccess) dev_out = (attr.type == hipMemoryTypeDevice);
-        else (void)hipGetLastError();
-        if (!dev_out) {
+        if (!gml_is_device_ptr(out)) {
             const std::string first = gml_last_error();
             const size_t R = (size_t)(p->node1 - p->node0);
             std::vector<double> out1(out, out + R * (size_t)p->P), kkt1;
             if (kkt_out) kkt1.assign(kkt_out, kkt_out + R);
-            gml_stats st1{};
-            if (stats_out) st1 = *stats_out;
-            gml_opts o64 = o;
-            o64.precision = GML_PREC_F64;
-            Solver s(p, formulation, o64, gml_lambda(regularizer_c, p->n, p->M));
-            s.x0 = x0;
-            int rc2 = s.init();
-            if (rc2 == GML_OK) rc2 = s.iterate(out, kkt_out);
+            const gml_stats st1 = st; // (the first solve's, as *stats_out holds them)
+            const int rc2 = solve_once(p, formulation, o, GML_PREC_F64, lambda, x0, t_start, out, kkt_out, &st);
             const bool usable = rc2 == GML_OK || rc2 == GML_ENOTCONV;
-            const bool better = usable && (!stats_out || s.stats.not_converged < st1.not_converged ||
-                                           (s.stats.not_converged == st1.not_converged && s.stats.max_kkt < st1.max_kkt));
+            const bool better = usable && (!stats_out || st.not_converged < st1.not_converged ||
+                                           (st.not_converged == st1.not_converged && st.max_kkt < st1.max_kkt));
             if (better) {
                 rc = rc2;
-                s.stats.t_total = gml_now_s() - t_start;
-                s.stats.t_pack = p->t_ingest[3];
-                s.stats.t_host = std::max(0.0, s.stats.t_total - s.stats.t_pass - s.stats.t_hess);
-                s.stats.polished = 1;
-                if (stats_out) *stats_out = s.stats;
+                st.polished = 1;
+                if (stats_out) *stats_out = st;
             } else { // the first solve stands
                 std::copy(out1.begin(), out1.end(), out);
                 if (kkt_out) std::copy(kkt1.begin(), kkt1.end(), kkt_out);

@@ -166,19 +166,6 @@ int make_plan(int64_t n, int order, TermPlan &pl) {
     return GML_OK;
 }
 
-bool is_device_ptr(const void *q, int *dev) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, q) == hipSuccess) {
-        if (attr.type == hipMemoryTypeDevice) {
-            if (dev) *dev = attr.device;
-            return true;
-        }
-        return false;
-    }
-    (void)hipGetLastError();
-    return false;
-}
-
 } // namespace
 
 extern "C" int64_t gml_terms_count(int64_t n, int order, int symmetrize) {
@@ -221,7 +208,7 @@ extern "C" int gml_terms_assemble(const double *rows, int64_t ld, int64_t n, int
     if (ld < P) return fail(GML_EINVAL, "terms: leading dimension %lld < %lld parameters per node", (long long)ld, (long long)P);
     const int64_t T = symmetrize ? pl.off[order + 1] : pl.uoff[order + 1];
     int rdev = device, odev = device;
-    const bool rows_dev = is_device_ptr(rows, &rdev), out_dev = is_device_ptr(out, &odev);
+    const bool rows_dev = gml_is_device_ptr(rows, &rdev), out_dev = gml_is_device_ptr(out, &odev);
     if (rows_dev) device = rdev;
     else if (out_dev) device = odev;
     HIPCHK(hipSetDevice(device));
@@ -368,7 +355,7 @@ int gml_pair_symmetrize_dev(const double *drows, int64_t ld, int64_t n, double *
 extern "C" int gml_matrix_symmetrize(const double *rows, int64_t ld, int64_t n, int device, double *out) {
     if (!rows || !out || n < 1 || ld < n) return fail(GML_EINVAL, "gml_matrix_symmetrize: bad argument");
     int rdev = device, odev = device;
-    const bool rows_dev = is_device_ptr(rows, &rdev), out_dev = is_device_ptr(out, &odev);
+    const bool rows_dev = gml_is_device_ptr(rows, &rdev), out_dev = gml_is_device_ptr(out, &odev);
     if (rows_dev) device = rdev;
     else if (out_dev) device = odev;
     HIPCHK(hipSetDevice(device));
@@ -424,7 +411,7 @@ extern "C" int gml_learn_matrix(gml_problem *p, int formulation, double regulari
     if (rc == GML_OK || rc == GML_ENOTCONV) {
         const double t0 = gml_now_s();
         int odev = 0;
-        const bool out_dev = is_device_ptr(out, &odev);
+        const bool out_dev = gml_is_device_ptr(out, &odev);
         hipError_t e = hipSuccess;
         double *dst = out;
         if (!out_dev) {
@@ -470,7 +457,7 @@ extern "C" int gml_learn_terms(gml_problem *p, int formulation, double regulariz
     if (rc == GML_OK || rc == GML_ENOTCONV) {
         const double t0 = gml_now_s();
         int odev = 0;
-        const bool out_dev = is_device_ptr(terms, &odev);
+        const bool out_dev = gml_is_device_ptr(terms, &odev);
         hipError_t e = hipSuccess;
         double *dst = terms;
         if (!out_dev) {
