@@ -87,6 +87,8 @@ def lib():
     L.gml_problem_create_mcmc_chains.argtypes = [p, i64, i64, i64, i32, i32, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_create_mcmc_terms_chains.argtypes = [p, i32, p, i64, i64, i64, i64, i32, i32, C.c_uint64, i32, i32, i64, i64, i32,
                                                        C.POINTER(p)]
+    L.gml_problem_create_mcmc_terms_tempered.argtypes = [p, i32, p, i64, i64, i64, i64, i32, i32, p, i32, i32, C.c_uint64, i32, i32, i64,
+                                                         i64, i32, p, C.POINTER(p)]
     L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -268,7 +270,7 @@ class Problem:
 
     def __init__(self, samples=None, *, counts=None, spins=None, packed=None, model=None, terms=None, n=None, num_samples=None,
                  seed=0, mcmc_sweeps=None, order=2, node_range=None, device=0, ingest="host", histogram=False, burn_in=None, thin=None,
-                 samples_per_chain=None, mcmc_thin=None, mcmc_samples_per_chain=None):
+                 samples_per_chain=None, mcmc_thin=None, mcmc_samples_per_chain=None, mcmc_betas=None, mcmc_swap_every=1):
         """histogram=True (sampled handles, n <= 64): the handle holds the distinct configurations with their counts
         (gml_problem_create_sampled_hist: sorted and run-length encoded on the device), not one row per draw.
         burn_in / thin / samples_per_chain (with model=): num_samples // samples_per_chain Glauber chains of a pairwise model on the
@@ -276,15 +278,21 @@ class Problem:
         mcmc_thin / mcmc_samples_per_chain (with terms=; either one, even 1, selects it): num_samples // mcmc_samples_per_chain
         Glauber chains of the term list with exact integer fields, burnt in for mcmc_sweeps sweeps (required) and then recorded every
         mcmc_thin sweeps (gml_problem_create_mcmc_terms_chains; defaults thin 10, samples per chain 1).  mcmc_sweeps alone: one
-        sample per chain (gml_problem_create_mcmc_terms)."""
+        sample per chain (gml_problem_create_mcmc_terms).
+        mcmc_betas (with terms=; needs mcmc_sweeps): replica exchange -- num_samples // mcmc_samples_per_chain ladders of
+        len(mcmc_betas) rungs at these inverse temperatures (non-increasing, the first positive; 1, 2, 4 .. 64 of them), swaps
+        between neighbouring rungs every mcmc_swap_every sweeps, rung 0 recorded as above (gml_problem_create_mcmc_terms_tempered).
+        The handle's swap_counts is then the (2, R - 1) int64 array of swap attempts and accepts per pair (None otherwise)."""
         L = lib()
         h = C.c_void_p()
-        term_chains = mcmc_thin is not None or mcmc_samples_per_chain is not None
+        term_chains = mcmc_thin is not None or mcmc_samples_per_chain is not None or mcmc_betas is not None
+        self.swap_counts = None
         if term_chains:
+            tc_names = "mcmc_thin / mcmc_samples_per_chain" + (" / mcmc_betas" if mcmc_betas is not None else "")
             if terms is None or model is not None or samples is not None or spins is not None or packed is not None:
-                raise GMLError(GML_EINVAL, "mcmc_thin / mcmc_samples_per_chain apply to a term list given as terms=")
+                raise GMLError(GML_EINVAL, f"{tc_names} apply to a term list given as terms=")
             if not mcmc_sweeps:
-                raise GMLError(GML_EINVAL, "mcmc_thin / mcmc_samples_per_chain need mcmc_sweeps (the burn-in)")
+                raise GMLError(GML_EINVAL, f"{tc_names} need mcmc_sweeps (the burn-in)")
             tc_spc = 1 if mcmc_samples_per_chain is None else int(mcmc_samples_per_chain)
             if tc_spc < 1 or num_samples is None or int(num_samples) < 1 or int(num_samples) % tc_spc != 0:
                 raise GMLError(GML_EINVAL, f"num_samples must be a positive multiple of mcmc_samples_per_chain ({tc_spc})")
@@ -358,7 +366,16 @@ class Problem:
                     keys[t, :len(k)] = np.asarray(k, dtype=np.int64) - 1
                     wts[t] = v
             n0, n1 = _node_range(node_range, n)
-            if term_chains:  # thinned chains with exact integer fields (any order, any sparsity)
+            if mcmc_betas is not None:  # replica exchange on the same chains: ladders of len(betas) rungs, rung 0 recorded
+                betas = np.ascontiguousarray(mcmc_betas, dtype=np.float64).ravel()
+                swaps = np.zeros((2, max(len(betas) - 1, 0)), dtype=np.int64)
+                check(L.gml_problem_create_mcmc_terms_tempered(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples) // tc_spc,
+                                                               tc_spc, int(mcmc_sweeps), int(10 if mcmc_thin is None else mcmc_thin),
+                                                               _ptr(betas), len(betas), int(mcmc_swap_every), int(seed),
+                                                               int(bool(histogram)), int(order), n0, n1, int(device), _ptr(swaps),
+                                                               C.byref(h)))
+                self.swap_counts = swaps
+            elif term_chains:  # thinned chains with exact integer fields (any order, any sparsity)
                 check(L.gml_problem_create_mcmc_terms_chains(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples) // tc_spc,
                                                              tc_spc, int(mcmc_sweeps), int(10 if mcmc_thin is None else mcmc_thin),
                                                              int(seed), int(bool(histogram)), int(order), n0, n1, int(device),

@@ -224,6 +224,12 @@ extern int g_term_chains_tile;
 int term_chains_tile(int64_t n, int64_t chains);
 void launch_term_chains(const TermChainSpin *dspin, const unsigned *drec, int64_t n, int64_t chains, int burn_in, int thin, int spc,
                         unsigned long long seed, int8_t *dout, int64_t ld, hipStream_t st);
+// Replica-exchange chains of the same records (gml_tempered_chains.hip): `ladders` ladders of `replicas` rungs (a power of two up
+// to 64) at dbetas[replicas], one lane per rung on the tile term_chains_tile(n, ladders replicas); rung 0 recorded into out [n][ld];
+// dswap_counts [2][replicas - 1] (attempts, accepts; zeroed by the caller) is added to.
+void launch_tempered_chains(const TermChainSpin *dspin, const unsigned *drec, int64_t n, int64_t ladders, int replicas,
+                            const double *dbetas, int swap_every, int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout,
+                            int64_t ld, unsigned long long *dswap_counts, hipStream_t st);
 
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].

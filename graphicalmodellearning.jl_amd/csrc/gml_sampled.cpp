@@ -452,6 +452,63 @@ extern "C" int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key
     return s.finish(true, ld, histogram != 0, out); // the recorded states, spin-major
 }
 
+// the ladder of gml_problem_create_mcmc_terms_tempered: a power of two of rungs up to 64, finite betas that do not increase, the first positive
+static int check_ladder(const double *betas, int replicas, int swap_every, int64_t ladders) {
+    if (!betas) return fail(GML_EINVAL, "betas is NULL");
+    if (replicas < 1 || replicas > 64 || (replicas & (replicas - 1)) != 0)
+        return fail(GML_EINVAL, "replicas must be one of 1, 2, 4, 8, 16, 32, 64 (given %d)", replicas);
+    for (int r = 0; r < replicas; ++r) {
+        if (!std::isfinite(betas[r]) || betas[r] < 0.0) return fail(GML_EINVAL, "betas[%d] is negative or not finite", r);
+        if (r > 0 && betas[r] > betas[r - 1]) return fail(GML_EINVAL, "betas must not increase (betas[%d] > betas[%d])", r, r - 1);
+    }
+    if (!(betas[0] > 0.0)) return fail(GML_EINVAL, "betas[0] must be positive");
+    if (swap_every < 1) return fail(GML_EINVAL, "swap_every must be at least 1");
+    if (ladders > ((int64_t)1 << 40) / replicas) return fail(GML_EINVAL, "ladders * replicas is too large");
+    return GML_OK;
+}
+
+// gml_problem_create_mcmc_terms_tempered: replica-exchange chains of any term list, rung 0 recorded (gml_tempered_chains.hip).
+extern "C" int gml_problem_create_mcmc_terms_tempered(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                                      int64_t ladders, int64_t samples_per_chain, int burn_in, int thin,
+                                                      const double *betas, int replicas, int swap_every, uint64_t seed, int histogram,
+                                                      int order, int64_t node0, int64_t node1, int device, int64_t *swap_counts,
+                                                      gml_problem **out) {
+    if (int rc = check_out(out)) return rc;
+    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
+    if (int rc = check_chain_args(n, ladders, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
+    if (int rc = check_ladder(betas, replicas, swap_every, ladders)) return rc;
+    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
+    const int64_t M = ladders * samples_per_chain;
+    if (n > kMcmcChainsMaxN || term_chains_tile(n, ladders * replicas) == 0)
+        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
+                    (long long)n);
+    if (histogram)
+        if (int rc = check_hist_limits(n, M)) return rc;
+    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
+    std::vector<TermChainSpin> spin;
+    std::vector<unsigned> rec;
+    build_spin_records(build_incidences(keys, key_stride, weights, nterms, n), spin, rec);
+    if (int rc = gml_check_device(device)) return rc;
+    const int64_t ld = round_up(M, 256);
+    const size_t ncounts = 2 * (size_t)(replicas - 1);
+    std::vector<unsigned long long> counts(std::max<size_t>(ncounts, 1), 0ull);
+    const std::vector<double> ladder(betas, betas + replicas);
+    SamplerStaging s;
+    if (int rc = s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true)) return rc;
+    const TermChainSpin *dspin = s.upload(spin);
+    const unsigned *drec = s.upload(rec);
+    const double *dbetas = s.upload(ladder);
+    unsigned long long *dcounts = s.upload(counts); // zeros
+    if (s.rc) return s.rc;
+    launch_tempered_chains(dspin, drec, n, ladders, replicas, dbetas, swap_every, burn_in, thin, (int)samples_per_chain,
+                           (unsigned long long)seed, s.out, ld, dcounts, s.st);
+    s.ok(hipMemcpyAsync(counts.data(), dcounts, sizeof(unsigned long long) * counts.size(), hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    if (int rc = s.finish(true, ld, histogram != 0, out)) return rc; // the recorded states of rung 0, spin-major
+    if (swap_counts)
+        for (size_t k = 0; k < ncounts; ++k) swap_counts[k] = (int64_t)counts[k];
+    return GML_OK;
+}
+
 extern "C" int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,
                                              int64_t n, int64_t N, uint64_t seed, int sweeps, int order, int64_t node0,
                                              int64_t node1, int device, gml_problem **out) {

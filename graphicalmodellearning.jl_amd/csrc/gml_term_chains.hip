@@ -15,55 +15,9 @@
 #include "../../include/gml.h"
 #include "gml_dev.h"
 #include "gml_chain.h"
+#include "gml_term_field.h"
 
 namespace gml {
-
-// q_e if the product of the other spins of the record r is -1 (an odd number of set bits), else 0.  my: the lane's chain column.
-template <int K>
-__device__ __forceinline__ long long odd_q(const unsigned *r, const unsigned *my, int T) {
-    const unsigned w0 = r[0];
-    const long long q = (long long)(((unsigned long long)r[1] << 32) | w0) >> 24;
-    unsigned j = w0 & 0xFFFFFFu;
-    unsigned p = my[(j >> 5) * T] >> (j & 31);
-#pragma unroll
-    for (int m = 2; m <= K; ++m) {
-        j = r[m];
-        p ^= my[(j >> 5) * T] >> (j & 31);
-    }
-    const unsigned m = (unsigned)((int)(p << 31) >> 31); // 0 or ~0
-    return q & (long long)(((unsigned long long)m << 32) | m);
-}
-
-// G records from word e on: one wait for their scalar loads, G independent LDS reads (per other spin) in flight
-template <int K, int G>
-__device__ __forceinline__ long long odd_step(const unsigned *__restrict__ rec, long long e, const unsigned *my, int T) {
-    long long acc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) acc[g] = odd_q<K>(rec + e + g * (K + 1), my, T);
-#pragma unroll
-    for (int w = 1; w < G; w <<= 1)
-#pragma unroll
-        for (int g = 0; g + w < G; g += 2 * w) acc[g] += acc[g + w];
-    return acc[0];
-}
-
-// the odd part of the records with K other spins in the words [beg, end).  Every step waits for its scalar loads (one wave per SIMD
-// at 65 536 chains: nothing else hides them), so a list is walked in the largest steps that fit -- up to 32 words of records
-// (16 pairs, 8 triples, 4 records beyond) -- and a short one still takes one wait per 4 records, not one per record.
-template <int K>
-__device__ __forceinline__ long long odd_sum(const unsigned *__restrict__ rec, long long beg, long long end, const unsigned *my, int T) {
-    constexpr int R = K + 1, G = K == 1 ? 16 : K == 2 ? 8 : 4;
-    long long s = 0, e = beg;
-    for (; e + G * R <= end; e += G * R) s += odd_step<K, G>(rec, e, my, T);
-    if constexpr (G > 8) {
-        if (e + 8 * R <= end) s += odd_step<K, 8>(rec, e, my, T), e += 8 * R;
-    }
-    if constexpr (G > 4) {
-        if (e + 4 * R <= end) s += odd_step<K, 4>(rec, e, my, T), e += 4 * R;
-    }
-    for (; e < end; e += R) s += odd_q<K>(rec + e, my, T);
-    return s;
-}
 
 __global__ __launch_bounds__(256) void k_term_chains(const TermChainSpin *__restrict__ spin, const unsigned *__restrict__ rec, int n,
                                                      int64_t chains, int burn_in, int thin, int spc, unsigned long long seed,
@@ -78,14 +32,7 @@ __global__ __launch_bounds__(256) void k_term_chains(const TermChainSpin *__rest
         const unsigned long long z0 = chain_z0(seed, c, n, sw);
         for (int i = 0; i < n; ++i) {
             const TermChainSpin &r = spin[i];
-            long long odd = odd_sum<1>(rec, r.off[0], r.off[1], my, T);
-            odd += odd_sum<2>(rec, r.off[1], r.off[2], my, T);
-            odd += odd_sum<3>(rec, r.off[2], r.off[3], my, T);
-            odd += odd_sum<4>(rec, r.off[3], r.off[4], my, T);
-            odd += odd_sum<5>(rec, r.off[4], r.off[5], my, T);
-            odd += odd_sum<6>(rec, r.off[5], r.off[6], my, T);
-            odd += odd_sum<7>(rec, r.off[6], r.off[7], my, T);
-            const double f = (double)(r.Q - 2 * odd);
+            const double f = term_field(r, rec, my, T);
             const unsigned neg = chain_heat_bath(z0, (unsigned long long)i, r.a + r.sig * f);
             unsigned *wp = my + (i >> 5) * T;
             *wp = (*wp & ~(1u << (i & 31))) | (neg << (i & 31));

@@ -2,8 +2,8 @@
 the on-device exact sampler (gml_problem_create_sampled / _sampled_terms).  Any interaction order; every
 connected component of the term hypergraph must have at most 22 spins (the reference enumerates all 2^n
 states of the whole model, which limits it to n ~ 25).  Beyond that, Markov chains on the device: Glauber (one sample per
-chain), GlauberChains (long thinned chains of dense pairwise models) and GlauberTermChains (long thinned chains of any term
-list)."""
+chain), GlauberChains (long thinned chains of dense pairwise models), GlauberTermChains (long thinned chains of any term
+list) and TemperedTermChains (replica exchange on those, for models with more than one deep well)."""
 import numpy as np
 
 from . import _lib
@@ -48,6 +48,29 @@ class GlauberTermChains(GMSampler):
         self.burn_in, self.thin, self.samples_per_chain = int(burn_in), int(thin), int(samples_per_chain)
 
 
+class TemperedTermChains(GMSampler):
+    """Not in the reference: replica exchange (parallel tempering) on the chains of GlauberTermChains
+    (gml_problem_create_mcmc_terms_tempered), for models with more than one deep well -- a ferromagnet below its transition, a glass
+    at low temperature, a sharply learned model -- where a single-temperature chain stays in the well it started in.
+    N // samples_per_chain ladders of `replicas` chains (1, 2, 4 .. 64) at the inverse temperatures `betas` (non-increasing, the first
+    positive; default: geometric from 1 down to beta_min); neighbouring rungs try to exchange their states every `swap_every`
+    sweeps; the rung at betas[0] is recorded.  After sample(), swap_rates holds accepts / attempts per neighbouring pair (of the last
+    replicate): a rate near 0 asks for more rungs or a larger beta_min between those two."""
+
+    def __init__(self, burn_in=200, thin=10, samples_per_chain=1, replicas=8, beta_min=0.1, betas=None, swap_every=1):
+        self.burn_in, self.thin, self.samples_per_chain = int(burn_in), int(thin), int(samples_per_chain)
+        self.swap_every = int(swap_every)
+        if betas is not None:
+            self.betas = [float(b) for b in betas]
+        else:
+            R = int(replicas)
+            if R < 1:
+                raise ValueError(f"replicas must be at least 1 (given {replicas})")
+            self.betas = [float(beta_min) ** (r / (R - 1)) for r in range(R)] if R > 1 else [1.0]
+        self.replicas = len(self.betas)
+        self.swap_rates = None
+
+
 def _problem_args(model):
     """Keyword arguments of _lib.Problem for a model: matrix (order <= 2, :98-99) or term list (:100-101)."""
     if isinstance(model, FactorGraph):
@@ -88,6 +111,11 @@ def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, devic
         args = _term_list_args(model, args)
         _check_whole_chains(number_sample, sampler)
         args.update(mcmc_sweeps=sampler.burn_in, mcmc_thin=sampler.thin, mcmc_samples_per_chain=sampler.samples_per_chain)
+    elif isinstance(sampler, TemperedTermChains):
+        args = _term_list_args(model, args)
+        _check_whole_chains(number_sample, sampler)
+        args.update(mcmc_sweeps=sampler.burn_in, mcmc_thin=sampler.thin, mcmc_samples_per_chain=sampler.samples_per_chain,
+                    mcmc_betas=sampler.betas, mcmc_swap_every=sampler.swap_every)
     elif isinstance(sampler, Glauber):
         args = _term_list_args(model, args)
         args["mcmc_sweeps"] = sampler.sweeps
@@ -100,12 +128,15 @@ def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, devic
             # countmap (sampling.jl:52) on the device: the draws are sorted and run-length encoded there; only the distinct
             # configurations and their counts come back
             with _lib.Problem(histogram=True, **kw) as p:
-                states, counts = p.spins(), p.counts()
+                states, counts, swaps = p.spins(), p.counts(), p.swap_counts
             order = np.lexsort(states.T[::-1])  # rows in the order np.unique would give them
             states, counts = states[order], counts[order]
         else:
             with _lib.Problem(**kw) as p:
-                spins = p.spins()
+                spins, swaps = p.spins(), p.swap_counts
             states, counts = np.unique(spins, axis=0, return_counts=True)
+        if isinstance(sampler, TemperedTermChains):
+            # (a pair without a swap round -- swap_every above the sweep count -- has no rate: NaN)
+            sampler.swap_rates = np.divide(swaps[1], swaps[0], out=np.full(swaps.shape[1], np.nan), where=swaps[0] > 0)
         out.append(np.concatenate([np.rint(counts)[:, None].astype(np.int64), states.astype(np.int64)], axis=1))
     return out[0] if replicates is None else out

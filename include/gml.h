@@ -282,6 +282,39 @@ int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key_stride, co
                                          int order, int64_t node0, int64_t node1, int device, gml_problem **out);
 
 /*
+ * gml_problem_create_mcmc_terms_tempered -- replica-exchange (parallel tempering) chains of ANY term list: the sampler for models with
+ * more than one deep well (a ferromagnet below its transition, a glass at low temperature, a sharply learned model), where a
+ * single-temperature chain stays in the well it fell into.  Term list, incidences, a_i, sigma_i, q_e and the exact int64 field h_i
+ * are those of gml_problem_create_mcmc_terms_chains; E(s) = - sum_t w_t prod_{i in t} s_i.
+ * Ladder l (of `ladders`) holds R = replicas states at the inverse temperatures betas[0] >= betas[1] >= ... >= betas[R-1] >= 0,
+ * betas[0] > 0; rung r of ladder l has the chain index c = l R + r and targets P ~ exp(-beta_r E).  Only rung 0 is recorded.
+ *   start:    every rung of ladder l starts from the start state of chain l R (spin i is +1 iff u01(seed, 0xFFFFFFFF, l R n + i) <
+ *             0.5) with the tracked energy E_r = 0: energies are relative to the ladder's common start, which is all a swap needs.
+ *   sweep sw (0-based, burn-in included): rung r updates the spins 0 .. n-1 in order,
+ *             pup = 1.0 / (1.0 + exp(-2.0 * (beta_r * h_i))),  s_i = +1 iff u01(seed, sw, c n + i) < pup,
+ *             E_r <- E_r - (s_new - s_old) * h_i in FP64 (the factor is 0 or +-2: the product is exact, one rounding per flip).
+ *             The random stream belongs to the rung, not to the state that travels.
+ *   swap:     after done = sw + 1 completed sweeps with done % swap_every == 0, round m = done / swap_every: for every r with
+ *             r = m - 1 (mod 2) and r + 1 < R,  d = (beta_r - beta_{r+1}) * (E_r - E_{r+1});  the two rungs exchange their states
+ *             and tracked energies iff u01(seed, 2^32 + sw, l R + r) < exp(fmin(d, 0.0)).  (Stream 2^32 + sw is no sweep's stream --
+ *             a run has at most 2^31 - 1 sweeps -- and not the start's.)
+ * Recorded, after the swap: rung 0 of ladder l after burn_in + t thin completed sweeps (t = 0 .. samples_per_chain-1) is row
+ * t ladders + l, count 1, M = ladders samples_per_chain.  histogram as in gml_problem_create_mcmc_terms_chains.
+ * swap_counts (host, [2][R-1], may be NULL): attempts[r] and accepts[r] of the pair (r, r+1), summed over all ladders and all rounds,
+ * burn-in included; exact integers.
+ * The samples and the counts depend only on (model, seed, betas, swap_every, burn_in, thin, samples_per_chain, ladder index): not on
+ * the order of the terms with other spins, the kernel's tile, the grid or the device.  With replicas = 1 and betas[0] == 1.0 the
+ * samples are those of gml_problem_create_mcmc_terms_chains, bit for bit.
+ * GML_EINVAL (checked before any HIP call): everything gml_problem_create_mcmc_terms_chains rejects (ladders in the place of chains);
+ * betas NULL; replicas not one of 1, 2, 4, 8, 16, 32, 64; a non-finite, negative or increasing beta; betas[0] <= 0; swap_every < 1;
+ * ladders replicas > 2^40.  GML_EUNSUPPORTED: as gml_problem_create_mcmc_terms_chains.
+ */
+int gml_problem_create_mcmc_terms_tempered(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                           int64_t ladders, int64_t samples_per_chain, int burn_in, int thin, const double *betas,
+                                           int replicas, int swap_every, uint64_t seed, int histogram, int order, int64_t node0,
+                                           int64_t node1, int device, int64_t *swap_counts, gml_problem **out);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
