@@ -29,7 +29,8 @@
 // Files: gml_i8_pack.hip (bit images, quantisation of Theta), gml_i8_fwd.hip (forward kernel of the 38/31-bit pass "i8x" and of the
 // Hessian-vector forms), gml_i8_bwd.hip (backward kernel, finalisation), gml_i8_hess.hip (working-set Hessians),
 // gml_kernels_i8w.hip (forward kernel and finalisation of the FP64-grade 54/47-bit pass "i8w"), gml_i8_pass.hip (workspace and
-// the orchestration of a pass).  This header: what they share.  Internal, device side.
+// the orchestration of a pass).  This header: what they share; gml_i8_fwd.h: what the two forward kernels share beyond it;
+// gml_i8_map.h: their block mapping (plain C++, tested on the host).  Internal, device side.
 #pragma once
 #include "../../include/gml.h"
 #include "gml_dev.h"

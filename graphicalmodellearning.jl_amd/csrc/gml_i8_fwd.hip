@@ -1,8 +1,7 @@
 // Int8-limb path, part 2: the forward kernel of the 38/31-bit pass "i8x" and of the Hessian-vector forms (overview: gml_i8.h).
-#include "gml_i8.h"
+#include "gml_i8_fwd.h"
 #include <algorithm>
 #include <string>
-#include <type_traits>
 
 namespace gml {
 
@@ -11,19 +10,14 @@ namespace gml {
 // polynomial for expm1 of the reduced argument, table of 2^(j/64), exponent added as an integer, and the final rounding
 // to an integer through the 1.5 * 2^52 trick, after adding a dither in [-1/2, 1/2) that is a fixed function of
 // (node, sample): the rounding is then "stochastic" -- still deterministic and within one unit, but uncorrelated across
-// samples.  Round-to-nearest is coherent whenever a sparse theta row leaves only a few distinct energies (thousands of
-// samples share each rounding error), which made the realised error of f and grad approach the K * tau / 2 worst case
-// instead of ~ sqrt(K) * tau.
+// samples (why, and the hash: gml_i8_fwd.h).
 // The epilogue is bound by the number of vector instructions, so this is written for few of them:
 //   * sb (bit 0: s = +1) flips the sign of Ea going in (x = -s E) and of the result coming out by adding sb << 31 to
 //     the high word -- round-half-even is symmetric, so rounding -y gives minus the rounding of y;
 //   * everything from the weight on is scaled by 2^32 (wk32 = 2^32 w / tau; exact): the dither is then the hash itself,
 //     converted int -> double, and the integer is read off below 1.5 * 2^84;
-//   * the table holds 2^(j/64) with j << 14 taken off the high word: the exponent of 2^(n >> 6), n = 64 q + j, goes on
-//     as n << 14 (= (q << 20) + (j << 14)) in one shift-add.
+//   * the table holds 2^(j/64) with j << 14 taken off the high word (fill_tables()): the exponent goes on in one shift-add.
 __device__ __forceinline__ int vq_exp(double Ea, unsigned sb, double wk32, unsigned dh, const double *__restrict__ tabb) {
-    const double MAGIC = 6755399441055744.0;                  // 1.5 * 2^52
-    const double MAGIC32 = 6755399441055744.0 * 4294967296.0; // 1.5 * 2^84: rounds to multiples of 2^32
     const int flip = (int)(sb << 31);
     const double x = __hiloint2double(__double2hiint(Ea) + flip, __double2loint(Ea)); // -s E
     const double tm = fma(x, 92.33248261689366, MAGIC);                               // 64/ln2
@@ -79,13 +73,10 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
     // column compaction of objective passes (gml_i8_pack.hip: k_col_union): steps of each tile's compact image (-1: all columns), the
     // images, bytes per tile, and the steps between two tiles' Tq images (= Qfp / 64 whatever is swept)
     const int *__restrict__ cnk, const int8_t *__restrict__ Xc, int64_t xc_tile, int nk_tq) {
-    constexpr int WM = 2;                 // 32-sample MFMA tiles per wave
     constexpr bool HV = FORM >= 3;
     constexpr int BR = 32 * LF;           // rows of the Tq image
     constexpr int NPIECE = 2 + BR / 16, NP = (NPIECE + 3) / 4;
-    // Ring stages hold DS consecutive 64-column steps: one barrier per DS steps (the waves of a workgroup then re-align
-    // half as often, and the LDS reads of a stage's second step issue under the MFMAs of its first).
-    constexpr int DS = 2;
+    constexpr int DS = 2; // 64-column steps per ring stage (gemm_stage2)
     constexpr int STEP = NPIECE * 1024, STAGE = DS * STEP, NS = 3;
     constexpr int RING = NS * STAGE;
     extern __shared__ __attribute__((aligned(16))) int8_t lds[]; // ring, then the exp (and log) tables
@@ -93,53 +84,17 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int lr = lane & 31, h = lane >> 5;
-    if (tid < 64) {
-        const double v = exp2((double)tid / 64.0);
-        // exp forms: the table of vq_exp(), j << 14 taken off the high word
-        etab[tid] = FORM == 0 ? __hiloint2double(__double2hiint(v) - (tid << 14), __double2loint(v)) : v;
-    }
-    if (FORM == 2 && tid < 64) { // log table for RPLE: c_j = 1 + (j + 1/2)/64 -> 1/c_j, log c_j
-        const double cj = 1.0 + ((double)tid + 0.5) / 64.0;
-        etab[64 + tid] = 1.0 / cj;
-        etab[128 + tid] = log(cj);
-    }
-    __syncthreads(); // tables visible to every wave (the ring uses raw s_barrier without an LDS wait)
+    fill_tables<FORM>(etab, tid);
 
-    // XCD-aware L2 blocking.  Blocks b and b+8 share an XCD (round-robin dispatch); XCD x owns the
-    // sample tiles st = 8*i + x.  Within an XCD: groups of TG node tiles (outer), sample tiles
-    // (middle), the TG node tiles (inner): Tq of the group stays resident in the XCD's L2 over the
-    // sweep and each bit piece is fetched once per node-tile group.  The last group holds ngroups % TG tiles; the grid
-    // has no idle workgroups beyond the sample tiles that pad ntiles_k to a multiple of 8 (a node-sharded rank runs few
-    // node tiles: half of its launch would otherwise be workgroups that start only to exit).
-    constexpr int TG = 8;
-    const int b = blockIdx.x, xcd = b & 7, bi = b >> 3;
-    const int ntk8 = (ntiles_k + 7) >> 3;
-    const int nfull = ngroups / TG, per_full = ntk8 * TG;
-    int st, gi;
-    if (bi < nfull * per_full) {
-        const int rem = bi % per_full;
-        st = (rem / TG) * 8 + xcd;
-        gi = (bi / per_full) * TG + rem % TG;
-    } else {
-        const int lastn = ngroups - nfull * TG, rem = bi - nfull * per_full;
-        st = (rem / lastn) * 8 + xcd;
-        gi = nfull * TG + rem % lastn;
-    }
-    if (st >= ntiles_k) return;
+    const FwdBlock blk = fwd_block(blockIdx.x, ntiles_k, ngroups);
+    if (!blk.live) return;
+    int st = blk.st;
     if (chunk_tiles != part_tiles) st = (st / part_tiles) * chunk_tiles + st % part_tiles;
     const int64_t k0 = (int64_t)st * 256;
     if (k0 >= Kp) return;
-    const int mytile = groups[gi];
-    // the columns this tile sweeps: all of them, or its compact list (the image then has the tile's own step count in its strides)
-    int nk = nk_all;
-    const int8_t *xbase = reinterpret_cast<const int8_t *>(Xb);
-    if (cnk) {
-        const int ck = cnk[mytile];
-        if (ck >= 0) {
-            nk = ck;
-            xbase = Xc + (int64_t)mytile * xc_tile;
-        }
-    }
+    const FwdTile tile = fwd_tile(groups, blk.gi, nk_all, Xb, cnk, Xc, xc_tile);
+    const int mytile = tile.mytile, nk = tile.nk;
+    const int8_t *const xbase = tile.xbase;
 
     // per-lane source of each 1-KB piece this wave loads, and its advance per 64-column step
     const int8_t *src[NP];
@@ -181,15 +136,11 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
     const int r = mytile * 32 + lr;
     const int rc = rowcol[r];
     const bool active = rc >= 0;
-    // the node's sign bits for this wave's 64 samples (word i <-> MFMA tile i), shifted so that bit 8g + j is this
-    // lane's sample 8g + 4h + j of the tile
+    const int64_t kw = k0 + wave * 64; // first sample of this wave
     unsigned sgn[WM];
 #pragma unroll
-    for (int i = 0; i < WM; ++i) sgn[i] = active ? (Sb[(int64_t)rc * (Kp >> 5) + ((k0 + wave * 64) >> 5) + i] >> (4 * h)) : 0u;
-    // samples at or beyond Kreal are padding (they carry no weight): this lane's element (i, g, j) sits 32 i + 8 g + j
-    // samples after its first one, k0 + 64 wave + 4 h
-    const int64_t left = Kreal - (k0 + wave * 64 + 4 * h);
-    const int nreal = left > 64 ? 64 : (left < 0 ? 0 : (int)left);
+    for (int i = 0; i < WM; ++i) sgn[i] = sign_word(Sb, rc, active, Kp, kw, h, i);
+    const int nreal = lane_real(Kreal, kw, h);
     const double sg = active ? sigma[r] : 0.0;
     const double q0 = active ? (double)qconst[r] : 0.0;
     const double it = active ? invtau[r] : 0.0;
@@ -201,49 +152,15 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
     for (int s = 0; s < NS - 1; ++s)
         if (s < nst) issue(s);
     auto gemm_stage = [&](int ks, auto first) {
-        constexpr bool FIRST = decltype(first)::value;
         ring_wait_ahead<DS * NP>(nst - 1 - ks > NS - 2 ? NS - 2 : nst - 1 - ks); // NS - 2 later stages may still be in flight
         if (ks + NS - 1 < nst) issue(ks + NS - 1);
-#pragma unroll
-        for (int sub = 0; sub < DS; ++sub) {
-            if (sub > 0 && DS * ks + sub >= nk) break; // (an odd number of steps: the last stage is half full)
-            const int8_t *cur = lds + (ks % NS) * STAGE + sub * STEP;
-            unsigned vb[WM];
-#pragma unroll
-            for (int i = 0; i < WM; ++i) {
-                const int row = wave * 64 + i * 32 + lr;
-                vb[i] = *reinterpret_cast<const unsigned *>(cur + (row >> 7) * 1024 + (((row & 127) * 2 + h) << 2));
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                v4i fa[WM], fb[LF];
-#pragma unroll
-                for (int l = 0; l < LF; ++l)
-                    fb[l] = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * t + h));
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) fa[i][e] = (int)((vb[i] >> (4 * t + e)) & 0x01010101u);
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int l = 0; l < LF; ++l) {
-                        if (FIRST && sub == 0 && t == 0) acc[i][l] = MFMA_I8(fa[i], fb[l], ((v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}));
-                        else acc[i][l] = MFMA_I8(fa[i], fb[l], acc[i][l]);
-                    }
-            }
-        }
+        gemm_stage2<decltype(first)::value>(lds + (ks % NS) * STAGE, STEP, DS * ks + 1 < nk, wave, lr, h, acc);
     };
-    if (nk > 0) { // Qfp >= 64; nk = 0: every row of Theta is zero (the caller says so), the sums are
+    if (nk > 0) { // Qfp >= 64
         gemm_stage(0, std::true_type{});
         for (int ks = 1; ks < nst; ++ks) gemm_stage(ks, std::false_type{});
     } else {
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int l = 0; l < LF; ++l)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
+        clear_acc(acc);
     }
     __builtin_amdgcn_s_setprio(0);
     // ---- epilogue ----------------------------------------------------------------------------
@@ -251,24 +168,21 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
     // Vq image stores a step's samples in the order vq_pos() (gml_dev.h), in which this lane's 16 samples of
     // tile i are 16 contiguous bytes per limb: no LDS transpose, two 16-byte stores per limb.
     const int form = FORM;
-    int8_t *vimg = Vq + vq_off(mytile * 32 + lr, 0, k0 + wave * 64, Kp) + h * 32; // row (limb 0, lr) of the wave's image
+    int8_t *vimg = Vq + vq_off(mytile * 32 + lr, 0, kw, Kp) + h * 32; // row (limb 0, lr) of the wave's image
     const int8_t *vsrc = nullptr; // Hessian-vector forms: the same bytes of the row's V image
     double tvh = 0.0;
     if (HV && active) {
         const int vs = vmap[r];
-        vsrc = Vsrc + vq_off(vs, vsrc_pl0, k0 + wave * 64, Kp, vsrc_lbt) + h * 32;
+        vsrc = Vsrc + vq_off(vs, vsrc_pl0, kw, Kp, vsrc_lbt) + h * 32;
         tvh = tauV[vs] * vsrc_scale;
     }
     long long cs = 0, as = 0;
     double fp = 0.0;
     int mx = 0;
-    const int64_t kw = k0 + wave * 64; // first sample of this wave
     constexpr double WSCALE = COARSE ? 16777216.0 : 4294967296.0; // 2^32 w / tau (vq_exp), 2^24 for the coarse form
     const double sgq0 = sg * q0, wk32 = WSCALE * (wuni * it);
     double sg2 = -2.0 * sg;
-    // dither of the V rounding: golden-ratio (Weyl) sequence in the global sample index, offset per node --
-    // independent of tiling, node sharding and compaction, so results stay bit-identical across GPU counts
-    const unsigned dh0 = (unsigned)rc * 0x85EBCA6Bu + (unsigned)(kw + 4 * h) * 0x9E3779B9u;
+    const unsigned dh0 = dither_seed(rc, kw, h);
     if constexpr (FORM == 0) {
         // Exp forms (RISE, logRISE): the arithmetic of vq_exp(), laid out in STAGES over 8 elements at a time (two 4-sample
         // groups).  Every stage is 8 independent copies of a short chain, fenced by sched_barriers: a wave in its epilogue
@@ -277,9 +191,8 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
         // Fewer instructions per element as well: the sign is applied to the rounded magnitude in integers (one bit-field
         // extract serves both sign flips), sum_k V comes from dot4 over the packed digit planes, max|V| from the unsigned
         // magnitudes, and padding samples are masked in a branch only the last sample tile takes.
-        constexpr double MAGIC = 6755399441055744.0, MAGIC32 = 6755399441055744.0 * 4294967296.0;
-        constexpr unsigned GOLD = 0x9E3779B9u, CB = 0x80808080u;
-        const int wleft = (int)((Kreal - kw) < 64 ? (Kreal - kw) : 64); // wave-uniform: real samples among this wave's 64
+        constexpr unsigned CB = 0x80808080u;
+        const int wleft = wave_real(Kreal, kw); // wave-uniform
         int csl[LB] = {0, 0, 0, 0};
         unsigned mxu = 0;
 #pragma unroll
@@ -387,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
                     const int idx = i * 32 + 8 * (2 * hg + (q >> 2)) + (q & 3);
                     tj0[q] = __hiloint2double((int)((unsigned)__double2hiint(tj0[q]) + ((unsigned)nn[q] << 14)), __double2loint(tj0[q]));
                     x[q] = (double)dd[q];
-                    yy[q] = (double)(int)(dh0 + (unsigned)idx * GOLD); // the dither
+                    yy[q] = (double)(int)dither_hash(dh0, idx);
                 }
                 SB;
 #pragma unroll
@@ -420,15 +333,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
                         asm("v_xad_u32 %0, %1, %2, %3" : "=v"(tq) : "v"(mag[q]), "v"(mneg[q]), "v"(CB - (unsigned)mneg[q]));
                         dj[j] = COARSE ? (tq ^ CB) << 8 : tq ^ CB; // (coarse: the three digits of the 23-bit value in the planes 1..3)
                     }
-#pragma unroll
-                    for (int lb = 0; lb < LB; ++lb) {
-                        const unsigned sel = ((4u + lb) << 8) | (unsigned)lb;
-                        const unsigned t01 = __builtin_amdgcn_perm(dj[1], dj[0], sel);
-                        const unsigned t23 = __builtin_amdgcn_perm(dj[3], dj[2], sel);
-                        const unsigned pk = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
-                        pl[lb][2 * hg + gg] = (int)pk;
-                        csl[lb] = __builtin_amdgcn_sdot4((int)pk, 0x01010101, csl[lb], false); // sum of the 4 digits
-                    }
+                    planes_of4<LB>(dj, dj, pl, 2 * hg + gg, csl);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -438,9 +343,9 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
             }
         }
         cs = (long long)csl[0] + 256ll * csl[1] + 65536ll * csl[2] + 16777216ll * csl[3];
-        cs += __shfl_xor(cs, 32);
-        as += __shfl_xor(as, 32);
-        const unsigned mo = (unsigned)__shfl_xor((int)mxu, 32);
+        cs = half_sum(cs);
+        as = half_sum(as);
+        const unsigned mo = (unsigned)__shfl_xor((int)mxu, 32); // (not half_max(): through it these instances take two more registers)
         mxu = mo > mxu ? mo : mxu;
         if (COARSE) mxu = (mxu + 1u) << 8; // in units of tau, rounded up to the next multiple of 2^8 tau
         if (active && h == 0) {
@@ -461,14 +366,10 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
         for (int g = 0; g < 4; ++g) {
             const int64_t kk = kw + i * 32 + 8 * g + 4 * h;
             unsigned dj[4], dv[4];
-            if (HV) { // the 4 balanced digits of V of each of the group's 4 samples (inverse of the transpose below)
+            if (HV) { // the 4 balanced digits of V of each of the group's 4 samples (the transpose below, backwards)
+                const unsigned pg[4] = {(unsigned)pv[0][g], (unsigned)pv[1][g], (unsigned)pv[2][g], (unsigned)pv[3][g]};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned sel = ((4u + j) << 8) | (unsigned)j;
-                    const unsigned t01 = __builtin_amdgcn_perm((unsigned)pv[1][g], (unsigned)pv[0][g], sel);
-                    const unsigned t23 = __builtin_amdgcn_perm((unsigned)pv[3][g], (unsigned)pv[2][g], sel);
-                    dv[j] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
-                }
+                for (int j = 0; j < 4; ++j) dv[j] = bytes_of4(pg, j);
             }
             if (FORM == 2) { // RPLE: gate each 4-sample group on the previous one (its longer arithmetic otherwise
                              // interleaves across groups and spills); pure arithmetic floats across sched_barriers
@@ -501,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
                     a = (double)(acc[i][0][e] + (acc[i][1][e] << 8));
                 }
                 const double Ea = fma(a, sg2, sgq0);                // |E| pre-sign: sigma * (q0 + S - 2 A)
-                const double dith = (double)(int)(dh0 + (unsigned)(i * 32 + 8 * g + j) * 0x9E3779B9u) * 2.3283064365386963e-10; // [-1/2, 1/2)
+                const double dith = dither_unit(dh0, i * 32 + 8 * g + j); // [-1/2, 1/2)
                 const bool neg = ((sgn[i] >> (8 * g + j)) & 1u) != 0; // s_u^k = -1
                 int vq;
                 if (HV) {
@@ -514,33 +415,14 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
                         const double wk0 = UNIW ? (i * 32 + 8 * g + j < nreal ? wuni : 0.0) : w[kk + j];
                         hh = wk0 > 0.0 ? 2.0 * hh * (1.0 - hh * tvh / (2.0 * wk0)) : 0.0;
                     }
-                    vq = __double2loint(fma(hh, Ea * it, dith) + 6755399441055744.0);
-                } else if (FORM == 2) { // RPLE (:317): f = w log(1 + exp(-2E)), V = -2 w s / (1 + exp(2E)), E = s * Ea
+                    vq = __double2loint(fma(hh, Ea * it, dith) + MAGIC);
+                } else if (FORM == 2) { // RPLE, rounded to a 31-bit integer
                     const double wk0 = UNIW ? (i * 32 + 8 * g + j < nreal ? wuni : 0.0) : w[kk + j];
-                    const double E2 = neg ? -2.0 * Ea : 2.0 * Ea;
-                    const double u = exp_tab(-fabs(E2), etab); // in (0, 1]
-                    const double opu = 1.0 + u;
-                    double rc = __builtin_amdgcn_rcp(opu); // 1 / (1 + u), two Newton steps
-                    rc = fma(fma(-opu, rc, 1.0), rc, rc);
-                    rc = fma(fma(-opu, rc, 1.0), rc, rc);
-                    const double sig = E2 >= 0.0 ? u * rc : rc; // 1 / (1 + exp(2E))
-                    const int mag = __double2loint(fma(2.0 * wk0 * it, sig, dith) + 6755399441055744.0);
+                    const int mag = __double2loint(rple_point(Ea, neg, wk0, it, dith, etab, fp) + MAGIC);
                     vq = neg ? mag : -mag;
-                    // log(1 + u), 1 + u in (1, 2]: table of log c_j on 64 intervals + log1p of the residual
-                    int jt = (int)(u * 64.0);
-                    jt = jt > 63 ? 63 : jt;
-                    const double r1 = fma(opu, etab[64 + jt], -1.0); // |r1| <= 1/128
-                    double lp = fma(r1, 1.0 / 7.0, -1.0 / 6.0);
-                    lp = fma(lp, r1, 0.2);
-                    lp = fma(lp, r1, -0.25);
-                    lp = fma(lp, r1, 1.0 / 3.0);
-                    lp = fma(lp, r1, -0.5);
-                    lp = fma(lp, r1, 1.0);
-                    const double l1p = fma(lp, r1, etab[128 + jt]);
-                    fp += wk0 * ((E2 < 0.0 ? -E2 : 0.0) + l1p);
                 } else { // RISE (:196,:204) / logRISE Z (:279): V = -w exp(-E) s
                     const unsigned sb = ~sgn[i] >> (8 * g + j); // bit 0: s = +1
-                    const unsigned dh = dh0 + (unsigned)(i * 32 + 8 * g + j) * 0x9E3779B9u;
+                    const unsigned dh = dither_hash(dh0, i * 32 + 8 * g + j);
                     if (UNIW) {
                         vq = vq_exp(Ea, sb, wk32, dh, etab);
                         if (i * 32 + 8 * g + j >= nreal) vq = 0; // padding samples carry no weight
@@ -554,14 +436,8 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
                 cs += vq;
                 dj[j] = ((unsigned)vq + 0x80808080u) ^ 0x80808080u; // 4 balanced base-256 digits
             }
-            // 4 samples x 4 limbs byte transpose -> one dword per limb plane
 #pragma unroll
-            for (int lb = 0; lb < LB; ++lb) {
-                const unsigned sel = ((4u + lb) << 8) | (unsigned)lb;
-                const unsigned t01 = __builtin_amdgcn_perm(dj[1], dj[0], sel);
-                const unsigned t23 = __builtin_amdgcn_perm(dj[3], dj[2], sel);
-                pl[lb][g] = (int)__builtin_amdgcn_perm(t23, t01, 0x05040100u);
-            }
+            for (int lb = 0; lb < LB; ++lb) pl[lb][g] = (int)bytes_of4(dj, lb);
         }
         if (active) {
 #pragma unroll
@@ -570,25 +446,24 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8(
             for (int lb = 0; lb < LB; ++lb) *reinterpret_cast<v4i *>(vimg + lb * 32 * 64 + i * 16) = pl[lb];
         }
     }
-    cs += __shfl_xor(cs, 32);
-    as += __shfl_xor(as, 32);
+    cs = half_sum(cs);
+    as = half_sum(as);
     if (active && h == 0) {
         atomicAdd(reinterpret_cast<unsigned long long *>(&csum[r]), (unsigned long long)cs);
         if (WANTF) atomicAdd(reinterpret_cast<unsigned long long *>(&asum[r]), (unsigned long long)as);
     }
     if (form == 0) {
-        const int mo = __shfl_xor(mx, 32);
-        mx = mo > mx ? mo : mx;
+        mx = half_max(mx);
         if (active && h == 0) atomicMax(&mmax[r], (unsigned)mx);
     }
     if (form == 2) {
-        fp += __shfl_xor(fp, 32);
+        fp = half_sum(fp);
         if (active && h == 0) unsafeAtomicAdd(&fsum[r], fp);
     }
 }
 
-template <int LF, int FORM, bool WANTF, bool WIDE, bool UNIW, bool COARSE>
-static void launch_fwd5(const FwdLaunch &a) {
+template <int LF, int FORM, bool WANTF, bool WIDE, bool COARSE, bool UNIW>
+static void launch_one(const FwdLaunch &a) {
     constexpr int STAGE = 2 * (2 + 2 * LF) * 1024; // two 64-column steps per ring stage, three stages
     constexpr int shmem = 3 * STAGE + 512 + 1024;   // ring + exp, log tables
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_i8<LF, FORM, WANTF, WIDE, COARSE, UNIW>),
@@ -597,31 +472,19 @@ static void launch_fwd5(const FwdLaunch &a) {
     i8_note_instance((LF - 2) * 64 + fi * 16 + WANTF * 8 + WIDE * 4 + COARSE * 2 + UNIW);
     const DevProblem &d = *a.d;
     const int ntk = a.ntk;
-    const int grid = ((ntk + 7) / 8) * 8 * a.ngroups; // one workgroup per (sample tile, node tile); see the kernel's block mapping
+    const int grid = fwd_grid(ntk, a.ngroups);
     hipLaunchKernelGGL((k_fwd_i8<LF, FORM, WANTF, WIDE, COARSE, UNIW>), dim3(grid), dim3(256), shmem, a.st, d.Xb, d.Sb, a.w->Tq, a.rowcol, a.groups,
                        a.ngroups, d.w, a.sc->sigma, a.sc->qconst, a.sc->invtau, d.Kp, ntk, a.zero_theta ? 0 : (int)(d.Qfp / 64), d.wuni, d.K, a.Vout,
                        a.sc->csum, a.sc->asum, a.F, a.sc->mmax, a.w->Vq, a.vmap, a.w->sc[0].tau, a.w->LBT, a.w->vpl0(), a.w->vscale(),
                        a.chunk_tiles, a.part_tiles, a.cc ? a.cc->cnk : nullptr, a.cc ? a.cc->Xc : nullptr, a.cc ? a.cc->xc_tile : 0, (int)(d.Qfp / 64));
 }
 
-template <int LF, int FORM, bool WANTF, bool WIDE, bool UNIW>
-static void launch_fwd4(const FwdLaunch &a) {
-    if constexpr (LF == 4 && FORM == 0) {
-        if (a.coarse) return launch_fwd5<LF, FORM, WANTF, WIDE, UNIW, true>(a);
-    }
-    launch_fwd5<LF, FORM, WANTF, WIDE, UNIW, false>(a);
-}
-
-template <int LF, int FORM, bool WANTF, bool WIDE>
-static void launch_fwd3(const FwdLaunch &a) {
-    if (a.d->wuni > 0.0) launch_fwd4<LF, FORM, WANTF, WIDE, true>(a);
-    else launch_fwd4<LF, FORM, WANTF, WIDE, false>(a);
-}
-
+// COARSE only for LF = 4 and the exp forms (elsewhere a.coarse selects nothing)
 template <int LF, int FORM, bool WANTF>
 static void launch_fwd2(const FwdLaunch &a) {
-    if (a.d->Qfp > 32768) launch_fwd3<LF, FORM, WANTF, true>(a);
-    else launch_fwd3<LF, FORM, WANTF, false>(a);
+    dispatch_bools([&](auto wide, auto uniw, auto coarse) {
+        launch_one<LF, FORM, WANTF, decltype(wide)::value, decltype(coarse)::value && LF == 4 && FORM == 0, decltype(uniw)::value>(a);
+    }, a.d->Qfp > 32768, a.d->wuni > 0.0, a.coarse);
 }
 
 template <int LF>

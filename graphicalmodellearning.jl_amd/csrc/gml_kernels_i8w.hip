@@ -20,9 +20,15 @@
 // registers), sweep B multiplies the planes 0..2 (96 accumulators), the sample bits loaded twice.  V is kept as two halves of 3
 // planes, V / tau = lo + 2^24 hi: the backward GEMM runs as two launches of the 3-plane form of k_bwd_i8 and every integer sum
 // (per half) stays far inside 64 bits.
-#include "gml_i8.h"
+//
+// Build flags: -DI8W_TWO_SWEEPS (above; tests/test_gpu_i8w_single_sweep.py) and -DABL_TIMING (s_memrealtime stamps per phase,
+// read back through the V planes: scripts/gpu_fwd_timing.py).  Variants that were measured and no longer have a flag -- they live
+// in git history: the two-sweep kernel without its V stores, without its exp arithmetic, without both, and with sweep B cut to one
+// stage (forward 7.36 ms -> 6.48 / 6.83 / 6.11 / 5.63 ms: profiles/r4_ab_i8w_forward_ablation.txt); the epilogue's sign words and
+// 1 / tau fetched ahead of the sweeps (not adopted: registers are what the sweeps are short of); V stored in whole 128-byte
+// lines through LDS (0.8 % slower: profiles/r5_ab_i8w_line_stores.txt).
+#include "gml_i8_fwd.h"
 #include <string>
-#include <type_traits>
 
 namespace gml {
 
@@ -41,9 +47,6 @@ static_assert(P1 % 4 == 0 && NL1 == 4, "one stage: 4 DMA instructions per wave")
 constexpr bool ONE_SWEEP = false;
 #else
 constexpr bool ONE_SWEEP = true;
-#endif
-#if defined(I8W_LINE_STORES) && !defined(I8W_TWO_SWEEPS)
-#error "I8W_LINE_STORES stages through the ring of the two-sweep form: build it with -DI8W_TWO_SWEEPS"
 #endif
 // the forms that take the single sweep: the full-width ones, but RPLE beyond 32768 columns (its epilogue keeps 2 more registers
 // through the fold, which spills them: it keeps the two sweeps)
@@ -71,7 +74,7 @@ __device__ __forceinline__ void digits6(double yr, unsigned &dl, unsigned &dh) {
 // forward: energies by two sweeps of C[k][m] = sum_c b[k][c] * Tq[m][c] (b = [x = -1] from the bit image), then the pointwise
 // epilogue   E = s sigma (C0 - 2 sum_l 256^l C_l),  V = -w exp(-E) s  (RISE / logRISE),  -2 w s / (1 + exp(2E))  (RPLE),
 // V -> 6 balanced digits -> the planes of the wave's Vq image.  Workgroup = 4 waves along the samples: 256 samples x one
-// 32-node tile; block mapping, ring and fragment handling as in k_fwd_i8.
+// 32-node tile (block mapping: gml_i8_map.h; what the kernel shares with k_fwd_i8: gml_i8_fwd.h).
 // ------------------------------------------------------------------------------------------
 template <int FORM /* 0: exp forms (RISE, logRISE), 2: RPLE */, bool WANTF, bool WIDE /* more than 32768 statistics columns */, bool UNIW,
           bool COARSE /* sweep A only: Theta from its top four planes (30 bits), V in three planes (dithered 23 bits: planes 3..5, plane 2
@@ -86,53 +89,21 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     // column compaction (gml_i8_pack.hip: k_col_union): steps of each tile's compact image (-1: all columns), the images, bytes per tile,
     // and the steps between two tiles' Tq images (= Qfp / 64 whatever is swept)
     const int *__restrict__ cnk, const int8_t *__restrict__ Xc, int64_t xc_tile, int nk_tq) {
-    constexpr int WM = 2; // 32-sample MFMA tiles per wave
     extern __shared__ __attribute__((aligned(16))) int8_t lds[]; // ring, then the exp (and log) tables
     double *etab = reinterpret_cast<double *>(lds + ring_bytes(FORM, WIDE, COARSE));
 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lane = tid & 63, lr = lane & 31, h = lane >> 5; // (the single sweep takes them afresh after its GEMM)
-    if (tid < 64) {
-        const double v = exp2((double)tid / 64.0);
-        // exp forms: 2^(j/64) with j << 14 taken off the high word (the exponent of 2^(n >> 6), n = 64 q + j, goes on as n << 14)
-        etab[tid] = FORM == 0 ? __hiloint2double(__double2hiint(v) - (tid << 14), __double2loint(v)) : v;
-    }
-    if (FORM == 2 && tid < 64) { // log table for RPLE: c_j = 1 + (j + 1/2)/64 -> 1/c_j, log c_j
-        const double cj = 1.0 + ((double)tid + 0.5) / 64.0;
-        etab[64 + tid] = 1.0 / cj;
-        etab[128 + tid] = log(cj);
-    }
-    __syncthreads();
+    fill_tables<FORM>(etab, tid);
 
-    // XCD-aware L2 blocking, as in k_fwd_i8: XCD x owns the sample tiles st = 8 i + x and sweeps them inside groups of TG node tiles
-    constexpr int TG = 8;
-    const int b = blockIdx.x, xcd = b & 7, bi = b >> 3;
-    const int ntk8 = (ntiles_k + 7) >> 3;
-    const int nfull = ngroups / TG, per_full = ntk8 * TG;
-    int st, gi;
-    if (bi < nfull * per_full) {
-        const int rem = bi % per_full;
-        st = (rem / TG) * 8 + xcd;
-        gi = (bi / per_full) * TG + rem % TG;
-    } else {
-        const int lastn = ngroups - nfull * TG, rem = bi - nfull * per_full;
-        st = (rem / lastn) * 8 + xcd;
-        gi = nfull * TG + rem % lastn;
-    }
-    if (st >= ntiles_k) return;
+    const FwdBlock blk = fwd_block(blockIdx.x, ntiles_k, ngroups);
+    if (!blk.live) return;
+    const int st = blk.st;
     const int64_t k0 = (int64_t)st * 256;
     if (k0 >= Kp) return;
-    const int mytile = groups[gi];
-    // the columns this tile sweeps: all of them, or its compact list (the image then has the tile's own step count in its strides)
-    int nk = nk_all;
-    const int8_t *xbase = reinterpret_cast<const int8_t *>(Xb);
-    if (cnk) {
-        const int ck = cnk[mytile];
-        if (ck >= 0) {
-            nk = ck;
-            xbase = Xc + (int64_t)mytile * xc_tile;
-        }
-    }
+    const FwdTile tile = fwd_tile(groups, blk.gi, nk_all, Xb, cnk, Xc, xc_tile);
+    const int mytile = tile.mytile, nk = tile.nk;
+    const int8_t *const xbase = tile.xbase;
 
     const int voffX = lane * 16;
     const int voffT = (lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4);
@@ -142,12 +113,6 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     int r = mytile * 32 + lr;
     const int rc = rowcol[r];
     const bool active = rc >= 0;
-#ifdef ABL_EARLY_INPUTS
-    unsigned sgn[WM];
-#pragma unroll
-    for (int i = 0; i < WM; ++i) sgn[i] = active ? (Sb[(int64_t)rc * (Kp >> 5) + ((k0 + wave * 64) >> 5) + i] >> (4 * h)) : 0u;
-    const double it = active ? invtau[r] : 0.0;
-#endif
 
 #ifdef ABL_TIMING
     unsigned long long tst[6];
@@ -189,22 +154,12 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
             __builtin_amdgcn_sched_barrier(0);
             if (ks + NS1 - 1 < nk) issue1(ks + NS1 - 1); // (into the stage every wave finished reading before the barrier)
             const int8_t *cur = lds + (ks % NS1) * STEP1;
-            // lane (lr, h) needs dword h of its sample's 8 bytes of bits.  One ds_read_b64 per lane reads both: the 32 lanes of a
-            // half-wave cover 256 contiguous bytes, one bank each (ds_read_b32 banks modulo 32 dwords: lanes lr and lr + 16 collide).
             unsigned vb[WM];
-#pragma unroll
-            for (int i = 0; i < WM; ++i) {
-                const int row = wave * 64 + i * 32 + lr;
-                const uint2 v = *reinterpret_cast<const uint2 *>(cur + (row >> 7) * 1024 + (row & 127) * 8);
-                vb[i] = h ? v.y : v.x;
-            }
+            read_bits<true>(cur, wave, lr, h, vb);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 v4i fa[WM];
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) fa[i][e] = (int)((vb[i] >> (4 * t + e)) & 0x01010101u);
+                expand_bits(vb, t, fa);
 #pragma unroll
                 for (int l = 0; l < LFW; ++l) {
                     const v4i fb = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * t + h));
@@ -216,16 +171,11 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 }
             }
         };
-        if (nk > 0) { // Qfp >= 64; nk = 0: every row of Theta is zero (the caller says so): all sums are 0, nothing is loaded
+        if (nk > 0) { // Qfp >= 64
             step(0, std::true_type{});
             for (int ks = 1; ks < nk; ++ks) step(ks, std::false_type{});
         } else {
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int l = 0; l < LFW; ++l)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
+            clear_acc(acc);
         }
 #ifdef ABL_TIMING
         tst[1] = tst[2] = __builtin_amdgcn_s_memrealtime();
@@ -326,7 +276,6 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         // one ring stage of GEMM work on NPL digit planes
         auto gemm_stage = [&](int gs, int ks, auto first, auto &acc) {
             constexpr bool FIRST = decltype(first)::value;
-            constexpr int NPL = sizeof(acc[0]) / sizeof(acc[0][0]);
             // the next stage may stay in flight: its loads are the last ones this wave issued
             if (gs + 1 < ntot) {
                 if (gs + 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLA) : "memory");
@@ -337,50 +286,18 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             if (gs + NSW - 1 < ntot) issue(gs + NSW - 1);
-#pragma unroll
-            for (int sub = 0; sub < DSW; ++sub) {
-                if (sub > 0 && DSW * ks + sub >= nk) break; // (an odd number of steps: the last stage is half full)
-                const int8_t *cur = lds + (gs % NSW) * STAGEW + sub * STEPW;
-                unsigned vb[WM];
-#pragma unroll
-                for (int i = 0; i < WM; ++i) {
-                    const int row = wave * 64 + i * 32 + lr;
-                    vb[i] = *reinterpret_cast<const unsigned *>(cur + (row >> 7) * 1024 + (((row & 127) * 2 + h) << 2));
-                }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    v4i fa[WM], fb[NPL];
-#pragma unroll
-                    for (int l = 0; l < NPL; ++l) fb[l] = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * t + h));
-#pragma unroll
-                    for (int i = 0; i < WM; ++i)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) fa[i][e] = (int)((vb[i] >> (4 * t + e)) & 0x01010101u);
-#pragma unroll
-                    for (int i = 0; i < WM; ++i)
-#pragma unroll
-                        for (int l = 0; l < NPL; ++l) {
-                            if (FIRST && sub == 0 && t == 0) acc[i][l] = MFMA_I8(fa[i], fb[l], ((v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}));
-                            else acc[i][l] = MFMA_I8(fa[i], fb[l], acc[i][l]);
-                        }
-                }
-            }
+            gemm_stage2<FIRST>(lds + (gs % NSW) * STAGEW, STEPW, DSW * ks + 1 < nk, wave, lr, h, acc);
         };
 
         // ---- sweep A: digit planes 3..6, folded into us = sigma 2^24 (c_hi - 2 a_hi), a_hi = sum_{l>=3} 256^(l-3) C_l (exact: an integer
         // below 2^53 times a power of two)
         {
             v16i acc[WM][LFA];
-            if (nk > 0) { // Qfp >= 64; nk = 0: every row of Theta is zero (the caller says so): all sums are 0, nothing is loaded
+            if (nk > 0) { // Qfp >= 64
                 gemm_stage(0, 0, std::true_type{}, acc);
                 for (int ks = 1; ks < nst; ++ks) gemm_stage(ks, ks, std::false_type{}, acc);
             } else {
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int l = 0; l < LFA; ++l)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
+                clear_acc(acc);
             }
 #ifdef ABL_TIMING
             tst[1] = __builtin_amdgcn_s_memrealtime();
@@ -414,18 +331,9 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
             v16i acc[WM][LFB];
             if (nk > 0) {
                 gemm_stage(nst, 0, std::true_type{}, acc);
-#ifndef ABL_ONESWEEP
                 for (int ks = 1; ks < nst; ++ks) gemm_stage(nst + ks, ks, std::false_type{}, acc);
-#else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             } else {
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int l = 0; l < LFB; ++l)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[i][l][e] = 0;
+                clear_acc(acc);
             }
 #pragma unroll
             for (int i = 0; i < WM; ++i)
@@ -448,27 +356,22 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     tst[3] = __builtin_amdgcn_s_memrealtime();
 #endif
 
-#ifndef ABL_EARLY_INPUTS
-    unsigned sgn[WM]; // the node's sign bits for this wave's 64 samples, shifted so that bit 8g + j is this lane's sample 8g + 4h + j
+    const int64_t kw = k0 + wave * 64; // first sample of this wave
+    unsigned sgn[WM];
 #pragma unroll
-    for (int i = 0; i < WM; ++i) sgn[i] = active ? (Sb[(int64_t)rc * (Kp >> 5) + ((k0 + wave * 64) >> 5) + i] >> (4 * h)) : 0u;
+    for (int i = 0; i < WM; ++i) sgn[i] = sign_word(Sb, rc, active, Kp, kw, h, i);
     const double it = active ? invtau[r] : 0.0;
-#endif
-    const int64_t left = Kreal - (k0 + wave * 64 + 4 * h);
-    const int nreal = left > 64 ? 64 : (left < 0 ? 0 : (int)left);
+    const int nreal = lane_real(Kreal, kw, h);
 
     // ---- epilogue ----------------------------------------------------------------------------
     // lane <-> node row (lr), register e <-> sample (e&3) + 8*(e>>2) + 4*h within the 32-sample tile; the Vq image stores a
     // step's samples in the order vq_pos() (gml_bits.h): this lane's 16 samples of tile i are 16 contiguous bytes per plane.
-    int8_t *vimg = Vq + vq_off(mytile * 32 + lr, 0, k0 + wave * 64, Kp, LBW) + h * 32;
-    const int64_t kw = k0 + wave * 64; // first sample of this wave
+    int8_t *vimg = Vq + vq_off(mytile * 32 + lr, 0, kw, Kp, LBW) + h * 32;
     // 2^32 w / tau; a coarse pass rounds V to multiples of 2^24 tau (the same dither, one step up)
     const double wscale = COARSE ? 256.0 : 4294967296.0; // 2^32 / 2^24
     const double wk32 = wscale * (wuni * it);
-    const unsigned dh0 = (unsigned)rc * 0x85EBCA6Bu + (unsigned)(kw + 4 * h) * 0x9E3779B9u; // dither: see k_fwd_i8
-    constexpr double MAGIC = 6755399441055744.0, MAGIC32 = 6755399441055744.0 * 4294967296.0;
-    constexpr unsigned GOLD = 0x9E3779B9u;
-    const int wleft = (int)((Kreal - kw) < 64 ? (Kreal - kw) : 64); // wave-uniform: real samples among this wave's 64
+    const unsigned dh0 = dither_seed(rc, kw, h);
+    const int wleft = wave_real(Kreal, kw); // wave-uniform
     int csl[LBW] = {0, 0, 0, 0, 0, 0};
     unsigned long long as64 = 0;
     int ymax_hi = 0; // high word of the largest 2^32 (|V| / tau + dither): non-negative doubles order like their bit patterns
@@ -477,36 +380,19 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     // digits of 4 consecutive samples -> one dword per plane, and the plane sums
     auto pack4 = [&](const unsigned (&dl)[4], const unsigned (&dhh)[4], v4i (&pl)[LBW], int slot) {
         if (COARSE) { // the three digits of the 23-bit value go to the planes 3..5; plane 2 reads zero (the consumers of the top four)
-#pragma unroll
-            for (int lb = 0; lb < 3; ++lb) {
-                const unsigned sel = ((4u + lb) << 8) | (unsigned)lb;
-                const unsigned pk = __builtin_amdgcn_perm(__builtin_amdgcn_perm(dl[3], dl[2], sel), __builtin_amdgcn_perm(dl[1], dl[0], sel), 0x05040100u);
-                pl[3 + lb][slot] = (int)pk;
-                csl[3 + lb] = __builtin_amdgcn_sdot4((int)pk, 0x01010101, csl[3 + lb], false);
-            }
+            planes_of4<3>(dl, dl, pl + 3, slot, csl + 3);
             pl[2][slot] = 0;
-            return;
-        }
-#pragma unroll
-        for (int lb = 0; lb < LBW; ++lb) {
-            const unsigned bsel = (unsigned)(lb & 3);
-            const unsigned sel = ((4u + bsel) << 8) | bsel;
-            const unsigned t01 = lb < 4 ? __builtin_amdgcn_perm(dl[1], dl[0], sel) : __builtin_amdgcn_perm(dhh[1], dhh[0], sel);
-            const unsigned t23 = lb < 4 ? __builtin_amdgcn_perm(dl[3], dl[2], sel) : __builtin_amdgcn_perm(dhh[3], dhh[2], sel);
-            const unsigned pk = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
-            pl[lb][slot] = (int)pk;
-            csl[lb] = __builtin_amdgcn_sdot4((int)pk, 0x01010101, csl[lb], false);
+        } else {
+            planes_of4<LBW>(dl, dhh, pl, slot, csl);
         }
     };
 
     if constexpr (FORM == 0) {
         // Exp forms: the arithmetic is laid out in layers of 8 independent instructions (two 4-sample groups), fenced by
-        // sched_barriers, as in k_fwd_i8 -- a wave in its epilogue then issues back to back instead of waiting out the latency
-        // of each dependent FP64 instruction.
+        // sched_barriers -- a wave in its epilogue then issues back to back instead of waiting out the latency of each dependent
+        // FP64 instruction (the element-at-a-time form left the scheduler, at 200+ live registers, emitting each element's chain
+        // serially).
 #define SB __builtin_amdgcn_sched_barrier(0)
-#ifdef I8W_LINE_STORES
-        v4i plk[WM][LBW]; // the digits of both sample tiles, until the wave's image leaves in whole lines (below)
-#endif
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
             const unsigned nsg = ~sgn[i]; // bit 8g + j set <=> s = +1
@@ -524,11 +410,6 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                     if (!UNIW) wk[q] = w[kw + i * 32 + 8 * (2 * hg + (q >> 2)) + 4 * h + (q & 3)];
                 }
                 SB;
-#ifdef ABL_NOEPI
-#pragma unroll
-                for (int q = 0; q < 8; ++q) yy[q] = fma(fabs(Ea[q]), 1.0e21, 2.0e23);
-                if (false) {
-#endif
                 // B: x = -s E, n = rint(64 x / ln2), r = x - n ln2 / 64 (two-part constant)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
@@ -570,7 +451,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 for (int q = 0; q < 8; ++q) {
                     const int idx = i * 32 + 8 * (2 * hg + (q >> 2)) + (q & 3);
                     tj0[q] = __hiloint2double((int)((unsigned)__double2hiint(tj0[q]) + ((unsigned)nn[q] << 14)), __double2loint(tj0[q]));
-                    yy[q] = (double)(int)(dh0 + (unsigned)idx * GOLD);
+                    yy[q] = (double)(int)dither_hash(dh0, idx);
                 }
                 SB;
 #pragma unroll
@@ -578,9 +459,6 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 SB;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) yy[q] = fma(UNIW ? wk32 : wscale * (wk[q] * it), x[q], yy[q]);
-#ifdef ABL_NOEPI
-                }
-#endif
                 if (UNIW && wleft < 64) { // the last sample tile: padding samples carry no weight
                     asm volatile("; padding samples" ::: "memory");
 #pragma unroll
@@ -609,66 +487,17 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-#ifndef I8W_LINE_STORES
-#ifdef ABL_NOSTORE
-            if (active && pl[0][0] == 0x12345678 && pl[5][3] == 0x1234567) {
-#else
             if (active) {
-#endif
                 // (every lane stores its 16 bytes per plane and tile straight from registers: an instruction covers 32 rows x 16 B, a
                 // quarter of each 64-byte row, and the write-combining of L2 puts the lines together -- WRITE_SIZE reads 8.8 GB per
-                // launch for 6.1 GB of planes.  The line-wide form below (-DI8W_LINE_STORES) removes that inflation and is 0.8 %
-                // SLOWER: profiles/r5_ab_i8w_line_stores.txt -- the partial writes cost no time, the LDS round trip does.)
+                // launch for 6.1 GB of planes.  A variant that staged the wave's image through LDS and stored whole 128-byte lines
+                // removed that inflation and was 0.8 % SLOWER: profiles/r5_ab_i8w_line_stores.txt -- the partial writes cost no time,
+                // the LDS round trip does.  It lives in git history.)
 #pragma unroll
                 for (int lb = COARSE ? 2 : 0; lb < LBW; ++lb) *reinterpret_cast<v4i *>(vimg + lb * 32 * 64 + i * 16) = pl[lb];
             }
-#else
-#pragma unroll
-            for (int lb = COARSE ? 2 : 0; lb < LBW; ++lb) plk[i][lb] = pl[lb];
-#endif
         }
-#ifdef I8W_LINE_STORES
-        // (A/B variant, not the default -- see above.)  The wave's 64 samples x 32 rows x 6 planes are ONE contiguous 12-KB image of
-        // Vq.  It leaves through LDS -- the two ring
-        // stages the last GEMM step no longer reads are free: every wave has passed that step's barrier -- so that each store
-        // instruction writes 1 KB = eight whole 128-byte lines: the lanes put their 16-byte pieces where the image has them
-        // (16-byte slots XOR-swizzled by (row >> 2) & 3: conflict-free on both sides), then read the image back linearly.  Three
-        // planes at a time (6 KB per wave).  Rows that are not part of this pass keep what they hold (a re-run of some rows of a
-        // tile must not touch the planes of the others): their lines are stored partially.
-        {
-            const int nst = (nk + DSW - 1) / DSW, ntot = COARSE ? nst : 2 * nst;
-            const int lastslot = (ntot > 0 ? ntot - 1 : 0) % NSW;
-            int8_t *stg = lds + ((lastslot + 1 + (wave >> 1)) % NSW) * STAGEW + (wave & 1) * 6144;
-            const unsigned amask = (unsigned)__ballot(active); // bit lr (lanes 0..31)
-            int8_t *img = Vq + vq_off(mytile * 32, 0, kw, Kp, LBW);
-            constexpr int G0 = COARSE ? 2 : 0, NG = COARSE ? 2 : 3; // plane groups [G0, G0 + NG), [G0 + NG, LBW)
-#pragma unroll
-            for (int grp = 0; grp < 2; ++grp) {
-                const int p0 = G0 + grp * NG;
-#pragma unroll
-                for (int lbl = 0; lbl < NG; ++lbl)
-#pragma unroll
-                    for (int i = 0; i < WM; ++i) {
-                        const int row = lbl * 32 + lr, sl = 2 * h + i;
-                        *reinterpret_cast<v4i *>(stg + row * 64 + ((sl ^ ((row >> 2) & 3)) << 4)) = plk[i][p0 + lbl];
-                    }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (one wave: its LDS accesses execute in order)
-#pragma unroll
-                for (int j = 0; j < 2 * NG; ++j) {
-                    const int o = j * 1024 + lane * 16, row = o >> 6, sl = (o >> 4) & 3;
-                    const v4i dv = *reinterpret_cast<const v4i *>(stg + row * 64 + ((sl ^ ((row >> 2) & 3)) << 4));
-#ifdef ABL_NOSTORE
-                    if (dv[0] == 0x12345678 && dv[3] == 0x1234567 && ((amask >> (row & 31)) & 1u))
-#else
-                    if ((amask >> (row & 31)) & 1u)
-#endif
-                        *reinterpret_cast<v4i *>(img + p0 * 2048 + o) = dv;
-                }
-                asm volatile("" ::: "memory");
-            }
-        }
-#endif
-    } else { // RPLE (:317): f = w log(1 + exp(-2E)), V = -2 w s / (1 + exp(2E)), E = s Ea
+    } else { // RPLE
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
             v4i pl[LBW];
@@ -679,32 +508,11 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 asm volatile("" : "+v"(fp)); // gate each 4-sample group on the previous one (register pressure)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * g + j;
-                    const double Ea = us[i][e];
-                    const double dith = (double)(int)(dh0 + (unsigned)(i * 32 + 8 * g + j) * GOLD) * 2.3283064365386963e-10; // [-1/2, 1/2)
+                    const double dith = dither_unit(dh0, i * 32 + 8 * g + j); // [-1/2, 1/2)
                     const bool neg = ((sgn[i] >> (8 * g + j)) & 1u) != 0; // s_u^k = -1
                     const double wk0 = UNIW ? (i * 32 + 8 * g + j < nreal ? wuni : 0.0) : w[kk + j];
-                    const double E2 = neg ? -2.0 * Ea : 2.0 * Ea;
-                    const double u = exp_tab(-fabs(E2), etab); // in (0, 1]
-                    const double opu = 1.0 + u;
-                    double rcp = __builtin_amdgcn_rcp(opu); // 1 / (1 + u), two Newton steps
-                    rcp = fma(fma(-opu, rcp, 1.0), rcp, rcp);
-                    rcp = fma(fma(-opu, rcp, 1.0), rcp, rcp);
-                    const double sig = E2 >= 0.0 ? u * rcp : rcp; // 1 / (1 + exp(2E))
-                    const double y = fma(2.0 * wk0 * it, sig, dith); // |V| / tau + dither
+                    const double y = rple_point(us[i][4 * g + j], neg, wk0, it, dith, etab, fp);
                     digits6((neg ? y : -y) + MAGIC, dl[j], dhh[j]);
-                    // log(1 + u), 1 + u in (1, 2]: table of log c_j on 64 intervals + log1p of the residual
-                    int jt = (int)(u * 64.0);
-                    jt = jt > 63 ? 63 : jt;
-                    const double r1 = fma(opu, etab[64 + jt], -1.0); // |r1| <= 1/128
-                    double lp = fma(r1, 1.0 / 7.0, -1.0 / 6.0);
-                    lp = fma(lp, r1, 0.2);
-                    lp = fma(lp, r1, -0.25);
-                    lp = fma(lp, r1, 1.0 / 3.0);
-                    lp = fma(lp, r1, -0.5);
-                    lp = fma(lp, r1, 1.0);
-                    const double l1p = fma(lp, r1, etab[128 + jt]);
-                    fp += wk0 * ((E2 < 0.0 ? -E2 : 0.0) + l1p);
                 }
                 pack4(dl, dhh, pl, g);
             }
@@ -726,21 +534,21 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     // per-slot sums: sum_k V (two halves), sum_k |V| (objective-only passes), max_k |V| >> 16
     long long cs_lo = (long long)csl[0] + 256ll * csl[1] + 65536ll * csl[2];
     long long cs_hi = (long long)csl[3] + 256ll * csl[4] + 65536ll * csl[5];
-    cs_lo += __shfl_xor(cs_lo, 32);
-    cs_hi += __shfl_xor(cs_hi, 32);
+    cs_lo = half_sum(cs_lo);
+    cs_hi = half_sum(cs_hi);
     if (active && h == 0) {
         if (!COARSE) atomicAdd(reinterpret_cast<unsigned long long *>(&csum[r]), (unsigned long long)cs_lo);
         atomicAdd(reinterpret_cast<unsigned long long *>(&csum2[r]), (unsigned long long)cs_hi);
     }
     if (FORM == 0) {
         if (WANTF) {
-            as64 += __shfl_xor(as64, 32);
+            as64 = half_sum(as64);
             if (active && h == 0) {
                 atomicAdd(reinterpret_cast<unsigned long long *>(&asum[r]), as64 & 0xffffffffull);
                 atomicAdd(reinterpret_cast<unsigned long long *>(&asum2[r]), as64 >> 32);
             }
         }
-        ymax_hi = max(ymax_hi, __shfl_xor(ymax_hi, 32));
+        ymax_hi = half_max(ymax_hi);
         // the high word + 1 bounds 2^32 max(|V| / tau + dither) from above (to 2^-20 relative); in units of 2^16 tau
         const double ymax = __hiloint2double(ymax_hi + 1, 0);
         // (coarse: ymax bounds 2^32 (|V| / (2^24 tau) + dither), the dither down to -1/2 of that unit: |V| / (2^24 tau) < floor(ymax 2^-32)
@@ -750,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                                     : (unsigned)fmin(fma(ymax, 3.5527136788005009e-15 /* 2^-48 */, 7.62939453125e-06 /* 2^-17 */), 4294967295.0);
         if (active && h == 0) atomicMax(&mmax[r], mxu);
     } else {
-        fp += __shfl_xor(fp, 32);
+        fp = half_sum(fp);
         if (active && h == 0) unsafeAtomicAdd(&fsum[r], fp);
     }
 }
@@ -811,38 +619,25 @@ void launch_finalize_i8w(const int32_t *Gacc, const SlotScalars &sc, const int *
 }
 
 template <int FORM, bool WANTF, bool WIDE, bool UNIW, bool COARSE>
-static void launch_fwd_w5(const FwdWArgs &a) {
+static void launch_one(const FwdWArgs &a) {
     constexpr int shmem = ring_bytes(FORM, WIDE, COARSE) + 512 + 1024; // ring + exp, log tables
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, shmem); // per device: set on every launch
     i8_note_instance(256 + (FORM == 2) * 16 + WANTF * 8 + WIDE * 4 + UNIW * 2 + COARSE);
     const DevProblem &d = *a.d;
     const int ntk = (int)(d.Kp / 256);
-    const int grid = ((ntk + 7) / 8) * 8 * a.ngroups; // one workgroup per (sample tile, node tile)
-    hipLaunchKernelGGL((k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>), dim3(grid), dim3(256), shmem, a.st, d.Xb, d.Sb, a.Tq, a.rowcol, a.groups,
+    hipLaunchKernelGGL((k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>), dim3(fwd_grid(ntk, a.ngroups)), dim3(256), shmem, a.st, d.Xb, d.Sb, a.Tq, a.rowcol, a.groups,
                        a.ngroups, d.w, a.sc->sigma, a.sc->qconst, a.sc->qconst2, a.sc->invtau, d.Kp, ntk, a.zero_theta ? 0 : (int)(d.Qfp / 64), d.wuni, d.K, a.Vq,
                        a.sc->csum, a.sc->csum2, a.sc->asum, a.sc->asum2, a.F, a.sc->mmax, a.cc ? a.cc->cnk : nullptr, a.cc ? a.cc->Xc : nullptr,
                        a.cc ? a.cc->xc_tile : 0, (int)(d.Qfp / 64));
 }
 
-template <int FORM, bool WANTF, bool WIDE, bool UNIW>
-static void launch_fwd_w4(const FwdWArgs &a) {
-    if constexpr (FORM == 0) {
-        if (a.coarse) return launch_fwd_w5<FORM, WANTF, WIDE, UNIW, true>(a);
-    }
-    launch_fwd_w5<FORM, WANTF, WIDE, UNIW, false>(a);
-}
-
-template <int FORM, bool WANTF, bool WIDE>
-static void launch_fwd_w3(const FwdWArgs &a) {
-    if (a.d->wuni > 0.0) launch_fwd_w4<FORM, WANTF, WIDE, true>(a);
-    else launch_fwd_w4<FORM, WANTF, WIDE, false>(a);
-}
-
+// COARSE only for the exp forms (for RPLE a.coarse selects nothing)
 template <int FORM, bool WANTF>
 static void launch_fwd_w2(const FwdWArgs &a) {
-    if (a.d->Qfp > 32768) launch_fwd_w3<FORM, WANTF, true>(a);
-    else launch_fwd_w3<FORM, WANTF, false>(a);
+    dispatch_bools([&](auto wide, auto uniw, auto coarse) {
+        launch_one<FORM, WANTF, decltype(wide)::value, decltype(uniw)::value, decltype(coarse)::value && FORM == 0>(a);
+    }, a.d->Qfp > 32768, a.d->wuni > 0.0, a.coarse);
 }
 
 void launch_fwd_i8w(const FwdWArgs &a) {
