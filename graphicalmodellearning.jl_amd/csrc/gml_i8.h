@@ -16,6 +16,7 @@
 // Layout of the limb planes ("planar tiles"): rows are grouped by 32-node tile `t` and limb `l`:
 //   Tq image (t, kt) = [LF*32 rows][64 B]: row l*32 + rl holds limb l of node row t*32+rl, columns
 //                      [64kt, 64kt+64); images are contiguous (t major)            (forward B operand)
+//                      (i8w, tiles on signed column pairs: the limbs of q + q', q - q' per pair, in the order of gml_i8_pairs.h)
 //   Vq image (t, k/64) = [LB*32 rows][64 B]: row l*32 + rl holds limb l of V row t*32+rl, samples
 //                      [64(k/64), +64); images are contiguous (t major), see vq_off()  (backward A operand)
 // so that a wave's 32x32 MFMA tiles of the different limbs share lane <-> node and
@@ -40,6 +41,7 @@
 namespace gml {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int LB = 4;  // limb planes of V of the i8x pass (31 significant bits relative to the per-node bound)
@@ -54,6 +56,7 @@ struct SlotScalars {
     double *sigma = nullptr, *tau = nullptr, *invtau = nullptr;
     long long *qconst = nullptr, *csum = nullptr, *asum = nullptr;
     long long *qconst2 = nullptr; // i8w: the constant of the coarse form (the number the top four planes of Theta spell)
+    long long *qpair = nullptr;   // i8w: the constant column's integer alone: what a paired sweep, which sums x q itself, adds (gml_i8_pairs.h)
     long long *csum2 = nullptr, *asum2 = nullptr; // i8w: the high halves (sum of the planes 3..5; sum of |V| >> 32)
     unsigned *mmax = nullptr; // largest |V| / tau seen per slot in the last pass (i8w: >> 16) (dynamic-range check)
 };
@@ -83,6 +86,7 @@ struct I8Ws {
     int *cnk = nullptr;    // [slots / 32] 64-column steps of the tile's compact image; -1: the tile runs on all columns
     int *cmap = nullptr;   // [slots / 32][csteps * 64] the columns, ascending, -1 padded
     int8_t *Xc = nullptr;  // [slots / 32][xc_tile bytes] compact forward images, Xb piece layout with the tile's own step count
+    int *tdense = nullptr; // [slots / 32] (7-plane workspaces) signed column pairs: 1 = the tile's Tq image holds plain planes (gml_i8_pairs.h)
     int csteps = 0;        // capacity in steps per tile
     int64_t xc_tile = 0;   // = Kp * csteps * 8
     int vpl0() const { return LBT - 4; }
@@ -94,6 +98,9 @@ struct I8Ws {
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
 
 #define MFMA_I8(a, b, c) __builtin_amdgcn_mfma_i32_32x32x32_i8((a), (b), (c), 0, 0, 0)
+// 2:4 structured-sparse form: a = the 16 kept bytes of the lane's 32 K slots, idx = their 2-bit slots within each group of four
+// (layout found on the device: scripts/ubench/smfmac_i8_rate.hip), b = 32 dense bytes; accumulates into c in place
+#define SMFMAC_I8(a, b, c, idx) __builtin_amdgcn_smfmac_i32_32x32x64_i8((a), (b), (c), (idx), 0, 0)
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
@@ -185,7 +192,7 @@ void i8_note_instance(int bit);
 // ---- launchers across the kernel files ----------------------------------------------------------------------------------
 // gml_i8_pack.hip
 void launch_quant_theta(int LF, int ns, const I8Pass &a, const DevProblem &d, int hv, const double *tauV, int8_t *Tq, const SlotScalars &sc,
-                        double vdiv, double vsrc_scale, hipStream_t st, const ColCompact *cc = nullptr);
+                        double vdiv, double vsrc_scale, hipStream_t st, const ColCompact *cc = nullptr, int *tdense = nullptr /* paired planes; marks the tiles that keep plain ones */);
 // the non-zero columns of every listed tile's rows -> cnk / cmap, then the compact forward images of the tiles that got one
 void launch_col_compact(const I8Pass &a, const DevProblem &d, I8Ws *w, hipStream_t st);
 // gml_i8_fwd.hip
@@ -206,7 +213,7 @@ struct FwdLaunch {
 void launch_fwd_i8(const FwdLaunch &a, int LF, int form, bool wantf, int hv);
 // gml_i8_bwd.hip
 void launch_zero_pass(const SlotScalars &sc, double *F, const int *rowcol, int slot0, int ns, int32_t *gacc0, int64_t ngacc4, int nplanes, int64_t plane_stride4,
-                      hipStream_t st);
+                      hipStream_t st, int *tdense = nullptr /* the pass pairs columns: its tiles' marks are cleared */);
 void launch_bwd_i8(int NL, const int8_t *Vin, const DevProblem &d, const int *groups, int ngt, int nNt, int64_t kchunk, int nsplit, int32_t *Gacc,
                    int cpp, int64_t plane_stride, int64_t kpart, int lbt, int pl0, hipStream_t st);
 void launch_finalize_i8(const int32_t *Gacc, const SlotScalars &sc, const int *srow, const int *rowcol, int slot0, int ns, const DevProblem &d,
@@ -226,7 +233,10 @@ struct FwdWArgs {
     hipStream_t st;
     bool zero_theta = false; // every row of Theta is zero: no column sweeps (the energies are 0)
     const ColCompact *cc = nullptr; // tiles with a compact column list sweep those columns only
+    const int *tdense = nullptr;    // signed column pairs: per node tile, 0 = the image holds pair planes (NULL: plain planes everywhere)
 };
+// does this form of the pass sweep once over all seven planes?  (only those forms have the paired sweep)
+bool fwd_i8w_one_sweep(int form, int64_t Qfp, bool coarse);
 void launch_fwd_i8w(const FwdWArgs &a);
 void launch_finalize_i8w(const int32_t *Gacc, const SlotScalars &sc, const int *srow, const int *rowcol, int slot0, int ns, int64_t Qp,
                          int64_t Qfp, int64_t Qf, int64_t cconst, int form, int want_grad, double *G, double *f, int nplanes,

@@ -262,8 +262,9 @@ __global__ __launch_bounds__(256) void k_zero_pass(long long *__restrict__ csum,
                                                    long long *__restrict__ csum2, long long *__restrict__ asum2,
                                                    unsigned *__restrict__ mmax, double *__restrict__ f, const int *__restrict__ rowcol,
                                                    int slot0, int ns, v4i *__restrict__ gacc, int64_t ngacc, int nplanes,
-                                                   int64_t plane_stride4) {
+                                                   int64_t plane_stride4, int *__restrict__ tdense /* NULL: the pass does not pair columns */) {
     const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    if (tdense && i0 < ns / 32) tdense[slot0 / 32 + i0] = 0; // (the quantisation marks the tiles that must keep plain planes)
     // (only the slots this pass evaluates: a re-run of some rows of a tile leaves the others' planes in place, and with them the
     // scalars that describe those planes -- the working-set Hessians read tau and the largest |V| of a row's LAST pass)
     if (i0 < ns && rowcol[slot0 + i0] >= 0) {
@@ -281,9 +282,9 @@ __global__ __launch_bounds__(256) void k_zero_pass(long long *__restrict__ csum,
 
 
 void launch_zero_pass(const SlotScalars &sc, double *F, const int *rowcol, int slot0, int ns, int32_t *gacc0, int64_t ngacc4, int nplanes,
-                      int64_t plane_stride4, hipStream_t st) {
+                      int64_t plane_stride4, hipStream_t st, int *tdense) {
     hipLaunchKernelGGL(k_zero_pass, dim3(1024), dim3(256), 0, st, sc.csum, sc.asum, sc.csum2, sc.asum2, sc.mmax, F, rowcol, slot0, ns,
-                       reinterpret_cast<v4i *>(gacc0), ngacc4, nplanes, plane_stride4);
+                       reinterpret_cast<v4i *>(gacc0), ngacc4, nplanes, plane_stride4, tdense);
 }
 
 void launch_bwd_i8(int NL, const int8_t *Vin, const DevProblem &d, const int *groups, int ngt, int nNt, int64_t kchunk, int nsplit, int32_t *Gacc,

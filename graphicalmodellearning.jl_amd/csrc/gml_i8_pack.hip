@@ -1,6 +1,7 @@
 // Int8-limb path, part 1: the bit images of the samples and the quantisation of the parameter rows into limb planes
 // (overview: gml_i8.h).
 #include "gml_i8.h"
+#include "gml_i8_pairs.h"
 #include <algorithm>
 #include <string>
 #include <type_traits>
@@ -241,13 +242,19 @@ __global__ __launch_bounds__(256) void k_quant_theta(const double *__restrict__ 
                                                      const int *__restrict__ vmap, const double *__restrict__ tauV,
                                                      int8_t *__restrict__ Tq, double *__restrict__ sigma,
                                                      double *__restrict__ tau, double *__restrict__ invtau,
-                                                     long long *__restrict__ qconst, long long *__restrict__ qconst2, const double *__restrict__ tauovr,
+                                                     long long *__restrict__ qconst, long long *__restrict__ qconst2, long long *__restrict__ qpair, const double *__restrict__ tauovr,
                                                      const double *__restrict__ tauovr_lnrow,
                                                      double vdiv /* largest |V| / tau the planes of this pass hold */,
                                                      double vsrc_scale /* hv: unit of the V planes read, in multiples of tauV */,
-                                                     const int *__restrict__ cnk, const int *__restrict__ cmap, int cstride) {
+                                                     const int *__restrict__ cnk, const int *__restrict__ cmap, int cstride,
+                                                     // signed column pairs (7 planes; gml_i8_pairs.h).  pairs = 1: the image gets the planes of
+                                                     // (q + q', q - q') per pair, and a pair outside seven digits marks its tile in tdense;
+                                                     // pairs = 2, the launch behind it: the rows of marked tiles again, with plain planes (a
+                                                     // tile's rows are quantised by 32 workgroups: none of them sees the others' pairs)
+                                                     int pairs, int *__restrict__ tdense) {
     const int r = slot0 + blockIdx.x; // slot
     if (rowcol[r] < 0) return;
+    if (LF > 5 && pairs == 2 && tdense[r >> 5] == 0) return;
     const double *th = Theta + (int64_t)srow[r] * Qp;
     __shared__ double red[256];
     __shared__ double red1[256];
@@ -297,7 +304,33 @@ __global__ __launch_bounds__(256) void k_quant_theta(const double *__restrict__ 
     const int ck = cnk ? cnk[tile] : -1;
     const int64_t ncol = ck >= 0 ? (int64_t)ck * 64 : Qfp;
     const int *cm = ck >= 0 ? cmap + (int64_t)tile * cstride : nullptr;
-    for (int64_t j = tid; j < ncol; j += 256) {
+    bool outside = false;
+    for (int64_t p = tid; LF > 5 && pairs == 1 && p < ncol / 2; p += 256) {
+        const int64_t kt = p >> 5;
+        const int h = (int)(p >> 4) & 1, m = (int)p & 15;
+        long long q2[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int64_t j = kt * 64 + pair_col(h, m, s);
+            const int64_t c = cm ? cm[j] : j;
+            long long q = c >= 0 ? (long long)rint(th[c] * isg) : 0;
+            q2[s] = q;
+            sabs += q < 0 ? -q : q;
+            ssum += q;
+            for (int l = 0; l < 3; ++l) (void)balanced_digit(q);
+            shi += q;
+        }
+        outside |= !pair_in_range(q2[0], q2[1]);
+        int8_t *img = Tq + ((((int64_t)tile * nk + kt) * LF) * 32 + rl) * 64 + pair_slot(h, m);
+        long long a = q2[0] + q2[1], b = q2[0] - q2[1];
+#pragma unroll
+        for (int l = 0; l < LF; ++l) {
+            img[l * 32 * 64] = (int8_t)balanced_digit(a);
+            img[l * 32 * 64 + 1] = (int8_t)balanced_digit(b);
+        }
+    }
+    if (outside) tdense[tile] = 1;
+    for (int64_t j = tid; !(LF > 5 && pairs == 1) && j < ncol; j += 256) {
         const int64_t c = cm ? cm[j] : j;
         long long q = c >= 0 ? (long long)rint(th[c] * isg) : 0;
         sabs += q < 0 ? -q : q;
@@ -336,6 +369,7 @@ __global__ __launch_bounds__(256) void k_quant_theta(const double *__restrict__ 
         }
         __syncthreads();
     }
+    const long long qc0 = q0; // (thread 0: the constant column's integer)
     q0 += redl[0];
     q0hi += redh[0];
     if (tid == 0) {
@@ -368,7 +402,10 @@ __global__ __launch_bounds__(256) void k_quant_theta(const double *__restrict__ 
         }
         sigma[r] = sg;
         qconst[r] = q0;
-        if (LF > 5) qconst2[r] = q0hi;
+        if (LF > 5) {
+            qconst2[r] = q0hi;
+            qpair[r] = qc0;
+        }
         tau[r] = t;
         invtau[r] = it;
     }
@@ -376,18 +413,25 @@ __global__ __launch_bounds__(256) void k_quant_theta(const double *__restrict__ 
 
 
 void launch_quant_theta(int LF, int ns, const I8Pass &a, const DevProblem &d, int hv, const double *tauV, int8_t *Tq, const SlotScalars &sc,
-                        double vdiv, double vsrc_scale, hipStream_t st, const ColCompact *cc) {
+                        double vdiv, double vsrc_scale, hipStream_t st, const ColCompact *cc, int *tdense) {
     const int *cnk = cc ? cc->cnk : nullptr, *cmap = cc ? cc->cmap : nullptr;
     const int cstride = cc ? cc->cstride : 0;
 #define QUANT(LFV)                                                                                                                    \
     hipLaunchKernelGGL((k_quant_theta<LFV>), dim3(ns), dim3(256), 0, st, a.theta, a.srow, a.rowcol, a.slot0, d.Qp, d.Qfp, d.cconst,   \
-                       d.wmax, a.form, hv, a.vmap, tauV, Tq, sc.sigma, sc.tau, sc.invtau, sc.qconst, sc.qconst2, a.tauovr, a.tauovr_lnrow, vdiv, vsrc_scale, \
-                       cnk, cmap, cstride)
+                       d.wmax, a.form, hv, a.vmap, tauV, Tq, sc.sigma, sc.tau, sc.invtau, sc.qconst, sc.qconst2, sc.qpair, a.tauovr, a.tauovr_lnrow, vdiv, vsrc_scale, \
+                       cnk, cmap, cstride, pairs, tdense)
+    int pairs = tdense && LF == 7 ? 1 : 0;
     switch (LF) {
     case 2: QUANT(2); break;
     case 3: QUANT(3); break;
     case 4: QUANT(4); break;
-    case 7: QUANT(7); break;
+    case 7:
+        QUANT(7);
+        if (pairs) {
+            pairs = 2;
+            QUANT(7);
+        }
+        break;
     default: QUANT(5);
     }
 #undef QUANT

@@ -1,6 +1,7 @@
 // Int8-limb path, part 5: the workspace of the passes and the orchestration of one pass (quantise -> forward -> backward ->
 // finalise) for both widths, "i8x" (38/31 bits) and "i8w" (54/47 bits, FP64-grade).  Overview: gml_i8.h.
 #include "gml_i8.h"
+#include "gml_solver.h"
 #include <algorithm>
 #include <string>
 
@@ -30,11 +31,11 @@ void i8_free(void *p) {
     I8Ws *w = static_cast<I8Ws *>(p);
     if (!w) return;
     (void)hipDeviceSynchronize(); // once for all the blocks below (dev_free_synced)
-    void *ptrs[] = {w->Tq, w->Vq, w->Uq, w->Gacc, w->tauovr, w->Hq, w->hS, w->H64, w->Mb, w->cnk, w->cmap, w->Xc};
+    void *ptrs[] = {w->Tq, w->Vq, w->Uq, w->Gacc, w->tauovr, w->Hq, w->hS, w->H64, w->Mb, w->cnk, w->cmap, w->Xc, w->tdense};
     for (void *q : ptrs)
         if (q) (void)dev_free_synced(q);
     for (auto &sc : w->sc) {
-        void *qs[] = {sc.sigma, sc.tau, sc.invtau, sc.qconst, sc.qconst2, sc.csum, sc.asum, sc.csum2, sc.asum2, sc.mmax};
+        void *qs[] = {sc.sigma, sc.tau, sc.invtau, sc.qconst, sc.qconst2, sc.qpair, sc.csum, sc.asum, sc.csum2, sc.asum2, sc.mmax};
         for (void *q : qs)
             if (q) (void)dev_free_synced(q);
     }
@@ -60,6 +61,7 @@ static int i8_ensure(void **wsp, const DevProblem &d, int64_t slots, int wide, h
         w->LBT = LBW;
     }
     I8CHK(dev_malloc(&w->Tq, (size_t)slots * w->LF * d.Qfp));
+    if (wide == 1) I8CHK(dev_malloc(&w->tdense, sizeof(int) * (size_t)(slots / 32 + 1)));
     I8CHK(dev_malloc(&w->Vq, (size_t)slots * w->LBT * d.Kp));
     // i32 accumulators of the backward GEMM hold |sum_k v_k b_k| <= 128 K: exact up to 2^24 configurations per set
     // (beyond 2^24: sets of <= 2^23 configurations + the slack of whole split-K chunks, see i8_pass)
@@ -71,6 +73,7 @@ static int i8_ensure(void **wsp, const DevProblem &d, int64_t slots, int wide, h
         I8CHK(dev_malloc(&sc.invtau, sizeof(double) * slots));
         I8CHK(dev_malloc(&sc.qconst, sizeof(long long) * slots));
         I8CHK(dev_malloc(&sc.qconst2, sizeof(long long) * slots));
+        I8CHK(dev_malloc(&sc.qpair, sizeof(long long) * slots));
         I8CHK(dev_malloc(&sc.csum, sizeof(long long) * slots));
         I8CHK(dev_malloc(&sc.asum, sizeof(long long) * slots));
         I8CHK(dev_malloc(&sc.csum2, sizeof(long long) * slots));
@@ -167,10 +170,13 @@ int i8_pass(void **wsp, const DevProblem &d, int64_t slot_capacity, const I8Pass
     const int lbg = wide ? LBW : LB; // limb planes of this pass's V and of its gradient accumulators
     int32_t *gacc0 = w->Gacc + (int64_t)a.slot0 * lbg * d.Qfp;
     const int64_t gplane_stride = (int64_t)w->slots * lbg * d.Qfp;
-    launch_zero_pass(sc, a.F, a.rowcol, a.slot0, ns, gacc0, grad ? (int64_t)ns * lbg * d.Qfp / 4 : 0, w->gplanes, gplane_stride / 4, st);
+    // signed column pairs on the sparse MFMA (gml_i8_pairs.h): the full-width objective passes whose forward kernel sweeps once.  The
+    // coarse form reads the top four planes of plain digits and Hessian-vector passes quantise their own; both keep the dense sweep.
+    int *const tdense = wide && !coarse && w->tdense && fwd_i8w_one_sweep(a.form, d.Qfp, coarse) && g_tune[GML_TUNE_NO_PAIRS] == 0.0 ? w->tdense : nullptr;
+    launch_zero_pass(sc, a.F, a.rowcol, a.slot0, ns, gacc0, grad ? (int64_t)ns * lbg * d.Qfp / 4 : 0, w->gplanes, gplane_stride / 4, st, tdense);
     if (LF < 3 && !hv) LF = 3; // 2 limbs exist for the directions of Hessian-vector passes only
     if (cc) launch_col_compact(a, d, w, st); // cnk / cmap / Xc of the listed tiles, in front of the quantisation that follows them
-    launch_quant_theta(LF, ns, a, d, hv, w->sc[0].tau, w->Tq, sc, wide ? kVdiv6 : kVdiv4, w->vscale(), st, cc);
+    launch_quant_theta(LF, ns, a, d, hv, w->sc[0].tau, w->Tq, sc, wide ? kVdiv6 : kVdiv4, w->vscale(), st, cc, tdense);
     // split-K plan of the backward GEMM (made here: a sub-sampled pass runs its forward kernel over the same parts)
     const int nNt = (int)((d.Qfp + 255) / 256);
     constexpr int TM = 1; // node tiles per backward workgroup (the 8-wave form with two, TM = 2, measured slower)
@@ -194,6 +200,7 @@ int i8_pass(void **wsp, const DevProblem &d, int64_t slot_capacity, const I8Pass
         FwdWArgs fw{&d, w->Tq, &sc, a.rowcol, a.groups, a.ngroups, a.form, !a.want_grad, coarse, a.F, w->Vq, st};
         fw.zero_theta = a.zero_theta && !hv;
         fw.cc = cc;
+        fw.tdense = tdense;
         launch_fwd_i8w(fw);
     } else {
         FwdLaunch fl{(int)(kchunk / 256), (int)(kpart / 256), 0, w, &d, &sc, a.rowcol, a.groups, a.vmap, a.ngroups, a.F, hv ? w->Uq : w->Vq, st};

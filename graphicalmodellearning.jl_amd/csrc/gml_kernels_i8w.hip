@@ -14,7 +14,10 @@
 // tiles x 16 accumulators = 224 registers, the 4 of one plane's Theta fragment (read plane by plane, fed to both sample tiles),
 // the 8 of the bit fragments, a handful of offsets: at most 256 at two workgroups per CU.  A ring stage is one 64-column step
 // (2 KB of bits + 14 KB of digit planes, 4 DMA instructions per wave), 4 stages deep; the sample bits are read and expanded once
-// per step.  After the sweep the 7 accumulators of each element are folded into its energy, element by element.  The coarse
+// per step.  After the sweep the 7 accumulators of each element are folded into its energy, element by element.  Where the tile's
+// image holds signed column pairs (gml_i8_pairs.h: the planes of q + q', q - q'; full-width objective passes) the step runs on the 2:4
+// sparse MFMA, v_smfmac_i32_32x32x64_i8: one instruction per plane and sample tile covers the 64 columns, 14 per step instead of 28,
+// the fragment 8 registers instead of 4 (254 - 256 registers, no spill: profiles/r15_fwd_pairs_resources.txt).  The coarse
 // form sweeps only the top four planes (its own ring, two steps per stage).  -DI8W_TWO_SWEEPS builds the earlier form for A/B
 // runs: sweep A multiplies the planes 3..6 (128 accumulators), folds them into 32 FP64 partial energies per lane (64
 // registers), sweep B multiplies the planes 0..2 (96 accumulators), the sample bits loaded twice.  V is kept as two halves of 3
@@ -82,13 +85,16 @@ template <int FORM /* 0: exp forms (RISE, logRISE), 2: RPLE */, bool WANTF, bool
 __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     const unsigned *__restrict__ Xb, const unsigned *__restrict__ Sb, const int8_t *__restrict__ Tq, const int *__restrict__ rowcol,
     const int *__restrict__ groups, int ngroups, const double *__restrict__ w, const double *__restrict__ sigma,
-    const long long *__restrict__ qconst, const long long *__restrict__ qconst2, const double *__restrict__ invtau, int64_t Kp, int ntiles_k,
+    const long long *__restrict__ qconst, const long long *__restrict__ qconst2, const long long *__restrict__ qpair, const double *__restrict__ invtau, int64_t Kp, int ntiles_k,
     int nk_all /* 64-column steps of a sweep over all columns (0: every row of Theta is zero) */,
     double wuni, int64_t Kreal, int8_t *__restrict__ Vq, long long *__restrict__ csum, long long *__restrict__ csum2,
     long long *__restrict__ asum, long long *__restrict__ asum2, double *__restrict__ fsum, unsigned *__restrict__ mmax,
     // column compaction (gml_i8_pack.hip: k_col_union): steps of each tile's compact image (-1: all columns), the images, bytes per tile,
     // and the steps between two tiles' Tq images (= Qfp / 64 whatever is swept)
-    const int *__restrict__ cnk, const int8_t *__restrict__ Xc, int64_t xc_tile, int nk_tq) {
+    const int *__restrict__ cnk, const int8_t *__restrict__ Xc, int64_t xc_tile, int nk_tq,
+    // signed column pairs (gml_i8_pairs.h): per node tile, 0 = the tile's Tq image holds the planes of (q + q', q - q') and the sweep runs on
+    // the 2:4 sparse MFMA, else plain planes and the dense sweep (NULL: every tile plain).  Single-sweep forms only.
+    const int *__restrict__ tdense) {
     extern __shared__ __attribute__((aligned(16))) int8_t lds[]; // ring, then the exp (and log) tables
     double *etab = reinterpret_cast<double *>(lds + ring_bytes(FORM, WIDE, COARSE));
 
@@ -171,7 +177,36 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 }
             }
         };
-        if (nk > 0) { // Qfp >= 64
+        // the same step on signed column pairs: the picks (+-1 bytes and their slot indices) come from the same bit dwords, one
+        // plane's fragment is the lane's 32 K-contiguous bytes of the row (two reads), one sparse MFMA per plane and sample tile
+        // covers the whole 64-column step: 14 where the dense step issues 28.  The sparse MFMA accumulates in place: no FIRST form.
+        auto step_pairs = [&](int ks) {
+            if (ks + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL1) : "memory");
+            else if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL1) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks + NS1 - 1 < nk) issue1(ks + NS1 - 1);
+            const int8_t *cur = lds + (ks % NS1) * STEP1;
+            unsigned vb[WM];
+            read_bits<true>(cur, wave, lr, h, vb);
+            v4i fa[WM];
+            int ix[WM];
+            pair_picks(vb, fa, ix);
+#pragma unroll
+            for (int l = 0; l < LFW; ++l) {
+                const v4i f0 = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * h));
+                const v4i f1 = *reinterpret_cast<const v4i *>(cur + 2048 + lds_off(l * 32 + lr, 2 * h + 1));
+                const v8i fb = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
+#pragma unroll
+                for (int i = 0; i < WM; ++i) acc[i][l] = SMFMAC_I8(fa[i], fb, acc[i][l], ix[i]);
+            }
+        };
+        const bool pairs = tdense && tdense[mytile] == 0; // (uniform over the workgroup)
+        if (nk > 0 && pairs) {
+            clear_acc(acc);
+            for (int ks = 0; ks < nk; ++ks) step_pairs(ks);
+        } else if (nk > 0) { // Qfp >= 64
             step(0, std::true_type{});
             for (int ks = 1; ks < nk; ++ks) step(ks, std::false_type{});
         } else {
@@ -188,9 +223,14 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         // what the fold needs is fetched behind the sweep: registers are what the sweep is short of, and the co-resident
         // workgroup covers the wait.  C0 = sum_c q_c + q_const = c_lo + 2^24 c_hi, 0 <= c_lo < 2^24 (see the two-sweep form).
         const double sg = active ? sigma[r] : 0.0;
-        const long long qc = active ? qconst[r] : 0;
+        const long long qc = active ? (pairs ? qpair[r] : qconst[r]) : 0;
         const double c_lo = (double)(unsigned)(qc & 0xffffffll), c_hi = (double)(qc >> 24);
-        const double sgT = sg * 16777216.0, us0 = c_hi * sgT, m2sT = -2.0 * sgT;
+        // (the paired sweep has summed x q = (1 - 2 b) q itself: its plane sums count once, with their sign, where the dense ones count
+        // -2 times, and its constant is the constant column's integer alone, not C0 = that + sum_c q_c.  Either way the two products below
+        // are exact -- an integer below 2^53 times a power of two -- and the last fma rounds sigma * (C0 - 2 sum b q) = sigma * (q_0 +
+        // sum x q) once: the same double)
+        const double ksum = pairs ? 1.0 : -2.0; // (wave-uniform)
+        const double sgT = sg * 16777216.0, us0 = c_hi * sgT, m2sT = ksum * sgT;
         // E / s = sigma (c_lo - 2 a_lo) + sigma 2^24 (c_hi - 2 a_hi), a_lo = sum_{l<3} 256^l C_l, a_hi = sum_{l>=3} 256^(l-3) C_l:
         // the two-sweep form's operations in its order, so the energies are the same bits.  Element by element, pinned, so that
         // the 7 accumulators of an element die as its energy appears.
@@ -210,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                     ahi = fma((double)p1, 65536.0, (double)p0);
                     alo = fma((double)acc[i][2][e], 65536.0, (double)(acc[i][0][e] + (acc[i][1][e] << 8)));
                 }
-                us[i][e] = fma(fma(alo, -2.0, c_lo), sg, fma(ahi, m2sT, us0));
+                us[i][e] = fma(fma(alo, ksum, c_lo), sg, fma(ahi, m2sT, us0));
                 asm volatile("" : "+v"(us[i][e]));
             }
         __builtin_amdgcn_sched_barrier(0);
@@ -627,9 +667,9 @@ static void launch_one(const FwdWArgs &a) {
     const DevProblem &d = *a.d;
     const int ntk = (int)(d.Kp / 256);
     hipLaunchKernelGGL((k_fwd_i8w<FORM, WANTF, WIDE, UNIW, COARSE>), dim3(fwd_grid(ntk, a.ngroups)), dim3(256), shmem, a.st, d.Xb, d.Sb, a.Tq, a.rowcol, a.groups,
-                       a.ngroups, d.w, a.sc->sigma, a.sc->qconst, a.sc->qconst2, a.sc->invtau, d.Kp, ntk, a.zero_theta ? 0 : (int)(d.Qfp / 64), d.wuni, d.K, a.Vq,
+                       a.ngroups, d.w, a.sc->sigma, a.sc->qconst, a.sc->qconst2, a.sc->qpair, a.sc->invtau, d.Kp, ntk, a.zero_theta ? 0 : (int)(d.Qfp / 64), d.wuni, d.K, a.Vq,
                        a.sc->csum, a.sc->csum2, a.sc->asum, a.sc->asum2, a.F, a.sc->mmax, a.cc ? a.cc->cnk : nullptr, a.cc ? a.cc->Xc : nullptr,
-                       a.cc ? a.cc->xc_tile : 0, (int)(d.Qfp / 64));
+                       a.cc ? a.cc->xc_tile : 0, (int)(d.Qfp / 64), one_sweep(FORM, WIDE, COARSE) ? a.tdense : nullptr);
 }
 
 // COARSE only for the exp forms (for RPLE a.coarse selects nothing)
@@ -639,6 +679,8 @@ static void launch_fwd_w2(const FwdWArgs &a) {
         launch_one<FORM, WANTF, decltype(wide)::value, decltype(uniw)::value, decltype(coarse)::value && FORM == 0>(a);
     }, a.d->Qfp > 32768, a.d->wuni > 0.0, a.coarse);
 }
+
+bool fwd_i8w_one_sweep(int form, int64_t Qfp, bool coarse) { return one_sweep(form == GML_RPLE ? 2 : 0, Qfp > 32768, coarse && form != GML_RPLE); }
 
 void launch_fwd_i8w(const FwdWArgs &a) {
     if (a.form == 2) launch_fwd_w2<2, true>(a);
