@@ -89,6 +89,10 @@ struct I8Ws {
     int *tdense = nullptr; // [slots / 32] (7-plane workspaces) signed column pairs: 1 = the tile's Tq image holds plain planes (gml_i8_pairs.h)
     int csteps = 0;        // capacity in steps per tile
     int64_t xc_tile = 0;   // = Kp * csteps * 8
+    // the form of the last objective pass (read by the test hook gml_test_i8_pack_state only): the planes it quantised Theta into, whether it
+    // handed the marks of paired tiles / a compact column table on; tq_hv_lf: planes of a Hessian-vector pass that has rewritten Tq since (0: none)
+    int last_lf = 0, tq_hv_lf = 0;
+    bool last_paired = false, last_compact = false;
     int vpl0() const { return LBT - 4; }
     double vscale() const { return LBT == 6 ? 65536.0 : 1.0; }
 };

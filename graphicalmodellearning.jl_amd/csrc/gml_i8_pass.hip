@@ -177,6 +177,14 @@ int i8_pass(void **wsp, const DevProblem &d, int64_t slot_capacity, const I8Pass
     if (LF < 3 && !hv) LF = 3; // 2 limbs exist for the directions of Hessian-vector passes only
     if (cc) launch_col_compact(a, d, w, st); // cnk / cmap / Xc of the listed tiles, in front of the quantisation that follows them
     launch_quant_theta(LF, ns, a, d, hv, w->sc[0].tau, w->Tq, sc, wide ? kVdiv6 : kVdiv4, w->vscale(), st, cc, tdense);
+    if (hv) {
+        w->tq_hv_lf = LF;
+    } else {
+        w->last_lf = LF;
+        w->tq_hv_lf = 0;
+        w->last_paired = tdense != nullptr;
+        w->last_compact = cc != nullptr;
+    }
     // split-K plan of the backward GEMM (made here: a sub-sampled pass runs its forward kernel over the same parts)
     const int nNt = (int)((d.Qfp + 255) / 256);
     constexpr int TM = 1; // node tiles per backward workgroup (the 8-wave form with two, TM = 2, measured slower)

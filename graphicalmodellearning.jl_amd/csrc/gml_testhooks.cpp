@@ -233,3 +233,56 @@ extern "C" int gml_test_i8_pass_state(gml_problem *p, int64_t *slots, int *plane
     for (size_t i = 0; i < ns; ++i) sums[4 * ns + i] = mm[i];
     return GML_OK;
 }
+
+// Test hook (not part of include/gml.h): the operands the last objective pass of an int8-limb precision was given -- what the pack layer
+// (gml_i8_pack.hip) and i8_pass left on the device.  Read only: synchronises the handle's stream and copies; launches nothing.
+//   dims [20]: 0 slots, 1 planes the Tq buffer is sized for, 2 LF of the last objective pass (0: none yet), 3 it paired columns (i8_pass
+//              handed tdense on), 4 it compacted (handed a column table on), 5 csteps (0: never tried, -1: no memory), 6 Qp, 7 Qfp, 8 Qf,
+//              9 cconst, 10 Kp, 11 K, 12 bytes of the Tq image of that LF, 13 bytes of Xb, 14 bytes of Xtb, 15 bytes of one tile's Xc,
+//              16 rows of the Theta workspace, 17 the workspace has marks (7 planes), 18 LF of a Hessian-vector pass that has rewritten
+//              Tq since (0: Tq is the objective pass's), 19 0
+//   out [13] or NULL (only the sizes); a NULL entry is skipped:
+//              0 Tq int8 [dims 12] = [tile][Qfp / 64][LF][32][64];  1 tdense int [slots / 32] (zeros without marks);  2 cnk int [slots / 32];
+//              3 cmap int [slots / 32][csteps * 64] (2, 3: untouched while csteps <= 0);  4 sigma, 5 tau double [slots];  6 qconst, 7 qconst2,
+//              8 qpair int64 [slots] of sc[0];  9 Theta double [dims 16][Qp], the internal-layout rows the pass read;  10 Xb;  11 Xtb;
+//              12 Xc of tile `xc_tile`
+extern "C" int gml_test_i8_pack_state(gml_problem *p, int64_t xc_tile, int64_t *dims, void **out) {
+    if (!p || !dims) return fail(GML_EINVAL, "bad argument");
+    const gml::I8Ws *w = static_cast<const gml::I8Ws *>(p->i8ws);
+    const DevProblem &d = p->d;
+    const int64_t ns = w ? w->slots : 0, nt = ns / 32;
+    const int64_t v[20] = {ns, w ? w->LF : 0, w ? w->last_lf : 0, w && w->last_paired, w && w->last_compact, w ? w->csteps : 0, d.Qp, d.Qfp, d.Qf, d.cconst,
+                           d.Kp, d.K, w ? ns * w->last_lf * d.Qfp : 0, d.Kp * (d.Qfp / 8), xtb_bytes(d), w ? w->xc_tile : 0, p->ws_rows,
+                           w && w->tdense, w ? w->tq_hv_lf : 0, 0};
+    std::copy(v, v + 20, dims);
+    if (!out) return GML_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->st));
+    auto get = [&](int i, const void *src, size_t bytes) -> hipError_t {
+        return out[i] && src && bytes ? hipMemcpy(out[i], src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIPCHK(get(10, d.Xb, (size_t)v[13]));
+    HIPCHK(get(11, d.Xtb, (size_t)v[14]));
+    if (p->dTheta) HIPCHK(get(9, p->dTheta, sizeof(double) * (size_t)p->ws_rows * d.Qp));
+    if (!w) return GML_OK;
+    HIPCHK(get(0, w->Tq, (size_t)v[12]));
+    if (out[1]) {
+        if (w->tdense) HIPCHK(get(1, w->tdense, sizeof(int) * nt));
+        else std::memset(out[1], 0, sizeof(int) * nt);
+    }
+    if (w->csteps > 0) {
+        HIPCHK(get(2, w->cnk, sizeof(int) * nt));
+        HIPCHK(get(3, w->cmap, sizeof(int) * nt * w->csteps * 64));
+        if (out[12]) {
+            if (xc_tile < 0 || xc_tile >= nt) return fail(GML_EINVAL, "tile %lld outside the %lld tiles of the workspace", (long long)xc_tile, (long long)nt);
+            HIPCHK(get(12, w->Xc + xc_tile * w->xc_tile, (size_t)w->xc_tile));
+        }
+    }
+    const gml::SlotScalars &sc = w->sc[0];
+    HIPCHK(get(4, sc.sigma, sizeof(double) * ns));
+    HIPCHK(get(5, sc.tau, sizeof(double) * ns));
+    HIPCHK(get(6, sc.qconst, sizeof(long long) * ns));
+    HIPCHK(get(7, sc.qconst2, sizeof(long long) * ns));
+    HIPCHK(get(8, sc.qpair, sizeof(long long) * ns));
+    return GML_OK;
+}
