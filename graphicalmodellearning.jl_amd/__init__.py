@@ -4,7 +4,8 @@ Same surface as the reference module (GraphicalModelLearning.jl:3-6, models.jl:3
 the GMLFormulation types, the GMLMethod types (NLP plus the new HIP), FactorGraph.  The compute
 path is libgml_hip.so (hand-written HIP kernels for gfx950 behind the C ABI in include/gml.h).
 """
-from ._lib import GMLConvergenceError, GMLError, MultiProblem, Problem, lib, moments  # noqa: F401
+from ._lib import (EXCLUDED, FREE, PENALISED, GMLConvergenceError, GMLError, MultiProblem, Problem, lib, moments,  # noqa: F401
+                   structure_from_keys, structure_from_rows)
 from .factor_graph import FactorGraph, matrix_to_terms, permutations, check_model_data  # noqa: F401
 from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, GMLMethod,  # noqa: F401
                            logRISE, multiRISE)
@@ -13,4 +14,5 @@ from .sampling import GMSampler, Gibbs, Glauber, GlauberChains, GlauberTermChain
 
 __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multiRISE", "ISODUS", "GMLMethod",
            "NLP", "HIP", "FactorGraph", "Problem", "MultiProblem", "GMLError", "GMLConvergenceError", "sample", "GMSampler", "Gibbs",
-           "Glauber", "GlauberChains", "GlauberTermChains", "TemperedTermChains", "moments"]
+           "Glauber", "GlauberChains", "GlauberTermChains", "TemperedTermChains", "moments", "EXCLUDED", "FREE", "PENALISED",
+           "structure_from_rows", "structure_from_keys"]

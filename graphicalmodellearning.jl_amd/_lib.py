@@ -15,6 +15,8 @@ GML_OK, GML_EINVAL, GML_ENOTCONV, GML_EHIP, GML_ENOMEM, GML_EUNSUPPORTED = range
 GML_ABI_VERSION = 6  # include/gml.h: the revision of the C ABI the mirrors below (Opts, Stats, argument lists) were written against
 FORMULATION_IDS = {"RISE": 0, "RISEA": 0, "multiRISE": 0, "logRISE": 1, "RPLE": 2}
 DTYPES = {np.dtype(np.int8): 0, np.dtype(np.int32): 1, np.dtype(np.int64): 2, np.dtype(np.float64): 3}
+EXCLUDED, FREE, PENALISED = 0, 1, 2  # GML_PARAM_*: the kind of a parameter slot in a structure (gml_learn_structured)
+RULES = {"row": 0, "mean": 1, "all": 2, "any": 3}  # GML_RULE_*: how structure_from_rows decides a key from its members' entries
 PRECISIONS = {"f64": 0, "i8x": 1, "auto": 2, "i8w": 3}  # auto: i8x, i8w for tight tolerances / small problems / operator calls; i8w: FP64-grade int8 limbs
 
 
@@ -109,6 +111,9 @@ def lib():
     L.gml_multi_destroy.restype = None
     L.gml_learn.argtypes = [p, i32, dbl, C.POINTER(Opts), p, p, C.POINTER(Stats)]
     L.gml_learn_warm.argtypes = [p, i32, dbl, C.POINTER(Opts), p, p, p, C.POINTER(Stats)]
+    L.gml_learn_structured.argtypes = [p, i32, dbl, C.POINTER(Opts), p, i64, p, p, p, C.POINTER(Stats)]
+    L.gml_structure_from_rows.argtypes = [p, i64, i64, i32, i32, dbl, i32, i32, i32, i32, p, i64, C.POINTER(i64)]
+    L.gml_structure_from_keys.argtypes = [p, i32, i64, i64, i32, i32, i32, i32, i32, p, i64]
     L.gml_terms_count.restype = i64
     L.gml_terms_count.argtypes = [i64, i32, i32]
     L.gml_terms_assemble.argtypes = [p, i64, i64, i32, i32, i32, p]
@@ -219,6 +224,46 @@ def matrix_symmetrize(rows, device=0):
         raise GMLError(GML_EINVAL, f"matrix_symmetrize needs the rows of all nodes (a square matrix), got {rows.shape}")
     out = np.empty_like(rows)
     check(lib().gml_matrix_symmetrize(_ptr(rows), rows.shape[1], rows.shape[0], int(device), _ptr(out)))
+    return out
+
+
+def params_per_node(n, order):
+    """P: parameters per node (n for order 2, sum_{s <= order} C(n-1, s-1) in general): the row length of learn() and of a structure"""
+    n, order = int(n), int(order)
+    return n if order == 2 else terms_count(n, order, False) // n
+
+
+def structure_from_rows(rows, n, order, threshold, rule="mean", keep=FREE, drop=EXCLUDED, field=FREE, device=0):
+    """gml_structure_from_rows: the structure of a refit from the n solved rows ((n, P) float64; order 2: also the symmetrised
+    n x n matrix), on the device.  A non-field slot is `keep` where its entry -- rule "row" -- or its key's mean / every / some member
+    entry -- "mean" / "all" / "any" -- reaches `threshold` in magnitude, else `drop`; fields are `field`.  Returns (uint8 [n, P],
+    kept): the structure for Problem.learn(structure=...) and the number of kept non-field entries."""
+    if rule not in RULES:
+        raise GMLError(GML_EINVAL, f"structure_from_rows: unknown rule {rule!r} (use 'row', 'mean', 'all' or 'any')")
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    P = params_per_node(n, order)
+    if rows.shape != (int(n), P):
+        raise GMLError(GML_EINVAL, f"structure_from_rows needs the rows of all {n} nodes, {(int(n), P)}, got {rows.shape}")
+    out = np.empty((int(n), P), dtype=np.uint8)
+    kept = C.c_int64()
+    check(lib().gml_structure_from_rows(_ptr(rows), P, int(n), int(order), RULES[rule], float(threshold), int(keep), int(drop), int(field),
+                                        int(device), _ptr(out), P, C.byref(kept)))
+    return out, int(kept.value)
+
+
+def structure_from_keys(terms, n, order, listed=PENALISED, other=EXCLUDED, field=FREE, device=0):
+    """gml_structure_from_keys: the structure that holds the listed terms -- the containers and the 1-based keys of
+    Problem.term_moments (a dict or list of tuples, a FactorGraph, a TermArray).  Every slot is `other` and every field `field`,
+    except that a listed key S sets the slot of (u, S without u) in the row of each of its members u to `listed` (a key of one spin:
+    that spin's field).  Returns uint8 [n, P]."""
+    P = params_per_node(n, order)
+    out = np.empty((int(n), P), dtype=np.uint8)
+    windows = list(moment_key_windows(terms)) or [np.zeros((0, 1), dtype=np.int32)]
+    if len(windows) > 1:  # (an array-backed model comes in windows of one stride)
+        windows = [np.concatenate(windows, axis=0)]
+    keys = windows[0]
+    check(lib().gml_structure_from_keys(_ptr(keys), keys.shape[1], len(keys), int(n), int(order), int(listed), int(other), int(field),
+                                        int(device), _ptr(out), P))
     return out
 
 
@@ -521,12 +566,16 @@ class Problem:
 
     def learn(self, formulation, c, *, tol=1e-9, max_iter=100, precision="auto", max_working=512, max_add=64,
               verbose=0, hess_samples=0, polish=True, max_cg=0, limbs_fwd=0, hv_limbs_fwd=0, hv_limbs_bwd=0, debug_row=0,
-              hv_subsample=0, cg_viol_frac=0.0, cg_eta=0.0, coarse=True, out_ptr=None, raise_on_fail=True, terms=None, x0=None, matrix=None):
+              hv_subsample=0, cg_viol_frac=0.0, cg_eta=0.0, coarse=True, out_ptr=None, raise_on_fail=True, terms=None, x0=None, matrix=None,
+              structure=None):
         """gml_learn: (rows, kkt, stats).  terms = True / False (handles over all nodes): gml_learn_terms instead -- the solved
         rows stay on the device and the first result is the model's weight array in (length, key) order, symmetrised (True) or
         not (False): the input of a FactorGraph (TermArray).  x0: rows to start from ((node1-node0) x P, the layout of the result;
         gml_learn_warm) -- a regularisation path solves each c from the previous solution.  matrix = True / False (pairwise handles
-        over all nodes): gml_learn_matrix -- the n x n result, symmetrised on the device (True) or as it is (False)."""
+        over all nodes): gml_learn_matrix -- the n x n result, symmetrised on the device (True) or as it is (False).
+        structure: uint8 (node1-node0) x P, the kind of every parameter slot in the layout of the result -- EXCLUDED (fixed at 0), FREE
+        (estimated, no penalty) or PENALISED (gml_learn_structured; structure_from_rows / structure_from_keys build one); combines
+        with x0, not with terms or matrix."""
         L = lib()
         o = Opts()
         L.gml_default_opts(C.byref(o))
@@ -547,6 +596,13 @@ class Problem:
             raise GMLError(GML_EINVAL, "matrix (gml_learn_matrix) cannot be combined with terms, x0 or out_ptr")
         if terms is not None and x0 is not None:
             raise GMLError(GML_EINVAL, "x0 (gml_learn_warm) and terms (gml_learn_terms) cannot be combined: solve with x0, then terms_assemble")
+        if structure is not None:
+            if terms is not None or matrix is not None:
+                raise GMLError(GML_EINVAL, "structure (gml_learn_structured) cannot be combined with terms or matrix: solve, then assemble the rows")
+            structure = np.asarray(structure)
+            if structure.dtype != np.uint8 or structure.shape != (R, self.P):
+                raise GMLError(GML_EINVAL, f"structure is {structure.dtype} {structure.shape}, the handle's rows take uint8 {(R, self.P)}")
+            structure = np.ascontiguousarray(structure)
         if matrix is not None:
             out = np.zeros((R, self.P))
             rc = L.gml_learn_matrix(self._h, FORMULATION_IDS[formulation], float(c), int(bool(matrix)), C.byref(o), _ptr(out), _ptr(kkt),
@@ -563,6 +619,10 @@ class Problem:
                 x0 = np.ascontiguousarray(x0, dtype=np.float64)
                 if x0.shape != (R, self.P):
                     raise GMLError(GML_EINVAL, f"x0 has shape {x0.shape}, the handle's rows are {(R, self.P)}")
+            if structure is not None:
+                rc = L.gml_learn_structured(self._h, FORMULATION_IDS[formulation], float(c), C.byref(o), _ptr(structure), self.P, _ptr(x0),
+                                            out_ptr, _ptr(kkt), C.byref(st))
+            elif x0 is not None:
                 rc = L.gml_learn_warm(self._h, FORMULATION_IDS[formulation], float(c), C.byref(o), _ptr(x0), out_ptr, _ptr(kkt), C.byref(st))
             else:
                 rc = L.gml_learn(self._h, FORMULATION_IDS[formulation], float(c), C.byref(o), out_ptr, _ptr(kkt), C.byref(st))

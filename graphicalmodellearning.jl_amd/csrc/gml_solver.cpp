@@ -172,6 +172,11 @@ struct Solver {
     gml_stats stats{};
     hipStream_t st;
     const double *x0 = nullptr; // warm start (gml_learn_warm): the rows to start from, reference layout [R][P], host or device; NULL = zeros
+    // the caller's structure (gml_learn_structured): kind of every parameter slot of every local row, reference layout [R][ld_s] bytes, host or
+    // device; NULL = the reference's (field free, the rest penalised: k_kind alone)
+    const uint8_t *structure = nullptr;
+    int64_t ld_s = 0;
+    std::vector<int> nparam; // with a structure: parameters (slots not excluded) per row; a row without any is complete before the first pass
     int32_t *dColsRef = nullptr; // multi-body: column of every parameter slot of every local row (:94-104), built once (warm start, finish)
     int compact_skip = 0, compact_backoff = 0; // passes that do not try the column compaction after one that came out dense (run_pass)
     bool underflow = false; // the solve ended because a row's weights left the fixed-point range at an iterate (gml_learn: auto -> FP64)
@@ -335,6 +340,7 @@ struct Solver {
     int line_search();
     int finish(double *out, double *kkt_out, int iterations);
     int ref_cols();
+    int apply_structure();
     int load_x0();
     int iterate(double *out, double *kkt_out);
 };
@@ -482,6 +488,7 @@ int Solver::init() {
         HIPCHK(stg.h2d(dBest, inf.data(), sizeof(double) * Rp));
     }
     launch_kind(d, p->order, dNode, (int)Rp, kind, st);
+    if (structure) RCCHK(apply_structure());
 
     for (auto *v : {&f, &ft, &Fobj, &dd, &fn, &fnt, &l1t, &vref, &dref, &stepn}) v->assign((size_t)R, 0.0);
     for (auto *v : {&Z, &Zt, &alpha}) v->assign((size_t)R, 1.0);
@@ -1451,6 +1458,37 @@ int Solver::ref_cols() {
     return GML_OK;
 }
 
+// the caller's structure over the kinds k_kind wrote (host or device pointer; a host array was checked by gml_learn_structured)
+int Solver::apply_structure() {
+    RCCHK(ref_cols());
+    const uint8_t *src = structure;
+    int64_t lds = ld_s;
+    if (!gml_is_device_ptr(structure)) {
+        uint8_t *tmp = nullptr;
+        HIPCHK(A.get(&tmp, (size_t)R * P));
+        HIPCHK(hipMemcpy2DAsync(tmp, (size_t)P, structure, (size_t)ld_s, (size_t)P, (size_t)R, hipMemcpyHostToDevice, st));
+        src = tmp;
+        lds = P;
+    }
+    int *dcnt = nullptr;
+    unsigned long long *dbad = nullptr;
+    HIPCHK(A.get(&dcnt, (size_t)R));
+    HIPCHK(A.get(&dbad, 1));
+    HIPCHK(hipMemsetAsync(dcnt, 0, sizeof(int) * R, st));
+    HIPCHK(hipMemsetAsync(dbad, 0xFF, sizeof(unsigned long long), st));
+    launch_apply_structure(src, lds, R, P, Qp, dNode, d.cconst, dColsRef, kind, dcnt, dbad, st);
+    HIPCHK(hipGetLastError());
+    nparam.assign((size_t)R, 0);
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(nparam.data(), dcnt, sizeof(int) * R, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad != ~0ull)
+        return fail(GML_EINVAL, "structure: row %lld, slot %lld holds a value outside {0, 1, 2}", (long long)(bad / (unsigned long long)P),
+                    (long long)(bad % (unsigned long long)P));
+    return GML_OK;
+}
+
 // warm start: X <- the caller's rows (reference layout, host or device pointer)
 int Solver::load_x0() {
     RCCHK(ref_cols());
@@ -1465,19 +1503,27 @@ int Solver::load_x0() {
     HIPCHK(A.get(&dbad, 4));
     HIPCHK(hipMemsetAsync(dbad, 0, sizeof(int) * 4, st));
     launch_ref_to_internal(src, P, R, P, Qp, dNode, d.cconst, dColsRef, X, dbad, st);
+    if (structure) launch_mask_x0(kind, R, Qp, X, dbad + 1, st); // entries at excluded slots are ignored, whatever they hold
     HIPCHK(hipGetLastError());
     int bad[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(bad, dbad, sizeof bad, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (bad[0]) return fail(GML_EINVAL, "the starting point contains a non-finite value");
+    if (bad[structure ? 1 : 0]) return fail(GML_EINVAL, "the starting point contains a non-finite value");
     return GML_OK;
 }
 
 int Solver::iterate(double *out, double *kkt_out) {
     // first pass at X = 0: every energy is 0, the forward kernel skips its sweeps over the columns (the same bits without the GEMM:
     // 3.4 -> 1 ms of the headline solve's first pass); a warm start (gml_learn_warm) begins at the caller's rows instead
-    std::vector<int> rows_all((size_t)R);
-    for (int64_t r = 0; r < R; ++r) rows_all[r] = (int)r;
+    std::vector<int> rows_all;
+    for (int64_t r = 0; r < R; ++r) {
+        if (structure && nparam[r] == 0) { // no parameter: x = 0 is the solution; the row never reaches a pass or the selection
+            done[r] = 1;
+            kkt[r] = best[r] = 0.0;
+            continue;
+        }
+        rows_all.push_back((int)r);
+    }
     if (x0) RCCHK(load_x0());
     at_zero = x0 == nullptr;
     const int rc0 = run_pass(rows_all, X, G, true, false, at_x);
@@ -1540,12 +1586,15 @@ int Solver::iterate(double *out, double *kkt_out) {
     return finish(out, kkt_out, it);
 }
 
-// one solve of gml_learn_warm at precision prec, from x0 (NULL: zeros) to out / kkt_out; *st: its stats, the wall-clock columns filled
-int solve_once(gml_problem *p, int formulation, gml_opts o, int prec, double lambda, const double *x0, double t_start, double *out, double *kkt_out,
-               gml_stats *st, bool *underflow = nullptr) {
+// one solve of gml_learn_structured at precision prec, under `structure` (NULL: the reference's), from x0 (NULL: zeros) to out / kkt_out;
+// *st: its stats, the wall-clock columns filled
+int solve_once(gml_problem *p, int formulation, gml_opts o, int prec, double lambda, const uint8_t *structure, int64_t ld_s, const double *x0,
+               double t_start, double *out, double *kkt_out, gml_stats *st, bool *underflow = nullptr) {
     o.precision = prec;
     Solver s(p, formulation, o, lambda);
     s.x0 = x0;
+    s.structure = structure;
+    s.ld_s = ld_s;
     int rc = s.init();
     if (rc == GML_OK) rc = s.iterate(out, kkt_out);
     s.stats.t_total = gml_now_s() - t_start;
@@ -1566,6 +1615,11 @@ extern "C" int gml_learn(gml_problem *p, int formulation, double regularizer_c, 
 
 extern "C" int gml_learn_warm(gml_problem *p, int formulation, double regularizer_c, const gml_opts *opts_in, const double *x0, double *out,
                               double *kkt_out, gml_stats *stats_out) {
+    return gml_learn_structured(p, formulation, regularizer_c, opts_in, nullptr, 0, x0, out, kkt_out, stats_out);
+}
+
+extern "C" int gml_learn_structured(gml_problem *p, int formulation, double regularizer_c, const gml_opts *opts_in, const uint8_t *structure,
+                                    int64_t ld_s, const double *x0, double *out, double *kkt_out, gml_stats *stats_out) {
     if (!p || !out) return fail(GML_EINVAL, "NULL argument");
     if (formulation < 0 || formulation > 2) return fail(GML_EINVAL, "unknown formulation %d", formulation);
     if (formulation != GML_RISE && p->order != 2)
@@ -1579,12 +1633,21 @@ extern "C" int gml_learn_warm(gml_problem *p, int formulation, double regularize
     const bool asked_auto = asked == GML_PREC_AUTO;
     o.precision = gml_resolve_precision(p, asked, o.tol > 0 ? o.tol : 1e-9);
     if (o.precision < 0) return fail(GML_EINVAL, "unknown precision %d", asked);
+    if (structure) {
+        if (ld_s < p->P) return fail(GML_EINVAL, "structure: leading dimension %lld < %lld parameters per node", (long long)ld_s, (long long)p->P);
+        if (!gml_is_device_ptr(structure)) // (a device array is checked by the kernel that reads it: Solver::apply_structure)
+            for (int64_t r = 0; r < p->node1 - p->node0; ++r)
+                for (int64_t j = 0; j < p->P; ++j)
+                    if (structure[r * ld_s + j] > GML_PARAM_PENALISED)
+                        return fail(GML_EINVAL, "structure: row %lld, slot %lld holds %d, not one of GML_PARAM_EXCLUDED, _FREE, _PENALISED",
+                                    (long long)r, (long long)j, (int)structure[r * ld_s + j]);
+    }
     HIPCHK(hipSetDevice(p->device));
     const double t_start = gml_now_s();
     const double lambda = gml_lambda(regularizer_c, p->n, p->M);
     bool underflow = false;
     gml_stats st{};
-    int rc = solve_once(p, formulation, o, o.precision, lambda, x0, t_start, out, kkt_out, &st, &underflow);
+    int rc = solve_once(p, formulation, o, o.precision, lambda, structure, ld_s, x0, t_start, out, kkt_out, &st, &underflow);
     if (stats_out && (rc == GML_OK || rc == GML_ENOTCONV)) *stats_out = st;
     if (rc == GML_EUNSUPPORTED && underflow && asked_auto) {
         // `auto` is the reference's Float64 solve (:164-181) by other means: a histogram whose optimum lies where exp(-E) spreads over
@@ -1592,7 +1655,7 @@ extern "C" int gml_learn_warm(gml_problem *p, int formulation, double regularize
         // the reference returns a result there, so `auto` runs the solve again on the FP64-MFMA path.  A caller who named an
         // int8-limb precision keeps the error.
         const std::string first = gml_last_error();
-        rc = solve_once(p, formulation, o, GML_PREC_F64, lambda, x0, t_start, out, kkt_out, &st);
+        rc = solve_once(p, formulation, o, GML_PREC_F64, lambda, structure, ld_s, x0, t_start, out, kkt_out, &st);
         if (rc != GML_OK && rc != GML_ENOTCONV)
             return fail(rc, "%s; the FP64 path, which precision auto falls back to, then failed: %s", first.c_str(), std::string(gml_last_error()).c_str());
         st.polished = 1; // (finished on the FP64 path)
@@ -1609,7 +1672,7 @@ extern "C" int gml_learn_warm(gml_problem *p, int formulation, double regularize
             std::vector<double> out1(out, out + R * (size_t)p->P), kkt1;
             if (kkt_out) kkt1.assign(kkt_out, kkt_out + R);
             const gml_stats st1 = st; // (the first solve's, as *stats_out holds them)
-            const int rc2 = solve_once(p, formulation, o, GML_PREC_F64, lambda, x0, t_start, out, kkt_out, &st);
+            const int rc2 = solve_once(p, formulation, o, GML_PREC_F64, lambda, structure, ld_s, x0, t_start, out, kkt_out, &st);
             const bool usable = rc2 == GML_OK || rc2 == GML_ENOTCONV;
             const bool better = usable && (!stats_out || st.not_converged < st1.not_converged ||
                                            (st.not_converged == st1.not_converged && st.max_kkt < st1.max_kkt));

@@ -75,6 +75,46 @@ void launch_kind(const DevProblem &d, int order, const int *dnode, int R, uint8_
                        dnode, kind);
 }
 
+// The caller's structure (gml_learn_structured: S[r ld_s + j] = kind of parameter slot j of local row r, reference layout -- the
+// slot -> column map of k_ref_to_internal) over what k_kind wrote: a column k_kind calls a parameter takes the caller's kind, a
+// column it gave 0 stays 0 (no slot maps to one).  nparam[r] += the row's slots that are not excluded; *bad = the smallest
+// r P + j with a value outside {0, 1, 2} (initialised to ~0).
+__global__ __launch_bounds__(256) void k_apply_structure(const uint8_t *__restrict__ S, int64_t ld_s, int64_t P, int64_t Qp, const int *__restrict__ node,
+                                                         int64_t cconst, const int32_t *__restrict__ cols, uint8_t *__restrict__ kind,
+                                                         int *__restrict__ nparam, unsigned long long *__restrict__ bad) {
+    const int64_t r = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int u = node[r];
+    if (j >= P || u < 0) return;
+    const uint8_t s = S[r * ld_s + j];
+    if (s > 2) {
+        atomicMin(bad, (unsigned long long)(r * P + j));
+        return;
+    }
+    const int64_t c = cols ? cols[r * P + j] : (j == u ? cconst : j);
+    if (kind[r * Qp + c]) {
+        kind[r * Qp + c] = s;
+        if (s) atomicAdd(nparam + r, 1);
+    }
+}
+void launch_apply_structure(const uint8_t *S, int64_t ld_s, int64_t R, int64_t P, int64_t Qp, const int *dnode, int64_t cconst, const int32_t *cols,
+                            uint8_t *kind, int *nparam, unsigned long long *bad, hipStream_t st) {
+    if (R > 0)
+        hipLaunchKernelGGL(k_apply_structure, dim3((unsigned)((P + 255) / 256), (unsigned)R), dim3(256), 0, st, S, ld_s, P, Qp, dnode, cconst, cols, kind,
+                           nparam, bad);
+}
+
+// warm start under a structure: X = 0 wherever the row has no parameter (the caller's entries at excluded slots are ignored);
+// *bad |= 1 on a non-finite entry anywhere else
+__global__ __launch_bounds__(256) void k_mask_x0(const uint8_t *__restrict__ kind, int64_t Qp, double *__restrict__ X, int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.y * Qp + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if ((int64_t)blockIdx.x * 256 + threadIdx.x >= Qp) return;
+    if (!kind[i]) X[i] = 0.0;
+    else if (!isfinite(X[i])) atomicOr(bad, 1);
+}
+void launch_mask_x0(const uint8_t *kind, int64_t R, int64_t Qp, double *X, int *bad, hipStream_t st) {
+    if (R > 0) hipLaunchKernelGGL(k_mask_x0, dim3((unsigned)((Qp + 255) / 256), (unsigned)R), dim3(256), 0, st, kind, Qp, X, bad);
+}
+
 // G[r][:] *= scale[r] for the listed rows (logRISE: grad log Z = grad Z / Z, :279)
 __global__ __launch_bounds__(256) void k_scale_rows(const int *__restrict__ rows, const double *__restrict__ scale, int64_t Qp,
                                                     double *__restrict__ G) {

@@ -144,6 +144,159 @@ __global__ __launch_bounds__(256) void k_terms_unsym(TermPlan pl, const double *
     out[t] = rows[u * ld + slot];
 }
 
+// ------------------------------------------------------------------------------------------
+// Structures for gml_learn_structured (include/gml.h): one byte per (node, slot) in the layout of the rows, from solved rows
+// (k_struct_row / k_struct_sym / k_struct_sym3) or from a list of keys (k_struct_fill + k_struct_scatter).  Every (u, slot)
+// belongs to exactly one ascending key, so a thread per key writes its |S| bytes without races.  HBM-bound: 8 B read and 1 B
+// written per row entry.
+// ------------------------------------------------------------------------------------------
+struct StructRule {
+    int rule;
+    double thr;
+    uint8_t keep, drop, field;
+};
+
+// the decision for one key from its members' entries v[0..s) (ascending u).  MEAN: the operations of k_terms_sym -- add in ascending
+// u, then / s -- so that thresholding here and thresholding the assembled model agree bit for bit.  A NaN compares false.
+__device__ inline bool struct_keep(const StructRule &sr, const double *v, int s) {
+    if (sr.rule == GML_RULE_MEAN) {
+        double sum = 0.0;
+        for (int a = 0; a < s; ++a) sum += v[a];
+        return fabs(sum / (double)s) >= sr.thr;
+    }
+    bool all = true, any = false;
+    for (int a = 0; a < s; ++a) {
+        const bool k = fabs(v[a]) >= sr.thr;
+        all &= k;
+        any |= k;
+    }
+    return sr.rule == GML_RULE_ALL ? all : any;
+}
+
+// *kept += the workgroup's sum of add (every thread of the 256 calls it)
+__device__ inline void struct_count(int add, unsigned long long *kept) {
+    __shared__ int red[4];
+    for (int o = 32; o > 0; o >>= 1) add += __shfl_xor(add, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = add;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int tot = red[0] + red[1] + red[2] + red[3];
+        if (tot) atomicAdd(kept, (unsigned long long)tot);
+    }
+}
+
+// rule ROW: elementwise over the rows; one grid row per node, the slots along x (as k_terms_unsym)
+__global__ __launch_bounds__(256) void k_struct_row(TermPlan pl, const double *__restrict__ rows, int64_t ld, StructRule sr, uint8_t *__restrict__ S,
+                                                    int64_t ld_s, int64_t u0, unsigned long long *__restrict__ kept) {
+    const int64_t u = u0 + blockIdx.y, slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t P = pl.pairwise ? pl.n : pl.roff[pl.order + 1];
+    int add = 0;
+    if (slot < P) {
+        const bool field = pl.pairwise ? slot == u : slot == 0;
+        const bool keep = !field && fabs(rows[u * ld + slot]) >= sr.thr;
+        S[u * ld_s + slot] = field ? sr.field : keep ? sr.keep : sr.drop;
+        add = keep;
+    }
+    struct_count(add, kept);
+}
+
+// rules MEAN / ALL / ANY: one thread per ascending key, as k_terms_sym: its |S| member entries in, its |S| bytes out
+__global__ __launch_bounds__(256) void k_struct_sym(TermPlan pl, const double *__restrict__ rows, int64_t ld, StructRule sr, uint8_t *__restrict__ S,
+                                                    int64_t ld_s, int64_t tmax, unsigned long long *__restrict__ kept) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int add = 0;
+    if (t < tmax) {
+        int s = 1;
+        while (t >= pl.off[s + 1]) ++s;
+        int32_t c[MAXORD];
+        unrank_lex(t - pl.off[s], pl.n, s, c);
+        if (s == 1) {
+            S[(int64_t)c[0] * ld_s + row_slot(pl, c, 1, 0)] = sr.field;
+        } else {
+            int64_t slot[MAXORD];
+            double v[MAXORD];
+            for (int a = 0; a < s; ++a) {
+                slot[a] = row_slot(pl, c, s, a);
+                v[a] = rows[(int64_t)c[a] * ld + slot[a]];
+            }
+            const bool keep = struct_keep(sr, v, s);
+            for (int a = 0; a < s; ++a) S[(int64_t)c[a] * ld_s + slot[a]] = keep ? sr.keep : sr.drop;
+            add = keep ? s : 0;
+        }
+    }
+    struct_count(add, kept);
+}
+
+// the triples of an order-3 model, tiled as k_terms_sym3: row c's entries for (a, b) come in along b and go through LDS, and the
+// decisions return to row c the same way (a second tile), so that all three reads and all three writes are coalesced
+__global__ __launch_bounds__(256) void k_struct_sym3(int64_t n, int64_t roff3, const double *__restrict__ rows, int64_t ld, StructRule sr,
+                                                     uint8_t *__restrict__ S, int64_t ld_s, unsigned long long *__restrict__ kept) {
+    const int64_t a = blockIdx.z, b0 = (int64_t)blockIdx.y * TT, c0 = (int64_t)blockIdx.x * TT;
+    if (c0 + TT - 1 <= b0 || b0 + TT - 1 <= a) return; // no (b, c) of the tile has a < b < c
+    __shared__ double tile[TT][TT + 1];
+    __shared__ uint8_t dec[TT][TT + 4];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t m = n - 1;
+#pragma unroll
+    for (int i = 0; i < TT / 8; ++i) {
+        const int64_t c = c0 + ty + 8 * i, b = b0 + tx;
+        double v = 0.0;
+        if (c < n && b > a && b < c) v = rows[c * ld + roff3 + c2(m) - c2(m - a) + (b - a - 1)];
+        tile[ty + 8 * i][tx] = v;
+    }
+    __syncthreads();
+    int add = 0;
+#pragma unroll
+    for (int i = 0; i < TT / 8; ++i) {
+        const int64_t b = b0 + ty + 8 * i, c = c0 + tx;
+        uint8_t k = 0;
+        if (b > a && c > b && c < n) {
+            const int64_t sa = roff3 + c2(m) - c2(m - (b - 1)) + (c - b - 1); // row a: (b, c) renumbered b - 1, c - 1
+            const int64_t sb = roff3 + c2(m) - c2(m - a) + (c - 1 - a - 1);   // row b: a, c - 1
+            const double v[3] = {rows[a * ld + sa], rows[b * ld + sb], tile[tx][ty + 8 * i]};
+            const bool keep = struct_keep(sr, v, 3);
+            k = keep ? sr.keep : sr.drop;
+            S[a * ld_s + sa] = k;
+            S[b * ld_s + sb] = k;
+            add += keep ? 3 : 0;
+        }
+        dec[ty + 8 * i][tx] = k;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < TT / 8; ++i) {
+        const int64_t c = c0 + ty + 8 * i, b = b0 + tx;
+        if (c < n && b > a && b < c) S[c * ld_s + roff3 + c2(m) - c2(m - a) + (b - a - 1)] = dec[tx][ty + 8 * i];
+    }
+    struct_count(add, kept);
+}
+
+// from keys: every slot kind_other, the fields kind_field ...
+__global__ __launch_bounds__(256) void k_struct_fill(TermPlan pl, uint8_t other, uint8_t field, uint8_t *__restrict__ S, int64_t ld_s, int64_t u0) {
+    const int64_t u = u0 + blockIdx.y, slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t P = pl.pairwise ? pl.n : pl.roff[pl.order + 1];
+    if (slot >= P) return;
+    S[u * ld_s + slot] = (pl.pairwise ? slot == u : slot == 0) ? field : other;
+}
+
+// ... then every listed key (checked on the host: 1 .. order distinct spins of [0, n)) marks its members' slots; keys listed twice
+// write the same byte twice
+__global__ __launch_bounds__(256) void k_struct_scatter(TermPlan pl, const int32_t *__restrict__ keys, int stride, int64_t nterms, uint8_t listed,
+                                                        uint8_t *__restrict__ S, int64_t ld_s) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nterms) return;
+    int32_t c[MAXORD];
+    int s = 0;
+    for (int j = 0; j < stride; ++j) {
+        const int32_t v = keys[t * stride + j];
+        if (v < 0 || s >= MAXORD) continue;
+        int q = s++;
+        for (; q > 0 && c[q - 1] > v; --q) c[q] = c[q - 1]; // ascending
+        c[q] = v;
+    }
+    for (int a = 0; a < s; ++a) S[(int64_t)c[a] * ld_s + row_slot(pl, c, s, a)] = listed;
+}
+
 int make_plan(int64_t n, int order, TermPlan &pl) {
     if (n < 1 || order < 1) return fail(GML_EINVAL, "terms: n = %lld, order = %d", (long long)n, order);
     if (order > MAXORD) return fail(GML_EUNSUPPORTED, "terms: interaction orders above %d are not assembled on the device", MAXORD);
@@ -245,6 +398,161 @@ extern "C" int gml_terms_assemble(const double *rows, int64_t ld, int64_t n, int
     cleanup();
     if (rc != GML_OK) return rc;
     if (e != hipSuccess) return fail(GML_EHIP, "terms: %s", hipGetErrorString(e));
+    return GML_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// gml_structure_from_rows / gml_structure_from_keys (include/gml.h)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+bool kind_ok(int k) { return k == GML_PARAM_EXCLUDED || k == GML_PARAM_FREE || k == GML_PARAM_PENALISED; }
+
+// The device side of both builders: where the structure is written (the caller's device array with its own pitch, or a packed n x P
+// block that is copied into the caller's host array row by row, which leaves the bytes [P, ld_s) of every row alone), and the counter
+struct StructOut {
+    uint8_t *host = nullptr, *dev = nullptr, *own = nullptr;
+    int64_t ld_host = 0, ld_dev = 0, n = 0, P = 0;
+    unsigned long long *dkept = nullptr;
+    hipError_t open(uint8_t *structure, bool is_dev, int64_t ld_s, int64_t n_, int64_t P_, hipStream_t st) {
+        n = n_;
+        P = P_;
+        hipError_t e = gml::dev_malloc(&dkept, sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemsetAsync(dkept, 0, sizeof(unsigned long long), st);
+        if (e != hipSuccess) return e;
+        if (is_dev) {
+            dev = structure;
+            ld_dev = ld_s;
+            return hipSuccess;
+        }
+        host = structure;
+        ld_host = ld_s;
+        ld_dev = P;
+        e = gml::dev_malloc(&own, (size_t)n * (size_t)P);
+        dev = own;
+        return e;
+    }
+    hipError_t finish(int64_t *kept, hipStream_t st) { // copies back and waits
+        hipError_t e = hipSuccess;
+        unsigned long long k = 0;
+        if (host) e = hipMemcpy2DAsync(host, (size_t)ld_host, own, (size_t)P, (size_t)P, (size_t)n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && kept) e = hipMemcpyAsync(&k, dkept, sizeof k, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess && kept) *kept = (int64_t)k;
+        return e;
+    }
+    ~StructOut() {
+        if (own) (void)gml::dev_free(own);
+        if (dkept) (void)gml::dev_free(dkept);
+    }
+};
+
+} // namespace
+
+extern "C" int gml_structure_from_rows(const double *rows, int64_t ld, int64_t n, int order, int rule, double threshold, int kind_keep,
+                                       int kind_drop, int kind_field, int device, uint8_t *structure, int64_t ld_s, int64_t *kept) {
+    if (!rows || !structure) return fail(GML_EINVAL, "gml_structure_from_rows: NULL argument");
+    if (rule < GML_RULE_ROW || rule > GML_RULE_ANY) return fail(GML_EINVAL, "gml_structure_from_rows: unknown rule %d", rule);
+    if (!kind_ok(kind_keep) || !kind_ok(kind_drop) || !kind_ok(kind_field))
+        return fail(GML_EINVAL, "gml_structure_from_rows: kinds (%d, %d, %d) must be GML_PARAM_EXCLUDED, _FREE or _PENALISED", kind_keep, kind_drop, kind_field);
+    if (!(threshold >= 0.0) || !(threshold <= 1.7976931348623157e308))
+        return fail(GML_EINVAL, "gml_structure_from_rows: the threshold must be finite and >= 0");
+    TermPlan pl;
+    const int rc = make_plan(n, order, pl);
+    if (rc != GML_OK) return rc;
+    const int64_t P = pl.pairwise ? n : pl.roff[order + 1];
+    if (ld < P || ld_s < P)
+        return fail(GML_EINVAL, "gml_structure_from_rows: leading dimensions %lld / %lld < %lld parameters per node", (long long)ld, (long long)ld_s, (long long)P);
+    int rdev = device, sdev = device;
+    const bool rows_dev = gml_is_device_ptr(rows, &rdev), s_dev = gml_is_device_ptr(structure, &sdev);
+    if (rows_dev) device = rdev;
+    else if (s_dev) device = sdev;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = nullptr; // the device's null stream: ordered after whatever the caller queued there
+    double *drows = nullptr;
+    StructOut so;
+    hipError_t e = so.open(structure, s_dev, ld_s, n, P, st);
+    const double *src = rows;
+    if (e == hipSuccess && !rows_dev) {
+        const size_t bytes = sizeof(double) * (size_t)((n - 1) * ld + P);
+        e = gml::dev_malloc(&drows, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(drows, rows, bytes, hipMemcpyHostToDevice, st);
+        src = drows;
+    }
+    if (e == hipSuccess) {
+        const StructRule sr{rule, threshold, (uint8_t)kind_keep, (uint8_t)kind_drop, (uint8_t)kind_field};
+        if (rule == GML_RULE_ROW) {
+            for (int64_t u0 = 0; u0 < n; u0 += 65535) // (grid rows: at most 65 535 per launch)
+                hipLaunchKernelGGL(k_struct_row, dim3((unsigned)((P + 255) / 256), (unsigned)std::min<int64_t>(65535, n - u0)), dim3(256), 0, st, pl, src,
+                                   ld, sr, so.dev, so.ld_dev, u0, so.dkept);
+        } else if (order == 3 && n >= 3 && n <= 65535) { // fields and pairs by the generic kernel, the triples by the tiled one
+            const int64_t t2 = pl.off[3];
+            hipLaunchKernelGGL(k_struct_sym, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, st, pl, src, ld, sr, so.dev, so.ld_dev, t2, so.dkept);
+            const unsigned nt = (unsigned)((n + TT - 1) / TT);
+            hipLaunchKernelGGL(k_struct_sym3, dim3(nt, nt, (unsigned)n), dim3(256), 0, st, n, pl.roff[3], src, ld, sr, so.dev, so.ld_dev, so.dkept);
+        } else {
+            const int64_t T = pl.off[order + 1];
+            hipLaunchKernelGGL(k_struct_sym, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, pl, src, ld, sr, so.dev, so.ld_dev, T, so.dkept);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = so.finish(kept, st);
+    else (void)hipStreamSynchronize(st);
+    if (drows) (void)gml::dev_free(drows);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "gml_structure_from_rows: %s", hipGetErrorString(e));
+    return GML_OK;
+}
+
+extern "C" int gml_structure_from_keys(const int32_t *keys, int key_stride, int64_t nterms, int64_t n, int order, int kind_listed,
+                                       int kind_other, int kind_field, int device, uint8_t *structure, int64_t ld_s) {
+    if (!structure || (!keys && nterms > 0)) return fail(GML_EINVAL, "gml_structure_from_keys: NULL argument");
+    if (key_stride < 1 || nterms < 0) return fail(GML_EINVAL, "gml_structure_from_keys: key_stride = %d, nterms = %lld", key_stride, (long long)nterms);
+    if (!kind_ok(kind_listed) || !kind_ok(kind_other) || !kind_ok(kind_field))
+        return fail(GML_EINVAL, "gml_structure_from_keys: kinds (%d, %d, %d) must be GML_PARAM_EXCLUDED, _FREE or _PENALISED", kind_listed, kind_other, kind_field);
+    TermPlan pl;
+    const int rc = make_plan(n, order, pl);
+    if (rc != GML_OK) return rc;
+    const int64_t P = pl.pairwise ? n : pl.roff[order + 1];
+    if (ld_s < P) return fail(GML_EINVAL, "gml_structure_from_keys: leading dimension %lld < %lld parameters per node", (long long)ld_s, (long long)P);
+    for (int64_t t = 0; t < nterms; ++t) {
+        const int32_t *k = keys + t * key_stride;
+        int s = 0;
+        for (int j = 0; j < key_stride; ++j) {
+            if (k[j] == -1) continue;
+            if (k[j] < 0 || k[j] >= n) return fail(GML_EINVAL, "gml_structure_from_keys: term %lld names spin %d, outside [0, %lld)", (long long)t, (int)k[j], (long long)n);
+            for (int i = 0; i < j; ++i)
+                if (k[i] == k[j]) return fail(GML_EINVAL, "gml_structure_from_keys: term %lld names spin %d twice (a structure key is a set)", (long long)t, (int)k[j]);
+            ++s;
+        }
+        if (s > order) return fail(GML_EINVAL, "gml_structure_from_keys: term %lld has %d spins, the order is %d", (long long)t, s, order);
+        if (s == 0) return fail(GML_EINVAL, "gml_structure_from_keys: term %lld names no spin", (long long)t);
+    }
+    int sdev = device;
+    const bool s_dev = gml_is_device_ptr(structure, &sdev);
+    if (s_dev) device = sdev;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    int32_t *dkeys = nullptr;
+    StructOut so;
+    hipError_t e = so.open(structure, s_dev, ld_s, n, P, st);
+    if (e == hipSuccess && nterms > 0) {
+        const size_t bytes = sizeof(int32_t) * (size_t)nterms * (size_t)key_stride;
+        e = gml::dev_malloc(&dkeys, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(dkeys, keys, bytes, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) {
+        for (int64_t u0 = 0; u0 < n; u0 += 65535)
+            hipLaunchKernelGGL(k_struct_fill, dim3((unsigned)((P + 255) / 256), (unsigned)std::min<int64_t>(65535, n - u0)), dim3(256), 0, st, pl,
+                               (uint8_t)kind_other, (uint8_t)kind_field, so.dev, so.ld_dev, u0);
+        if (nterms > 0)
+            hipLaunchKernelGGL(k_struct_scatter, dim3((unsigned)((nterms + 255) / 256)), dim3(256), 0, st, pl, dkeys, key_stride, nterms, (uint8_t)kind_listed,
+                               so.dev, so.ld_dev);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = so.finish(nullptr, st);
+    else (void)hipStreamSynchronize(st);
+    if (dkeys) (void)gml::dev_free(dkeys);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "gml_structure_from_keys: %s", hipGetErrorString(e));
     return GML_OK;
 }
 

@@ -61,6 +61,15 @@ class HIP(GMLMethod):
     devices    several GPUs of this node from this one process: the library shards the nodes over them (one host thread
                per GPU, gml_multi_*); what the Julia wrapper's HIP(devices = 0:7) binds
     distributed  shard the nodes over torch.distributed ranks (one process per GPU) and gather the rows (RCCL)
+    structure  n x P uint8 array for the whole problem: the kind of every parameter slot of every node in the layout of the solved
+               rows -- EXCLUDED (fixed at 0), FREE (estimated, not penalised) or PENALISED (gml_learn_structured; built by
+               structure_from_keys / structure_from_rows).  node_range and distributed=True take their rows of it; not with devices
+    refit      threshold tau of the two-stage estimator: the l1 solve as usual, then a second, unpenalised solve on its support --
+               the couplings of magnitude >= tau are FREE, the others EXCLUDED, the fields FREE -- warm-started from the first; removes
+               the shrinkage of the l1 estimate.  One process, one GPU, all nodes.  stats["refit"] holds the second solve's
+               statistics, stats["support"] the number of kept couplings (per-node entries)
+    refit_rule how a coupling is judged: "mean" (the symmetrised value; the default with formulation.symmetrization), "row" (each
+               node's own entry; the default without), "all" or "any" (every / some member's entry)
     """
     tol: float = 1e-9
     precision: str = "auto"
@@ -74,6 +83,9 @@ class HIP(GMLMethod):
     verbose: int = 0
     distributed: bool = False
     node_range: Optional[Tuple[int, int]] = None
+    structure: Any = None
+    refit: Optional[float] = None
+    refit_rule: Optional[str] = None
     stats: dict = field(default_factory=dict, repr=False, compare=False)
 
 

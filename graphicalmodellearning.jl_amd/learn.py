@@ -28,18 +28,29 @@ def _node_partition(n, world, rank):
 DICT_TERMS_MAX = 1 << 17
 
 
-def _local_solve_hip(samples, formulation, method, order, node_range, device, terms=None, packed=None, matrix=None):
+def _local_solve_hip(samples, formulation, method, order, node_range, device, terms=None, packed=None, matrix=None, structure=None,
+                     refit=None):
     """rows of the local node range through libgml_hip: (out, kkt, stats).  terms = True / False (all nodes, multiRISE): the
     model's weight array instead of the rows -- solve and assembly in one library call, the rows never leave the device.
     packed = (sign_bits, counts or None, K): the handle is built from the packed form (gml_problem_create_packed) and `samples`
     is not looked at -- the ranks of a distributed run, which receive the bits from rank 0.  matrix = True / False (all nodes,
-    pairwise): the n x n result of gml_learn_matrix, symmetrised on the device (True)."""
+    pairwise): the n x n result of gml_learn_matrix, symmetrised on the device (True).  structure: the rows of HIP.structure for
+    this node range (gml_learn_structured).  refit = (tau, rule) (all nodes): the rows of a second solve on the same handle, whose
+    structure is the first solve's support (structure_from_rows: kept FREE, dropped EXCLUDED, fields FREE) and which starts from the
+    first solve's rows; st is the first solve's, st["refit"] the second's, st["support"] the number of kept entries."""
     src = {"packed": packed} if packed is not None else {"samples": samples}
     with _lib.Problem(order=order, node_range=node_range, device=device, **src) as prob:
-        out, kkt, st = prob.learn(_form_name(formulation), formulation.regularizer, tol=method.tol,
-                                  max_iter=method.max_iter, precision=method.precision,
-                                  max_working=method.max_working, max_add=method.max_add, verbose=method.verbose,
-                                  hess_samples=method.hess_samples, polish=method.polish, terms=terms, matrix=matrix)
+        opts = dict(tol=method.tol, max_iter=method.max_iter, precision=method.precision, max_working=method.max_working,
+                    max_add=method.max_add, verbose=method.verbose, hess_samples=method.hess_samples, polish=method.polish)
+        out, kkt, st = prob.learn(_form_name(formulation), formulation.regularizer, terms=terms, matrix=matrix, structure=structure, **opts)
+        if refit is not None:
+            tau, rule = refit
+            support, kept = _lib.structure_from_rows(out, prob.n, order, tau, rule=rule, keep=_lib.FREE, drop=_lib.EXCLUDED,
+                                                     field=_lib.FREE, device=device)
+            if structure is not None:  # a slot the caller excluded stays excluded
+                support = np.where(structure == _lib.EXCLUDED, np.uint8(_lib.EXCLUDED), support)
+            out, kkt, st2 = prob.learn(_form_name(formulation), formulation.regularizer, structure=support, x0=out, **opts)
+            st["refit"], st["support"] = st2, kept
     return out, kkt, st
 
 
@@ -159,6 +170,15 @@ def learn(samples, formulation=None, method=None):
         raise ValueError("HIP: devices (all nodes over several GPUs from this process) excludes distributed, node_range and device")
     if method.distributed and method.node_range is not None:
         raise ValueError("HIP: distributed=True derives the node range from the rank; node_range must not be given")
+    if method.structure is not None and method.devices is not None:
+        raise ValueError("HIP: structure is not carried over devices= (gml_multi); use distributed=True or one GPU")
+    if method.refit is not None:
+        if method.devices is not None or method.distributed or method.node_range is not None:
+            raise ValueError("HIP: refit thresholds the rows of ALL nodes: one process, one GPU, no node_range")
+        if not (float(method.refit) >= 0.0) or not np.isfinite(method.refit):
+            raise ValueError(f"HIP: refit is the threshold of the support, finite and >= 0, not {method.refit!r}")
+    if method.refit_rule is not None and method.refit_rule not in _lib.RULES:
+        raise ValueError(f"HIP: unknown refit_rule {method.refit_rule!r} (use 'mean', 'row', 'all' or 'any')")
     if method.precision not in _lib.PRECISIONS:
         raise ValueError(f"HIP: unknown precision {method.precision!r} (use 'auto', 'i8x', 'i8w' or 'f64')")
     order = int(formulation.interaction_order) if isinstance(formulation, multiRISE) else 2
@@ -190,13 +210,21 @@ def learn(samples, formulation=None, method=None):
     # (module attributes, looked up per call: the CPU-only tests of this layer substitute the oracle for both steps)
     solve, assemble, symmetrize = _local_solve_hip, _assemble_terms_hip, _symmetrize_hip
     multi = isinstance(formulation, multiRISE)
+    extra = {}  # (only what is asked for: a substituted solver keeps its signature)
+    if method.structure is not None:
+        whole = np.asarray(method.structure)
+        if whole.dtype != np.uint8 or whole.ndim != 2 or whole.shape[0] != n:
+            raise _lib.GMLError(_lib.GML_EINVAL, f"HIP: structure is {whole.dtype} {whole.shape}, the problem takes uint8 ({n}, P)")
+        extra["structure"] = np.ascontiguousarray(whole[node_range[0]:node_range[1]])
+    if method.refit is not None:
+        extra["refit"] = (float(method.refit), method.refit_rule or ("mean" if formulation.symmetrization else "row"))
     if multi and not (method.distributed and world > 1) and method.devices is None and tuple(node_range) != (0, n):
         raise ValueError("multiRISE assembles a FactorGraph from the rows of ALL nodes (:129-151): solve node shards with "
                          "Problem.learn and hand the gathered rows to _lib.terms_assemble")
     # one process, one GPU, all nodes: solve + assembly in one library call (gml_learn_terms)
     one_call = solve is _PRODUCT_SOLVE and method.devices is None and not (method.distributed and world > 1)
-    fused = multi and one_call
-    fused_sym = (not multi) and one_call and bool(formulation.symmetrization) and tuple(node_range) == (0, n)  # (gml_learn_matrix)
+    fused = multi and one_call and not extra  # (structured and refit solves return rows: assembled below)
+    fused_sym = (not multi) and one_call and not extra and bool(formulation.symmetrization) and tuple(node_range) == (0, n)  # (gml_learn_matrix)
     try:
         if method.devices is not None:
             out, kkt, st = _local_solve_multi(samples, formulation, method, order)
@@ -207,9 +235,9 @@ def learn(samples, formulation=None, method=None):
         elif fused_sym:
             out, kkt, st = solve(samples, formulation, method, order, node_range, device, matrix=True)
         elif packed is not None:
-            out, kkt, st = solve(None, formulation, method, order, node_range, device, packed=packed)[:3]
+            out, kkt, st = solve(None, formulation, method, order, node_range, device, packed=packed, **extra)[:3]
         else:
-            out, kkt, st = solve(samples, formulation, method, order, node_range, device)[:3]
+            out, kkt, st = solve(samples, formulation, method, order, node_range, device, **extra)[:3]
     except _lib.GMLConvergenceError as e:  # the reference's @assert (:180): keep what the solver reached
         method.stats.clear()
         method.stats.update(getattr(e, "stats", {}) or {})

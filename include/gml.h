@@ -465,6 +465,64 @@ int gml_learn_warm(gml_problem *p, int formulation, double regularizer_c, const 
                    double *kkt, gml_stats *stats);
 
 /*
+ * gml_learn_structured -- gml_learn_warm with the STRUCTURE of every row stated by the caller (beyond the reference, whose only
+ * structure is "the field free, every other parameter penalised", :118, :171): which parameters exist, and which of those carry the
+ * l1 penalty.  For refits on a learned support (threshold the l1 solution, re-estimate the kept couplings without the shrinkage), for
+ * known graphs (a lattice, a chip's couplers, no external fields) and for partly known models (known couplings free, the rest
+ * l1-screened).
+ *   structure[r*ld_s + j]   kind of parameter slot j of local row r (node node0 + r), in the layout of `out` (pairwise: slot j = spin
+ *                           j, slot u = the field; multi-body: the order of gml_multi_keys, slot 0 = the field); ld_s >= P.  Host
+ *                           pointer, or device pointer on the handle's GPU (detected, as x0 and out are).  NULL = gml_learn_warm.
+ * Any kind is allowed in any slot, the field included (every field GML_PARAM_EXCLUDED: a zero-field model).  x0, out, kkt and stats
+ * as in gml_learn_warm; entries of x0 at excluded slots are ignored (taken as 0), out is exactly 0.0 at every excluded slot, kkt[r] is
+ * the max |pseudo-gradient| over the slots that are not excluded.  A row without any parameter is complete before the first
+ * iteration: x = 0, kkt = 0, converged.  Sparse structures are cheap: the passes sweep only the non-zero columns of a node tile.
+ * GML_EINVAL: ld_s < P, or a value outside {0, 1, 2} (the text names row and slot; a host array is checked before any device work, a
+ * device array by a kernel in front of the solve).
+ */
+#define GML_PARAM_EXCLUDED 0   /* fixed at 0: not a parameter of this row               */
+#define GML_PARAM_FREE 1       /* estimated, not penalised (as the field is today)      */
+#define GML_PARAM_PENALISED 2  /* estimated, lambda |x| (as every coupling is today)    */
+int gml_learn_structured(gml_problem *p, int formulation, double regularizer_c, const gml_opts *opts, const uint8_t *structure,
+                         int64_t ld_s, const double *x0, double *out, double *kkt, gml_stats *stats);
+
+/*
+ * Structures for gml_learn_structured, built on the device in the (node, slot) layout of the rows (closed-form for multi-body models:
+ * no key table).  `structure` is n x P bytes with leading dimension ld_s >= P, host or device pointer; bytes [P, ld_s) of a row are
+ * not written.  `device`: where the kernels run when no argument is a device pointer.
+ *
+ *   gml_structure_from_rows   from solved rows: rows = the n x P solved rows of all nodes (leading dimension ld, host or device
+ *                             pointer; for order 2 also the symmetrised n x n matrix).  A non-field slot (u, S') -- the key S = {u} + S'
+ *                             -- gets kind_keep or kind_drop by `rule`:
+ *                               GML_RULE_ROW    keep iff |rows[u][slot]| >= threshold
+ *                               GML_RULE_MEAN   keep iff |mean over v in S of row v's entry for (v, S \ {v})| >= threshold; the mean is
+ *                                               formed as gml_terms_assemble forms it (added in ascending v, then / |S|), so the decision
+ *                                               is bit-consistent with thresholding the assembled model
+ *                               GML_RULE_ALL    keep iff every member's entry is >= threshold in magnitude ("AND")
+ *                               GML_RULE_ANY    keep iff some member's entry is ("OR")
+ *                             (MEAN, ALL, ANY decide per key: all |S| slots of a key get the same kind.)  A NaN compares false: dropped.
+ *                             Field slots get kind_field and are never thresholded.  kept (host, may be NULL): the exact number of
+ *                             non-field (u, slot) entries that got kind_keep.
+ *                             GML_EINVAL (before any HIP call): NULL rows / structure, order < 1, an unknown rule or kind, threshold
+ *                             negative or not finite, ld < P or ld_s < P.
+ *   gml_structure_from_keys   from a list of terms: keys as everywhere in this header (host, term t = keys[t*key_stride ..
+ *                             +key_stride), 0-based, -1 = unused slot).  Every slot starts as kind_other, the fields as kind_field;
+ *                             a key S with 2 <= |S| <= order sets, for every member u, row u's slot of (u, S \ {u}) to kind_listed; a
+ *                             key of one spin sets that spin's field to kind_listed.  Duplicate keys are harmless, nterms = 0 is allowed.
+ *                             GML_EINVAL (before any HIP call): NULL structure (or keys with nterms > 0), key_stride < 1, an unknown
+ *                             kind, ld_s < P, a spin outside [0, n), a spin named twice in one key (a structure key is a set), a key
+ *                             of more than `order` spins or of none; the text names the term.
+ */
+#define GML_RULE_ROW 0
+#define GML_RULE_MEAN 1
+#define GML_RULE_ALL 2
+#define GML_RULE_ANY 3
+int gml_structure_from_rows(const double *rows, int64_t ld, int64_t n, int order, int rule, double threshold, int kind_keep,
+                            int kind_drop, int kind_field, int device, uint8_t *structure, int64_t ld_s, int64_t *kept);
+int gml_structure_from_keys(const int32_t *keys, int key_stride, int64_t nterms, int64_t n, int order, int kind_listed, int kind_other,
+                            int kind_field, int device, uint8_t *structure, int64_t ld_s);
+
+/*
  * Result assembly of multiRISE on the device -- replaces the tail of learn(samples, ::multiRISE, ...): the per-node
  * `reconstruction[inter] = ...` (:129-132), the symmetrisation (group by sorted key, `mean`: :135-149) and the Dict that
  * FactorGraph(order, n, :spin, reconstruction) (:151, models.jl:8-17) is built from.  The terms of the learned model are returned
