@@ -1,5 +1,6 @@
 // Int8-limb path, part 4: working-set Hessians on the int8 matrix cores (overview: gml_i8.h).
 #include "gml_i8.h"
+#include "gml_i8_hw.h"
 #include "gml_solver.h"
 #include <algorithm>
 #include <string>
@@ -24,17 +25,7 @@ namespace gml {
 // the compact index <-> samples [512 cb kstride, +512)): spread over the whole histogram, whose rows are usually
 // sorted, instead of its first rows.
 // ------------------------------------------------------------------------------------------
-constexpr int HL = 2;
-
-// bits by which a row's weights are shifted down so that its largest fits the 15 bits of two balanced digits.  exp forms: mm = the row's largest |V| in the unit
-// of the planes, as its last pass recorded it.  RPLE: the passes do not record it, and need not: tau comes from the bound 2 w_max,
-// which the weights of a well-classified configuration reach, and h = 4 w sig (1 - sig) <= w_max = half the planes' range (2^30).
-__device__ __forceinline__ int hw_shift(unsigned mm, int form) {
-    if (form == 2) return 16;
-    int sh = 0;
-    while ((mm >> sh) + 1u > 32639u) ++sh; // (the dither adds less than one unit after the shift; 32 639 = two balanced digits' largest)
-    return sh;
-}
+// (HL = 2 digit planes; hw_shift, hw_dither, hw_clip, hw_digits: gml_i8_hw.h)
 
 // Hessian weights of the active rows as limb planes over the compact index, in the sample order of the bit images
 // (vq_pos within each 64): RISE / logRISE h = |V|; RPLE h = 2a(1 - a/(2w)), a = |V|
@@ -53,7 +44,6 @@ __global__ __launch_bounds__(256) void k_make_hw(const int8_t *__restrict__ Vq, 
     if (mt[r] == 0) return;
     const int u = rowcol[r], vs = vslot[r];
     const int sh = hw_shift(mmax[vs], form);
-    const unsigned dmask = (1u << sh) - 1u;
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; // (piece, dword)
     const int64_t jc = (t >> 4) * 64;                            // compact index of the piece's first sample
     const int p4 = (int)(t & 15) * 4;                            // byte position within the piece
@@ -83,12 +73,11 @@ __global__ __launch_bounds__(256) void k_make_hw(const int8_t *__restrict__ Vq, 
                 const double hv = wk > 0 ? rint(2.0 * a * (1.0 - a / (2.0 * wk)) / tt) : 0.0;
                 mag = hv > 0.0 ? (hv < 4294967040.0 ? (int)(unsigned)hv : -1) : 0; // (as unsigned below: up to 2 |V| < 2^32)
             }
-            // 15 bits below the row's largest, unbiased: a fixed function of (node, sample) in [0, 2^sh) is added before the shift
-            const unsigned dth = ((((unsigned)(kc + s0 + e) * 0x9E3779B1u) ^ ((unsigned)u * 0x85EBCA6Bu)) >> 9) & dmask;
-            unsigned long long hq = ((unsigned long long)(unsigned)mag + dth) >> sh;
-            unsigned h2 = hq > 32639ull ? 32639u : (unsigned)hq; // (balanced digits: the high one must stay <= 127)
+            const unsigned dth = hw_dither(u, kc + s0 + e, sh);
+            const unsigned h2 = hw_clip(mag, dth, sh);
             sm += h2;
-            const int lo = (int)((h2 + 128u) & 255u) - 128, hi = ((int)h2 - lo) >> 8;
+            int lo, hi;
+            hw_digits(h2, lo, hi);
             dgw[0] |= ((unsigned)lo & 0xffu) << (8 * e);
             dgw[1] |= ((unsigned)hi & 0xffu) << (8 * e);
         }
@@ -457,7 +446,7 @@ static void launch_hess_blk(const I8Ws *w, const DevProblem &d, const int *dF, c
     // and sized on R they would get a few long workgroups each)
     int ns = 1;
     int64_t kc = 0;
-    hess_split(Kh, (int64_t)(nrows_active > 0 ? nrows_active : 1) * nblk, 4096, &ns, &kc);
+    hess_split(Kh, (int64_t)(nrows_active > 0 ? nrows_active : 1) * nblk, g_tune[GML_TUNE_HESS_BLK_WGS] > 0 ? (int)g_tune[GML_TUNE_HESS_BLK_WGS] : 4096, &ns, &kc);
     constexpr int shmem = 3 * ((64 + 32 * BT) * 64 + HL * 512) + 2 * (4 + 2 * BT) * 1024;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hess_bits_blk<BT>), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
     const int64_t nv = R + tl.n;

@@ -642,6 +642,250 @@ extern "C" int gml_test_hessian_blocks(gml_problem *p, int formulation, int prec
     return GML_OK;
 }
 
+// Test hook (not part of include/gml.h): the Hessian call of one solver iteration on caller-given blocks -- the flow of
+// gml_test_hessian_blocks (device_pass at theta, rescaled re-runs included, then i8_hessian) with what run_group (gml_solver.cpp) can
+// hand the call and that hook cannot: a ragged size per row (mtV[r] tiles of 32, 0 = the row is skipped), blocks at caller-given
+// offsets, and optionally the preconditioner tiles of matrix-free rows.
+//   cols [nrows][cap]: every row's list, parameter indices in the reference's order; all cap entries are translated and uploaded (the
+//                      kernels read the first 32 mtV[r] of them), so the padding is the caller's
+//   ntiles > 0: T in {64, 128}; tcols [ntiles][T] the tiles' lists, parameters of row wrow[t] in the reference's order; vm [ntiles]
+//               (entries in use: uploaded with the control block as run_group lays it out -- hoffV | mtV | vm | wrow | hflag -- the Hessian
+//               kernels do not read it), wrow [ntiles], hflag [nrows] (rows whose weights are needed)
+//   mtV, hoffV [nrows + ntiles]: tiles of 32 and offset of every block in H (tiles: mtV = T / 32); htotal: elements of H
+// precision f64: the FP64 pass, then launch_hess_f64 on its V (the Newton matrices of the FP64 phase); no tiles.
+// H [htotal] is cleared first: what no kernel writes stays zero.  tests/test_gpu_i8_hess_exact.py.
+extern "C" int gml_test_hessian_run(gml_problem *p, int formulation, int precision, int64_t nrows, const int64_t *nodes, const double *theta,
+                                    int64_t ld, const int32_t *cols, int cap, int64_t Kh, int64_t kstride, int T, int ntiles,
+                                    const int32_t *tcols, const int32_t *vm, const int32_t *wrow, const int32_t *hflag, const int32_t *mtV,
+                                    const int64_t *hoffV, int64_t htotal, double *H) {
+    if (!p || !nodes || !theta || !cols || !mtV || !hoffV || !H || nrows <= 0 || nrows > 65535 || htotal <= 0) return fail(GML_EINVAL, "bad argument");
+    if (formulation < 0 || formulation > 2) return fail(GML_EINVAL, "unknown formulation %d", formulation);
+    const bool f64 = precision == GML_PREC_F64;
+    if (!f64 && !gml_is_i8(precision)) return fail(GML_EINVAL, "precision f64, i8x or i8w");
+    if (cap <= 0 || cap % 32 || cap > 512) return fail(GML_EINVAL, "cap: a multiple of 32 up to 512");
+    if (ntiles < 0 || (ntiles > 0 && (f64 || (T != 64 && T != 128) || !tcols || !vm || !wrow || !hflag))) return fail(GML_EINVAL, "bad tile set");
+    const int64_t Qp = p->d.Qp, P = p->P, Kp = p->d.Kp, NV = nrows + ntiles;
+    // the sub-sample stays inside the histogram: block cb of the compact index is the samples [512 cb kstride, +512)
+    if (Kh <= 0 || Kh % 512 || kstride < 1 || ((Kh / 512 - 1) * kstride + 1) * 512 > Kp) return fail(GML_EINVAL, "bad sub-sample");
+    for (int64_t b = 0; b < NV; ++b) {
+        const int64_t m = b < nrows ? mtV[b] : T / 32;
+        if (mtV[b] != m || m < 0 || m * 32 > (b < nrows ? cap : T) || hoffV[b] < 0 || hoffV[b] + m * 32 * m * 32 > htotal)
+            return fail(GML_EINVAL, "block %lld outside H or its list", (long long)b);
+    }
+    for (int64_t r = 0; r < nrows; ++r)
+        if (nodes[r] < 0 || nodes[r] >= p->n) return fail(GML_EINVAL, "node id out of range");
+    HIPCHK(hipSetDevice(p->device));
+    std::vector<NodeLayout> lay;
+    std::vector<double> Th((size_t)nrows * Qp, 0.0), Gi((size_t)nrows * Qp), fv((size_t)nrows);
+    if (to_internal(p, nrows, nodes, lay, theta, ld, Th.data()) >= 0) return fail(GML_EINVAL, "a row contains a non-finite value");
+    std::vector<int> F((size_t)nrows * cap + (size_t)ntiles * T, 0);
+    for (int64_t r = 0; r < nrows; ++r)
+        for (int a = 0; a < cap; ++a) {
+            const int32_t j = cols[r * cap + a];
+            if (j < 0 || j >= P) return fail(GML_EINVAL, "working-set entry out of range");
+            F[(size_t)r * cap + a] = lay[r].cols[j];
+        }
+    for (int64_t t = 0; t < ntiles; ++t) {
+        if (wrow[t] < 0 || wrow[t] >= nrows || vm[t] < 1 || vm[t] > T) return fail(GML_EINVAL, "bad tile %lld", (long long)t);
+        for (int a = 0; a < T; ++a) {
+            const int32_t j = tcols[t * T + a];
+            if (j < 0 || j >= P) return fail(GML_EINVAL, "tile entry out of range");
+            F[(size_t)nrows * cap + (size_t)t * T + a] = lay[wrow[t]].cols[j];
+        }
+    }
+    int rc = device_pass(p, nrows, nodes, Th.data(), formulation, precision, true, op_compact(), false, fv.data(), Gi.data());
+    if (rc) return rc;
+    hipStream_t st = p->st;
+    // rowcol [R] | vslot [R] (slot = row) | mtV [NV] | vm [ntiles] | wrow [ntiles] | hflag [R]
+    std::vector<int> ctl((size_t)(3 * nrows + NV + 2 * ntiles), 0);
+    for (int64_t r = 0; r < nrows; ++r) {
+        ctl[r] = (int)nodes[r];
+        ctl[nrows + r] = (int)r;
+        if (ntiles > 0) ctl[2 * nrows + NV + 2 * ntiles + r] = hflag[r];
+    }
+    for (int64_t b = 0; b < NV; ++b) ctl[2 * nrows + b] = mtV[b];
+    for (int64_t t = 0; t < ntiles; ++t) {
+        ctl[2 * nrows + NV + t] = vm[t];
+        ctl[2 * nrows + NV + ntiles + t] = wrow[t];
+    }
+    std::vector<long long> hoff(hoffV, hoffV + NV);
+    std::vector<int> hmt(mtV, mtV + NV);
+    int *dCtl = nullptr, *dF = nullptr;
+    long long *dHoff = nullptr;
+    double *dH = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(st);
+        for (void *q : {(void *)dCtl, (void *)dF, (void *)dHoff, (void *)dH})
+            if (q) (void)dev_free_synced(q);
+    };
+    hipError_t e = dev_malloc(&dCtl, sizeof(int) * ctl.size());
+    if (e == hipSuccess) e = dev_malloc(&dF, sizeof(int) * F.size());
+    if (e == hipSuccess) e = dev_malloc(&dHoff, sizeof(long long) * hoff.size());
+    if (e == hipSuccess) e = dev_malloc(&dH, sizeof(double) * (size_t)htotal);
+    if (e == hipSuccess) e = hipMemcpyAsync(dCtl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dF, F.data(), sizeof(int) * F.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dHoff, hoff.data(), sizeof(long long) * hoff.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dH, 0, sizeof(double) * (size_t)htotal, st);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(GML_EHIP, "gml_test_hessian_run: %s", hipGetErrorString(e));
+    }
+    const int *dMtV = dCtl + 2 * nrows;
+    std::string err;
+    if (f64) {
+        launch_hess_f64(p->d, p->dV, dCtl, dF, dMtV, dHoff, (int)nrows, cap, formulation, Kh, kstride, dH, st);
+        if (hipGetLastError() != hipSuccess) rc = GML_EHIP;
+    } else {
+        gml::HessTiles tl;
+        if (ntiles > 0) {
+            tl.n = ntiles;
+            tl.T = T;
+            tl.F = dF + (size_t)nrows * cap;
+            tl.wrow = dMtV + NV + ntiles;
+            tl.hflag = dMtV + NV + 2 * ntiles;
+        }
+        rc = gml::i8_hessian(p->i8ws, p->d, dCtl, dCtl + nrows, dF, dMtV, hmt.data(), dHoff, htotal, (int)nrows, cap, formulation, Kh, kstride, dH, st, &err,
+                             ntiles > 0 ? &tl : nullptr);
+    }
+    if (rc == GML_OK) {
+        e = hipMemcpyAsync(H, dH, sizeof(double) * (size_t)htotal, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = GML_EHIP;
+    }
+    cleanup();
+    if (rc) return fail(rc, "%s", err.empty() ? "gml_test_hessian_run failed" : err.c_str());
+    return GML_OK;
+}
+
+// Test hook (not part of include/gml.h): one Hessian-vector product two ways.  device_pass runs the objective pass (RISE or logRISE, i8x
+// or i8w; rescaled re-runs included) over the rows (nodes, theta), which leaves their curvature weights in the slots 0 .. nrows.  Then,
+// for the nloc product rows -- row i multiplies the weights of slot vslot[i] with the direction vec[i] -- as newton_cg_group's hv_pass
+// (gml_solver.cpp) builds the two calls:
+//   hs: i8_hv_sparse over the caller's lists: row i's nw[i] entries at FV[t0[i] T ..] (parameters of node nodes[vslot[i]] in the
+//       reference's order), wcap >= every nw, the plan (kchunk, kpart);
+//   hg: the GEMM pass with hv = 2, lf = 2 and the same (kchunk, kpart), slot i <- (row i, node, vmap = vslot[i]).
+// kchunk = 0: the plan i8_split_plan makes for all configurations.  The entry-by-entry form runs FIRST: the GEMM pass rewrites Tq, Uq
+// and the product scalars (sc[1]), none of which the entry-by-entry form reads, and neither touches the V planes or sc[0]; run first, it is
+// also seen to need nothing the GEMM pass leaves behind.
+// hs, hg [nloc][Qp] in the internal column order, both filled with `fill` beforehand (the entry-by-entry form writes the listed entries
+// only); colmap [nloc][P]: the internal column of every parameter.  tests/test_gpu_hv_sparse_direct.py.
+extern "C" int gml_test_hv_sparse(gml_problem *p, int formulation, int precision, int64_t nrows, const int64_t *nodes, const double *theta,
+                                  int64_t ld, int64_t nloc, const int32_t *vslot, const double *vec, const int32_t *FV, const int64_t *t0,
+                                  const int32_t *nw, int T, int64_t wcap, int64_t kchunk, int64_t kpart, double fill, double *hs, double *hg,
+                                  int32_t *colmap) {
+    if (!p || !nodes || !theta || !vslot || !vec || !FV || !t0 || !nw || !hs || !hg || !colmap || nrows <= 0 || nloc <= 0 || nloc > 65535 || T <= 0)
+        return fail(GML_EINVAL, "bad argument");
+    if (formulation != GML_RISE && formulation != GML_LOGRISE) return fail(GML_EINVAL, "an exp form");
+    if (!gml_is_i8(precision)) return fail(GML_EINVAL, "an int8-limb precision");
+    const int64_t Qp = p->d.Qp, P = p->P, np = gml_round_up(nloc, 32);
+    if (wcap < 1 || wcap > 65536 || kchunk < 0 || kchunk % 256 || kpart < 0 || kpart % 256 || (kchunk > 0 && (kpart == 0 || kpart > kchunk)))
+        return fail(GML_EINVAL, "bad wcap or plan");
+    for (int64_t r = 0; r < nrows; ++r)
+        if (nodes[r] < 0 || nodes[r] >= p->n) return fail(GML_EINVAL, "node id out of range");
+    int64_t fvlen = 0;
+    std::vector<int64_t> lnodes((size_t)nloc);
+    for (int64_t i = 0; i < nloc; ++i) {
+        if (vslot[i] < 0 || vslot[i] >= nrows || nw[i] < 1 || nw[i] > wcap || t0[i] < 0) return fail(GML_EINVAL, "bad product row %lld", (long long)i);
+        fvlen = std::max<int64_t>(fvlen, t0[i] * T + nw[i]);
+        lnodes[i] = nodes[vslot[i]];
+    }
+    HIPCHK(hipSetDevice(p->device));
+    int rc = gml_ensure_ws(p, std::max(nrows, nloc));
+    if (rc) return rc;
+    std::vector<NodeLayout> lay, llay;
+    std::vector<double> Th((size_t)nrows * Qp, 0.0), Gi((size_t)nrows * Qp), fv((size_t)nrows), Pv((size_t)nloc * Qp, 0.0);
+    if (to_internal(p, nrows, nodes, lay, theta, ld, Th.data()) >= 0) return fail(GML_EINVAL, "a row contains a non-finite value");
+    if (to_internal(p, nloc, lnodes.data(), llay, vec, ld, Pv.data()) >= 0) return fail(GML_EINVAL, "a direction contains a non-finite value");
+    std::vector<int> Fi((size_t)fvlen, 0);
+    for (int64_t i = 0; i < nloc; ++i) {
+        std::memcpy(colmap + i * P, llay[i].cols.data(), sizeof(int32_t) * P);
+        for (int a = 0; a < nw[i]; ++a) {
+            const int32_t j = FV[t0[i] * T + a];
+            if (j < 0 || j >= P) return fail(GML_EINVAL, "list entry out of range");
+            Fi[(size_t)(t0[i] * T + a)] = llay[i].cols[j];
+        }
+    }
+    rc = device_pass(p, nrows, nodes, Th.data(), formulation, precision, true, op_compact(), false, fv.data(), Gi.data());
+    if (rc) return rc;
+    hipStream_t st = p->st;
+    if (kchunk == 0) {
+        int nsplit = 0;
+        gml::i8_split_plan(p->d, (int)(np / 32), 1, &kchunk, &kpart, &nsplit);
+    }
+    // rows | node | vslot [np each] | groups [np / 32 + 4] | nw [nloc]   (hv_pass's control block, then the lists' sizes)
+    std::vector<int> ctl((size_t)(3 * np + np / 32 + 4 + nloc), -1);
+    for (int64_t a = 0; a < np; ++a) {
+        ctl[a] = a < nloc ? (int)a : 0;
+        ctl[np + a] = a < nloc ? (int)lnodes[a] : -1;
+        ctl[2 * np + a] = a < nloc ? vslot[a] : 0;
+    }
+    for (int64_t g = 0; g < np / 32; ++g) ctl[3 * np + g] = (int)g;
+    for (int64_t i = 0; i < nloc; ++i) ctl[3 * np + np / 32 + 4 + i] = nw[i];
+    std::vector<long long> t0l(t0, t0 + nloc);
+    std::vector<double> init((size_t)nloc * Qp, fill);
+    const size_t bufb = gml::i8_hv_sparse_bytes(p->d, (int)nloc, wcap);
+    int *dCtl = nullptr, *dFV = nullptr;
+    long long *dT0 = nullptr;
+    double *dP = nullptr, *dHs = nullptr, *dHg = nullptr;
+    char *dBuf = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(st);
+        for (void *q : {(void *)dCtl, (void *)dFV, (void *)dT0, (void *)dP, (void *)dHs, (void *)dHg, (void *)dBuf})
+            if (q) (void)dev_free_synced(q);
+    };
+    const size_t rowb = sizeof(double) * (size_t)np * Qp; // (the GEMM pass writes the rows of whole slot tiles)
+    hipError_t e = dev_malloc(&dCtl, sizeof(int) * ctl.size());
+    if (e == hipSuccess) e = dev_malloc(&dFV, sizeof(int) * Fi.size());
+    if (e == hipSuccess) e = dev_malloc(&dT0, sizeof(long long) * t0l.size());
+    if (e == hipSuccess) e = dev_malloc(&dP, rowb);
+    if (e == hipSuccess) e = dev_malloc(&dHs, rowb);
+    if (e == hipSuccess) e = dev_malloc(&dHg, rowb);
+    if (e == hipSuccess) e = dev_malloc(&dBuf, bufb);
+    if (e == hipSuccess) e = hipMemcpyAsync(dCtl, ctl.data(), sizeof(int) * ctl.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dFV, Fi.data(), sizeof(int) * Fi.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dT0, t0l.data(), sizeof(long long) * t0l.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dP, 0, rowb, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dP, Pv.data(), sizeof(double) * (size_t)nloc * Qp, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dHs, 0, rowb, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dHg, 0, rowb, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dHs, init.data(), sizeof(double) * (size_t)nloc * Qp, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dHg, init.data(), sizeof(double) * (size_t)nloc * Qp, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(GML_EHIP, "gml_test_hv_sparse: %s", hipGetErrorString(e));
+    }
+    std::string err;
+    rc = gml::i8_hv_sparse(p->i8ws, p->d, (int)nloc, dCtl, dCtl + np, dCtl + 2 * np, dT0, dCtl + 3 * np + np / 32 + 4, dFV, T, wcap, dP, dHs, kchunk,
+                           kpart, dBuf, st, &err);
+    if (rc == GML_OK) {
+        gml::I8Pass a{}; // (slots [0, np); no F)
+        a.theta = dP;
+        a.srow = dCtl;
+        a.rowcol = dCtl + np;
+        a.vmap = dCtl + 2 * np;
+        a.groups = dCtl + 3 * np;
+        a.ngroups = (int)(np / 32);
+        a.slot1 = (int)np;
+        a.form = formulation;
+        a.want_grad = true;
+        a.G = dHg;
+        a.hv = 2;
+        a.lf = 2;
+        a.kchunk = kchunk;
+        a.kpart = kpart;
+        rc = gml::i8_pass(&p->i8ws, p->d, p->ws_rows, a, st, nullptr, &err);
+    }
+    if (rc == GML_OK) {
+        e = hipMemcpyAsync(hs, dHs, sizeof(double) * (size_t)nloc * Qp, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(hg, dHg, sizeof(double) * (size_t)nloc * Qp, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = GML_EHIP;
+    }
+    cleanup();
+    if (rc) return fail(rc, "%s", err.empty() ? "gml_test_hv_sparse failed" : err.c_str());
+    return GML_OK;
+}
+
 // Test hook (not part of include/gml.h): ONE objective pass over caller-given rows in a form the public entry points do not choose, and
 // optionally one Hessian-vector pass after it, with no rescaled re-runs.  Host pointers; rows in the reference's parameter order.
 //   kn [11]: coarse, lf (0 / 3 / 4 / 5), want_grad, compact, zero_theta, then the product pass: hv (0 = none, 1, 2), its lf (2 .. 5),

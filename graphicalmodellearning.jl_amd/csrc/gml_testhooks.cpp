@@ -1,6 +1,7 @@
 // libgml_hip: test and experiment hooks (not part of include/gml.h).
 #include "gml_internal.h"
 #include "gml_i8.h"
+#include "gml_i8_hw.h"
 #include "gml_solver.h"
 #include "gml_pack.h"
 
@@ -284,5 +285,31 @@ extern "C" int gml_test_i8_pack_state(gml_problem *p, int64_t xc_tile, int64_t *
     HIPCHK(get(6, sc.qconst, sizeof(long long) * ns));
     HIPCHK(get(7, sc.qconst2, sizeof(long long) * ns));
     HIPCHK(get(8, sc.qpair, sizeof(long long) * ns));
+    return GML_OK;
+}
+
+// Test hook (not part of include/gml.h): what the last working-set Hessian call (i8_hessian, gml_i8_hess.hip) left in the handle's int8
+// workspace.  Read only: synchronises the handle's stream and copies; launches nothing.
+//   dims [8]: 0 pitch of the weight planes (= Kp; 0: no Hessian call yet), 1 rows the planes are sized for (a multiple of 32), 2 elements
+//             H64 is sized for, 3 Qp, 4 Kp, 5 bytes of Mb (0: not built), 6 Qfp, 7 digit planes of a weight (HL)
+//   out [3] or NULL (only the sizes); a NULL entry is skipped:
+//             0 Hq int8 [dims 1 / 32][HL][32][dims 0], the digits of the weights over the compact index, vq_pos order within each 64;
+//             1 H64 int64 [dims 2]: the integer blocks T_ij of the last call at its offsets, then (from its htotal on) the rows' sums hS --
+//               beyond them whatever larger earlier calls left;  2 Mb uint32 [Qp][Kp / 64][2]
+extern "C" int gml_test_i8_hess_state(gml_problem *p, int64_t *dims, void **out) {
+    if (!p || !dims) return fail(GML_EINVAL, "bad argument");
+    const gml::I8Ws *w = static_cast<const gml::I8Ws *>(p->i8ws);
+    const DevProblem &d = p->d;
+    const int64_t v[8] = {w ? w->hKh : 0, w ? w->hrows : 0, w ? w->hcap_elems : 0, d.Qp, d.Kp, w && w->Mb ? d.Qp * (d.Kp / 8) : 0, d.Qfp, gml::HL};
+    std::copy(v, v + 8, dims);
+    if (!out || !w) return GML_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->st));
+    auto get = [&](int i, const void *src, size_t bytes) -> hipError_t {
+        return out[i] && src && bytes ? hipMemcpy(out[i], src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIPCHK(get(0, w->Hq, (size_t)v[1] * gml::HL * v[0]));
+    HIPCHK(get(1, w->H64, sizeof(long long) * (size_t)v[2]));
+    HIPCHK(get(2, w->Mb, (size_t)v[5]));
     return GML_OK;
 }
