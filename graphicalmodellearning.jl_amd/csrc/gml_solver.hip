@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_select(const int *__restrict__ rows, co
             l1 += l * fabs(xc);
             pg = pseudo_grad(xc, g[c], l);
             const double a = fabs(pg);
-            worst = fmax(worst, a);
+            worst = fmax(worst, a == a ? a : INFINITY); // (fmax passes over a NaN; a NaN gradient is an infinite residual, never a best iterate)
             if (xc != 0.0 || k == 1) {
                 ++nsupp;
                 worstW = fmax(worstW, a);
@@ -232,7 +232,6 @@ __global__ __launch_bounds__(256) void k_select(const int *__restrict__ rows, co
     worstW = block_max(worstW, red);
     nsupp = block_sum_i(nsupp, redi);
     nviol = block_sum_i(nviol, redi);
-    if (!(worst == worst)) worst = INFINITY; // NaN
     const bool addv = !(worstW > worst * 0.999999 && worstW > 0 && nsupp > 1);
     // The Hessian blocks and the Cholesky work on whole 32-entry tiles: admit as many violators as fill the working set up
     // to a multiple of 32 rather than one entry into the next tile (support 1 + 64 violators = 65 entries would be three

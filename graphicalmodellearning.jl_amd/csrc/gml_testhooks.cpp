@@ -313,3 +313,344 @@ extern "C" int gml_test_i8_hess_state(gml_problem *p, int64_t *dims, void **out)
     HIPCHK(get(2, w->Mb, (size_t)v[5]));
     return GML_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Test hooks of the solver's device kernels (gml_solver.hip) and of the direction phase around the batched solve: host arrays in, the
+// launchers as gml_solver.cpp calls them, the results back out.  Nothing stays on the device between calls: the state the kernels
+// carry from one iteration to the next goes in and out as arguments.  tests/test_gpu_solver_kernels.py, tests/test_gpu_newton_solve.py.
+// ------------------------------------------------------------------------------------------
+namespace {
+// device arrays of one hook call: freed when the call returns, whichever way
+struct DevArrays {
+    std::vector<void *> ptrs;
+    ~DevArrays() {
+        for (void *q : ptrs) (void)dev_free(q);
+    }
+    // n elements on the device, copied from h (NULL: zeroed)
+    template <typename T> hipError_t up(T **d, const T *h, size_t n) {
+        const size_t bytes = sizeof(T) * std::max<size_t>(n, 1);
+        const hipError_t e = dev_malloc(d, bytes);
+        if (e != hipSuccess) return e;
+        ptrs.push_back(*d);
+        return h && n ? hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice) : hipMemset(*d, 0, bytes);
+    }
+    template <typename T> static hipError_t down(T *h, const T *d, size_t n) {
+        return h && n ? hipMemcpy(h, d, sizeof(T) * n, hipMemcpyDeviceToHost) : hipSuccess;
+    }
+};
+bool rows_in_range(const int *rows, int nrows, int R) {
+    for (int a = 0; a < nrows; ++a)
+        if (rows[a] < 0 || rows[a] >= R) return false;
+    return true;
+}
+} // namespace
+
+// k_select on the listed rows (any subset of the R rows, in any order).  PG, Xbest [R][Qp], F, gF, pgF [R][capP], out [R] (SelectOut), best
+// [R] are read from the caller and written back: what the kernel leaves alone keeps the caller's values.
+extern "C" int gml_test_solver_select(int R, int64_t Qp, int nrows, const int *rows, const double *X, const double *G, const unsigned char *kind,
+                                      double lambda, int max_add, int capW, int capP, double viol_frac, double *PG, int *F, double *gF, double *pgF,
+                                      void *out, double *best, double *Xbest, int device) {
+    if (R <= 0 || Qp <= 0 || nrows < 0 || capP <= 0 || capW > capP || !rows_in_range(rows, nrows, R)) return fail(GML_EINVAL, "bad argument");
+    HIPCHK(hipSetDevice(device));
+    DevArrays A;
+    const size_t nd = (size_t)R * Qp, nc = (size_t)R * capP;
+    int *dRows = nullptr, *dF = nullptr;
+    double *dX = nullptr, *dG = nullptr, *dPG = nullptr, *dgF = nullptr, *dpgF = nullptr, *dBest = nullptr, *dXbest = nullptr;
+    uint8_t *dKind = nullptr;
+    SelectOut *dOut = nullptr;
+    HIPCHK(A.up(&dRows, rows, (size_t)nrows));
+    HIPCHK(A.up(&dX, X, nd));
+    HIPCHK(A.up(&dG, G, nd));
+    HIPCHK(A.up(&dKind, kind, nd));
+    HIPCHK(A.up(&dPG, PG, nd));
+    HIPCHK(A.up(&dF, F, nc));
+    HIPCHK(A.up(&dgF, gF, nc));
+    HIPCHK(A.up(&dpgF, pgF, nc));
+    HIPCHK(A.up(&dOut, static_cast<const SelectOut *>(out), (size_t)R));
+    HIPCHK(A.up(&dBest, best, (size_t)R));
+    HIPCHK(A.up(&dXbest, Xbest, nd));
+    launch_select(dRows, nrows, dX, dG, dKind, Qp, lambda, max_add, capW, capP, viol_frac, dPG, dF, dgF, dpgF, dOut, dBest, dXbest, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(A.down(PG, dPG, nd));
+    HIPCHK(A.down(F, dF, nc));
+    HIPCHK(A.down(gF, dgF, nc));
+    HIPCHK(A.down(pgF, dpgF, nc));
+    HIPCHK(A.down(static_cast<SelectOut *>(out), dOut, (size_t)R));
+    HIPCHK(A.down(best, dBest, (size_t)R));
+    HIPCHK(A.down(Xbest, dXbest, nd));
+    return GML_OK;
+}
+
+// k_trial on the listed rows, then (Gt != NULL) k_back with that gradient at the trial points.  Xt [R][Qp], out [R] (TrialOut) and stepn
+// [R] (or NULL: the kernel gets NULL) are read from the caller and written back.
+extern "C" int gml_test_solver_trial(int R, int64_t Qp, int nrows, const int *rows, const double *X, const double *D, const double *PG,
+                                     const unsigned char *kind, double lambda, const double *alpha, double *Xt, void *out, double *stepn,
+                                     const double *Gt, int device) {
+    if (R <= 0 || Qp <= 0 || nrows < 0 || !rows_in_range(rows, nrows, R)) return fail(GML_EINVAL, "bad argument");
+    HIPCHK(hipSetDevice(device));
+    DevArrays A;
+    const size_t nd = (size_t)R * Qp;
+    int *dRows = nullptr;
+    double *dX = nullptr, *dD = nullptr, *dPG = nullptr, *dAl = nullptr, *dXt = nullptr, *dStepn = nullptr, *dGt = nullptr;
+    uint8_t *dKind = nullptr;
+    TrialOut *dOut = nullptr;
+    HIPCHK(A.up(&dRows, rows, (size_t)nrows));
+    HIPCHK(A.up(&dX, X, nd));
+    HIPCHK(A.up(&dD, D, nd));
+    HIPCHK(A.up(&dPG, PG, nd));
+    HIPCHK(A.up(&dKind, kind, nd));
+    HIPCHK(A.up(&dAl, alpha, (size_t)R));
+    HIPCHK(A.up(&dXt, Xt, nd));
+    HIPCHK(A.up(&dOut, static_cast<const TrialOut *>(out), (size_t)R));
+    if (stepn) HIPCHK(A.up(&dStepn, stepn, (size_t)R));
+    if (Gt) HIPCHK(A.up(&dGt, Gt, nd));
+    launch_trial(dRows, nrows, dX, dD, dPG, dKind, Qp, lambda, dAl, dXt, dOut, dStepn, nullptr);
+    if (Gt) launch_back(dRows, nrows, dX, dXt, dGt, dKind, Qp, lambda, dOut, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(A.down(Xt, dXt, nd));
+    HIPCHK(A.down(static_cast<TrialOut *>(out), dOut, (size_t)R));
+    if (stepn) HIPCHK(A.down(stepn, dStepn, (size_t)R));
+    return GML_OK;
+}
+
+// The direction phase of the Cholesky rows as Solver::newton_blocks runs it: (secant != 0) launch_secant on the listed rows with the
+// caller's apply_above, launch_newton_solve over all R rows -- per-row s1, the rank-one term s2, (pairs != 0) the rows' secant pairs for
+// the blocks it corrects itself, (faces != 0) the orthant faces from F / X / kind with `share` and `rounds`, (fix != NULL) entries fixed
+// from the start -- and launch_scatter_dir on the listed rows.  blocks [R][cap][cap]: row r's leading m_r x m_r, packed to pitch 32 mt
+// as test_newton_solve does; on return the lower triangle the solve read (k_secant's correction included), mirrored.  The secant state
+// (Fprev, xprev, gprev [R][cap], mprev, npairs [R], S, Y [2][R][cap]), dsol [R][cap], Sdiag [R] and D [R][Qp] are read from the caller and
+// written back.  A row that is not listed takes m = 0.
+extern "C" int gml_test_newton_direction(int R, int cap, int64_t Qp, int nrows, const int *rows, const int *m, const int *F, double *blocks,
+                                         const double *gF, const double *pgF, const double *s1, double s2, const double *X,
+                                         const unsigned char *kind, int secant, int apply_above, int pairs, const double *ynoise, int *Fprev,
+                                         int *mprev, double *xprev, double *gprev, double *S, double *Y, int *npairs, int faces, double share,
+                                         int rounds, const unsigned char *fix, const double *dfix, double *dsol, double *Sdiag, double *D,
+                                         int device) {
+    if (R <= 0 || cap <= 0 || cap > 512 || Qp <= 0 || nrows < 0 || !rows_in_range(rows, nrows, R)) return fail(GML_EINVAL, "bad argument");
+    std::vector<long long> hoff((size_t)R + 1, 0);
+    std::vector<int> mt((size_t)R), listed((size_t)R, 0);
+    for (int a = 0; a < nrows; ++a) listed[rows[a]] = 1;
+    int maxm = 1;
+    for (int r = 0; r < R; ++r) {
+        if (m[r] < 0 || m[r] > cap || (m[r] > 0 && !listed[r])) return fail(GML_EINVAL, "bad block size");
+        for (int a = 0; a < m[r]; ++a)
+            if (F[(size_t)r * cap + a] < 0 || F[(size_t)r * cap + a] >= Qp) return fail(GML_EINVAL, "working-set column out of range");
+        mt[r] = (m[r] + 31) / 32;
+        hoff[r + 1] = hoff[r] + (long long)mt[r] * 32 * mt[r] * 32;
+        maxm = std::max(maxm, m[r]);
+    }
+    std::vector<double> H((size_t)std::max<long long>(hoff[R], 1), 0.0);
+    for (int r = 0; r < R; ++r) {
+        const int hp = 32 * mt[r];
+        for (int i = 0; i < m[r]; ++i)
+            for (int j = 0; j < m[r]; ++j) H[(size_t)hoff[r] + (size_t)i * hp + j] = blocks[((size_t)r * cap + i) * cap + j];
+        for (int i = m[r]; i < hp; ++i) H[(size_t)hoff[r] + (size_t)i * hp + i] = 1.0; // padding: identity
+    }
+    HIPCHK(hipSetDevice(device));
+    DevArrays A;
+    const size_t nd = (size_t)R * Qp, nc = (size_t)R * cap;
+    int *dRows = nullptr, *dM = nullptr, *dMt = nullptr, *dF = nullptr, *dFprev = nullptr, *dMprev = nullptr, *dNp = nullptr;
+    long long *dHoff = nullptr;
+    double *dH = nullptr, *dgF = nullptr, *dpgF = nullptr, *dS1 = nullptr, *dX = nullptr, *dYn = nullptr, *dXprev = nullptr, *dGprev = nullptr,
+           *dS = nullptr, *dY = nullptr, *dDfix = nullptr, *dSol = nullptr, *dSd = nullptr, *dD = nullptr;
+    uint8_t *dKind = nullptr, *dFix = nullptr;
+    HIPCHK(A.up(&dRows, rows, (size_t)nrows));
+    HIPCHK(A.up(&dM, m, (size_t)R));
+    HIPCHK(A.up(&dMt, mt.data(), (size_t)R));
+    HIPCHK(A.up(&dHoff, hoff.data(), (size_t)R + 1));
+    HIPCHK(A.up(&dF, F, nc));
+    HIPCHK(A.up(&dH, H.data(), H.size()));
+    HIPCHK(A.up(&dgF, gF, nc));
+    HIPCHK(A.up(&dpgF, pgF, nc));
+    HIPCHK(A.up(&dS1, s1, (size_t)R));
+    HIPCHK(A.up(&dX, X, nd));
+    HIPCHK(A.up(&dKind, kind, nd));
+    HIPCHK(A.up(&dYn, ynoise, (size_t)R));
+    HIPCHK(A.up(&dFprev, Fprev, nc));
+    HIPCHK(A.up(&dMprev, mprev, (size_t)R));
+    HIPCHK(A.up(&dXprev, xprev, nc));
+    HIPCHK(A.up(&dGprev, gprev, nc));
+    HIPCHK(A.up(&dS, S, 2 * nc));
+    HIPCHK(A.up(&dY, Y, 2 * nc));
+    HIPCHK(A.up(&dNp, npairs, (size_t)R));
+    HIPCHK(A.up(&dSol, dsol, nc));
+    HIPCHK(A.up(&dSd, Sdiag, (size_t)R));
+    HIPCHK(A.up(&dD, D, nd));
+    if (fix) {
+        HIPCHK(A.up(&dFix, fix, nc));
+        HIPCHK(A.up(&dDfix, dfix, nc));
+    }
+    if (secant)
+        launch_secant(dRows, nrows, dF, dM, cap, dX, Qp, dgF, dH, dHoff, dMt, dS1, s2, dYn, dFprev, dMprev, dXprev, dGprev, dS, dY, dNp, (int64_t)nc,
+                      apply_above, nullptr);
+    NewtonFaces nf;
+    nf.F = dF;
+    nf.X = dX;
+    nf.kind = dKind;
+    nf.Qp = Qp;
+    nf.share = share;
+    nf.rounds = rounds;
+    const SecantPairs sp{dS, dY, dNp, (int64_t)nc};
+    launch_newton_solve(dH, dHoff, dMt, dM, dS1, s2, dgF, dpgF, R, cap, dSol, dSd, nullptr, maxm, faces ? &nf : nullptr, dFix, dDfix,
+                        pairs ? &sp : nullptr);
+    launch_scatter_dir(dRows, nrows, dF, dSol, dM, cap, Qp, dD, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(A.down(H.data(), dH, H.size()));
+    for (int r = 0; r < R; ++r) {
+        const int hp = 32 * mt[r];
+        for (int i = 0; i < m[r]; ++i)
+            for (int j = 0; j <= i; ++j)
+                blocks[((size_t)r * cap + i) * cap + j] = blocks[((size_t)r * cap + j) * cap + i] = H[(size_t)hoff[r] + (size_t)i * hp + j];
+    }
+    HIPCHK(A.down(Fprev, dFprev, nc));
+    HIPCHK(A.down(mprev, dMprev, (size_t)R));
+    HIPCHK(A.down(xprev, dXprev, nc));
+    HIPCHK(A.down(gprev, dGprev, nc));
+    HIPCHK(A.down(S, dS, 2 * nc));
+    HIPCHK(A.down(Y, dY, 2 * nc));
+    HIPCHK(A.down(npairs, dNp, (size_t)R));
+    HIPCHK(A.down(dsol, dSol, nc));
+    HIPCHK(A.down(Sdiag, dSd, (size_t)R));
+    HIPCHK(A.down(D, dD, nd));
+    return GML_OK;
+}
+
+// The matrix-free Newton-CG of the listed rows in the order of Solver::newton_cg_group, with the device operator's raw product
+// (sum_k h_k x_k x_k^T) v replaced by Hd[r] v, formed here on the host between the launches (Hd [R][Qp][Qp], symmetric):
+// k_cg_tiles, the tiles' blocks gathered from Hd at FV, the tile inverses, k_pcg_init / tile_apply / k_pcg_dir(first), nsteps x {product,
+// k_pcg_step, tile_apply, k_pcg_dir}; then, with faces != 0, k_pcg_faces, the product of D, k_pcg_resid, tile_apply, k_pcg_dir(first) and
+// nsteps2 more steps.  The per-step kernels run on the listed rows with live[r] != 0; k_cg_tiles, k_pcg_init and k_pcg_faces on all
+// listed rows.  FV, gV [ntiles T] (ntiles = sum over the listed rows, in list order, of ceil(|W| / T); the caller sizes them for
+// R ceil(Qp / T) tiles), D, Rv, Zv, Pv [R][Qp], Wm [R][Qp], cg [R] (CgState), fout [R] (FaceOut) are read from the caller and written back.
+extern "C" int gml_test_pcg(int R, int64_t Qp, int T, int nrows, const int *rows, const double *Hd, const double *s1, double s2, const double *X,
+                            const double *PG, const double *G, const unsigned char *kind, const int *live, int nsteps, int faces, int nsteps2,
+                            int *FV, double *gV, double *D, double *Rv, double *Zv, double *Pv, unsigned char *Wm, void *cg, void *fout,
+                            int device) {
+    if ((T != 64 && T != 128) || R <= 0 || Qp <= 0 || nrows <= 0 || !rows_in_range(rows, nrows, R)) return fail(GML_EINVAL, "bad argument");
+    const size_t nd = (size_t)R * Qp, tcap = (size_t)R * ((Qp + T - 1) / T);
+    std::vector<int> nW((size_t)R, 0), vm, wrow, liverows;
+    std::vector<long long> t0((size_t)R, 0), hoff;
+    for (int a = 0; a < nrows; ++a) {
+        const int r = rows[a];
+        int w = 0;
+        for (int64_t c = 0; c < Qp; ++c) w += kind[r * Qp + c] && (X[r * Qp + c] != 0.0 || PG[r * Qp + c] != 0.0);
+        nW[r] = w;
+        t0[r] = (long long)vm.size();
+        for (int b = 0; b < w; b += T) {
+            vm.push_back(std::min(T, w - b));
+            wrow.push_back(r);
+            hoff.push_back((long long)hoff.size() * T * T);
+        }
+        if (live[r]) liverows.push_back(r);
+    }
+    const size_t ntiles = vm.size();
+    if (ntiles == 0 || ntiles > tcap) return fail(GML_EINVAL, "no working set");
+    HIPCHK(hipSetDevice(device));
+    DevArrays A;
+    int *dRows = nullptr, *dLiveRows = nullptr, *dLive = nullptr, *dFV = nullptr, *dVm = nullptr, *dWrow = nullptr, *dNw = nullptr;
+    long long *dT0 = nullptr, *dHoff = nullptr;
+    double *dS1 = nullptr, *dX = nullptr, *dPG = nullptr, *dG = nullptr, *dgV = nullptr, *dHt = nullptr, *dD = nullptr, *dRv = nullptr, *dZv = nullptr,
+           *dPv = nullptr, *dHp = nullptr;
+    uint8_t *dKind = nullptr, *dWm = nullptr;
+    CgState *dCg = nullptr;
+    FaceOut *dFo = nullptr;
+    HIPCHK(A.up(&dRows, rows, (size_t)nrows));
+    HIPCHK(A.up(&dLiveRows, liverows.data(), liverows.size()));
+    HIPCHK(A.up(&dLive, live, (size_t)R));
+    HIPCHK(A.up(&dFV, FV, tcap * T));
+    HIPCHK(A.up(&dgV, gV, tcap * T));
+    HIPCHK(A.up(&dVm, vm.data(), ntiles));
+    HIPCHK(A.up(&dWrow, wrow.data(), ntiles));
+    HIPCHK(A.up(&dNw, nW.data(), (size_t)R));
+    HIPCHK(A.up(&dT0, t0.data(), (size_t)R));
+    HIPCHK(A.up(&dHoff, hoff.data(), ntiles));
+    HIPCHK(A.up(&dS1, s1, (size_t)R));
+    HIPCHK(A.up(&dX, X, nd));
+    HIPCHK(A.up(&dPG, PG, nd));
+    HIPCHK(A.up(&dG, G, nd));
+    HIPCHK(A.up(&dKind, kind, nd));
+    HIPCHK(A.up(&dD, D, nd));
+    HIPCHK(A.up(&dRv, Rv, nd));
+    HIPCHK(A.up(&dZv, Zv, nd));
+    HIPCHK(A.up(&dPv, Pv, nd));
+    HIPCHK(A.up(&dWm, Wm, nd));
+    HIPCHK(A.up(&dHp, static_cast<const double *>(nullptr), nd));
+    HIPCHK(A.up(&dCg, static_cast<const CgState *>(cg), (size_t)R));
+    HIPCHK(A.up(&dFo, static_cast<const FaceOut *>(fout), (size_t)R));
+    launch_cg_tiles(dRows, nrows, dX, dPG, dG, dKind, Qp, T, dT0, dFV, dgV, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<int> fv(ntiles * T);
+    HIPCHK(A.down(fv.data(), dFV, fv.size()));
+    std::vector<double> Ht(ntiles * T * T, 0.0);
+    for (size_t t = 0; t < ntiles; ++t) {
+        const double *Hr = Hd + (size_t)wrow[t] * Qp * Qp;
+        for (int i = 0; i < vm[t]; ++i)
+            for (int j = 0; j < vm[t]; ++j) {
+                const int ci = fv[t * T + i], cj = fv[t * T + j];
+                if (ci < 0 || ci >= Qp || cj < 0 || cj >= Qp) return fail(GML_EHIP, "k_cg_tiles listed a column out of range");
+                Ht[(t * T + i) * T + j] = Hr[(size_t)ci * Qp + cj];
+            }
+    }
+    HIPCHK(A.up(&dHt, Ht.data(), Ht.size()));
+    const WList wl{dFV, dT0, dNw, T};
+    const int nl = (int)liverows.size();
+    std::vector<double> hv(nd), hp(nd, 0.0);
+    // Hp[r] = Hd[r] v[r] for the given rows (long double accumulation: the operator's integer sums carry no rounding either)
+    auto product = [&](const std::vector<int> &rs, const double *dV) -> int {
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(A.down(hv.data(), dV, nd));
+        for (int r : rs) {
+            const double *Hr = Hd + (size_t)r * Qp * Qp, *v = hv.data() + (size_t)r * Qp;
+            for (int64_t i = 0; i < Qp; ++i) {
+                long double s = 0.0L;
+                for (int64_t j = 0; j < Qp; ++j)
+                    if (v[j] != 0.0) s += (long double)Hr[i * Qp + j] * v[j];
+                hp[(size_t)r * Qp + i] = (double)s;
+            }
+        }
+        HIPCHK(hipMemcpy(dHp, hp.data(), sizeof(double) * nd, hipMemcpyHostToDevice));
+        return GML_OK;
+    };
+    auto steps = [&](int n) -> int {
+        for (int k = 0; k < n && nl > 0; ++k) {
+            const int rc = product(liverows, dPv);
+            if (rc) return rc;
+            launch_pcg_step(dLiveRows, nl, dG, dWm, Qp, dS1, s2, dHp, dD, dRv, dPv, dCg, wl, nullptr);
+            launch_tile_apply(T, dHt, dFV, dVm, dWrow, dLive, (int64_t)ntiles, Qp, dRv, dZv, nullptr);
+            launch_pcg_dir(dLiveRows, nl, Qp, dWm, dRv, dZv, dPv, 0, dCg, wl, nullptr);
+        }
+        return GML_OK;
+    };
+    launch_tile_inverse(T, dHt, dHoff, dVm, dWrow, dS1, s2, dgV, (int64_t)ntiles, nullptr);
+    launch_pcg_init(dRows, nrows, dX, dPG, dKind, Qp, dD, dRv, dZv, dPv, dWm, dCg, nullptr);
+    launch_tile_apply(T, dHt, dFV, dVm, dWrow, dLive, (int64_t)ntiles, Qp, dRv, dZv, nullptr);
+    launch_pcg_dir(dLiveRows, nl, Qp, dWm, dRv, dZv, dPv, 1, dCg, wl, nullptr);
+    int rc = steps(nsteps);
+    if (rc) return rc;
+    if (faces) {
+        launch_pcg_faces(dRows, nrows, dX, dPG, dKind, Qp, dD, dWm, dFo, nullptr);
+        rc = product(liverows, dD);
+        if (rc) return rc;
+        launch_pcg_resid(dLiveRows, nl, dPG, dG, Qp, dS1, s2, dHp, dD, dWm, dRv, dCg, nullptr);
+        launch_tile_apply(T, dHt, dFV, dVm, dWrow, dLive, (int64_t)ntiles, Qp, dRv, dZv, nullptr);
+        launch_pcg_dir(dLiveRows, nl, Qp, dWm, dRv, dZv, dPv, 1, dCg, wl, nullptr);
+        rc = steps(nsteps2);
+        if (rc) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(A.down(FV, dFV, tcap * T));
+    HIPCHK(A.down(gV, dgV, tcap * T));
+    HIPCHK(A.down(D, dD, nd));
+    HIPCHK(A.down(Rv, dRv, nd));
+    HIPCHK(A.down(Zv, dZv, nd));
+    HIPCHK(A.down(Pv, dPv, nd));
+    HIPCHK(A.down(Wm, dWm, nd));
+    HIPCHK(A.down(static_cast<CgState *>(cg), dCg, (size_t)R));
+    HIPCHK(A.down(static_cast<FaceOut *>(fout), dFo, (size_t)R));
+    return GML_OK;
+}
