@@ -112,6 +112,7 @@ def lib():
     L.gml_learn.argtypes = [p, i32, dbl, C.POINTER(Opts), p, p, C.POINTER(Stats)]
     L.gml_learn_warm.argtypes = [p, i32, dbl, C.POINTER(Opts), p, p, p, C.POINTER(Stats)]
     L.gml_learn_structured.argtypes = [p, i32, dbl, C.POINTER(Opts), p, i64, p, p, p, C.POINTER(Stats)]
+    L.gml_stderr.argtypes = [p, i32, p, i64, p, i64, p, p, p]
     L.gml_structure_from_rows.argtypes = [p, i64, i64, i32, i32, dbl, i32, i32, i32, i32, p, i64, C.POINTER(i64)]
     L.gml_structure_from_keys.argtypes = [p, i32, i64, i64, i32, i32, i32, i32, i32, p, i64]
     L.gml_terms_count.restype = i64
@@ -634,6 +635,26 @@ class Problem:
         else:
             check(rc)
         return out, kkt, st.asdict()
+
+    def stderr(self, formulation, rows, structure=None):
+        """gml_stderr: (se, status) of the solved rows `rows` ((node1-node0) x P, the layout of learn's result) -- the M-estimator
+        ("sandwich") standard error of every parameter of the support (FREE slots, PENALISED slots with rows != 0; structure as in
+        learn, None = the field free, the rest penalised), 0.0 elsewhere; status per row: 0 ok, 1 singular support (se NaN there), 2 a
+        support of more than 512 entries (NaN).  Conditional on the support; meant for refitted rows (include/gml.h)."""
+        R = self.node1 - self.node0
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.shape != (R, self.P):
+            raise GMLError(GML_EINVAL, f"rows have shape {rows.shape}, the handle's rows are {(R, self.P)}")
+        if structure is not None:
+            structure = np.asarray(structure)
+            if structure.dtype != np.uint8 or structure.shape != (R, self.P):
+                raise GMLError(GML_EINVAL, f"structure is {structure.dtype} {structure.shape}, the handle's rows take uint8 {(R, self.P)}")
+            structure = np.ascontiguousarray(structure)
+        se = np.zeros((R, self.P))
+        status = np.zeros(R, dtype=np.int32)
+        check(lib().gml_stderr(self._h, FORMULATION_IDS[formulation], _ptr(rows), self.P, _ptr(structure), self.P, _ptr(se), _ptr(status),
+                               None))
+        return se, status
 
     def multi_keys_array(self, u):
         """gml_multi_keys as it comes: int32 [P, order], 0-based, -1 = unused slot"""

@@ -110,5 +110,18 @@ gml_problem *gml_new_problem(int64_t K, int64_t n, double M, int order, int64_t 
 int gml_create_from_device_bytes(gml_problem *p, int8_t *dbytes, bool spin_major, int64_t ld, const double *counts, gml_problem **out,
                                  bool dedupe = false);
 
+// gml_stderr and its test hook behind one body (gml_sandwich.hip).  hook != NULL: the finish kernel stops after the per-formulation
+// corrections, and the support lists (reference slots), sizes and the A, B, g blocks of the local rows hook->rows are copied out
+// (host arrays; row h at pitch cap: lists / g [nrows][cap], A / B [nrows][cap][cap]; cap >= every listed support).
+struct GmlSandwichHook {
+    int64_t nrows;
+    const int64_t *rows;
+    int cap;
+    int32_t *lists, *msz;
+    double *A, *B, *g;
+};
+int gml_sandwich_run(gml_problem *p, int formulation, const double *x, int64_t ld, const uint8_t *structure, int64_t ld_s, double *se,
+                     int32_t *status, double *times, const GmlSandwichHook *hook);
+
 int gml_ensure_ws(gml_problem *p, int64_t rows);
 int gml_ensure_f64(gml_problem *p, int64_t vrows); // byte images + V [vrows][Kp] of the FP64 path

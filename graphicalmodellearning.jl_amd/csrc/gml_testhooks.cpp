@@ -61,6 +61,25 @@ extern "C" double gml_test_hv_sparse_ratio(double ratio) {
     return old;
 }
 
+// gml_stderr up to the factorisation: the support lists (reference slots, ascending) and sizes of the local rows `rows`, and the A, B
+// and g blocks as the Cholesky of k_sandwich_finish receives them (gml_sandwich.hip; host arrays, pitch cap).  se / status as gml_stderr
+// leaves them before the finish (0.0 off the support, NaN on it).
+extern "C" int gml_test_sandwich_grams(gml_problem *p, int formulation, const double *x, int64_t ld, const uint8_t *structure, int64_t ld_s,
+                                       int64_t nrows, const int64_t *rows, int cap, int32_t *lists, int32_t *msz, double *A, double *B, double *g) {
+    if (!p || !rows || !lists || !msz || !A || !B || !g || nrows < 1 || cap < 1) return fail(GML_EINVAL, "NULL argument");
+    std::vector<double> se((size_t)(p->node1 - p->node0) * (size_t)std::max<int64_t>(ld, 1));
+    const GmlSandwichHook hook{nrows, rows, cap, lists, msz, A, B, g};
+    return gml_sandwich_run(p, formulation, x, ld, structure, ld_s, se.data(), nullptr, nullptr, &hook);
+}
+// A handle that holds sizes only -- no device, no samples -- for the tests of argument checks that run before any device work
+// (tests/test_host_sandwich.py).  Release it with gml_problem_destroy.
+extern "C" int gml_test_problem_stub(int64_t n, int64_t P, int order, int64_t node0, int64_t node1, gml_problem **out) {
+    if (!out || n < 1 || P < 1 || node0 < 0 || node1 > n || node0 > node1) return fail(GML_EINVAL, "bad stub");
+    gml_problem *q = gml_new_problem(0, n, 1.0, order, node0, node1, 0);
+    q->P = P;
+    *out = q;
+    return GML_OK;
+}
 
 extern "C" int gml_test_tile_precond(int T, int ntiles, const int *m, const double *tiles /* ntiles x T x T */, double s1, double s2,
                                      const double *g /* ntiles x T */, const double *r /* ntiles x T */, double *z_out /* ntiles x T */,

@@ -70,6 +70,15 @@ class HIP(GMLMethod):
                statistics, stats["support"] the number of kept couplings (per-node entries)
     refit_rule how a coupling is judged: "mean" (the symmetrised value; the default with formulation.symmetrization), "row" (each
                node's own entry; the default without), "all" or "any" (every / some member's entry)
+    stderr     True: after the solve (after the refit when refit is set, under the refit's structure) the standard errors of the
+               solved rows are computed on the same handle (gml_stderr: the sandwich covariance A^-1 B A^-1 / M of every node's
+               M-estimator).  stats["stderr"] is the (n, P) array in the layout of the solved rows (0 outside a row's support),
+               stats["stderr_status"] the per-node status (0 ok, 1 singular support, 2 more than 512 entries; NaN in both cases),
+               stats["z"] = x / se where se > 0 (0 elsewhere); pairwise formulations with symmetrization also get
+               stats["stderr_sym_bound"] = (se + se') / 2 (diagonal: the fields' own se) -- an UPPER BOUND on the standard error of the
+               symmetrised coupling (x_uv + x_vu) / 2, valid whatever the correlation between the two nodes' estimates, which is
+               not computed.  Conditional on the selected support: meant to be combined with refit.  Restrictions as refit: one
+               process, one GPU, all nodes
     """
     tol: float = 1e-9
     precision: str = "auto"
@@ -86,6 +95,7 @@ class HIP(GMLMethod):
     structure: Any = None
     refit: Optional[float] = None
     refit_rule: Optional[str] = None
+    stderr: bool = False
     stats: dict = field(default_factory=dict, repr=False, compare=False)
 
 

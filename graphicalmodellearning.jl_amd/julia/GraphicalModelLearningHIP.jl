@@ -145,6 +145,45 @@ end
 # this hands them back to the driver and returns the number of bytes released.
 trim_cache() = Int(ccall((:gml_trim_cache, libgml), Int64, ()))
 
+"""
+    stderr(samples, formulation, rows; method=HIP(), structure=nothing, order=2) -> (se, status)
+
+Standard errors of solved rows (gml_stderr: the sandwich covariance A^-1 B A^-1 / M of every node's M-estimator, include/gml.h).
+`rows` is the R x P matrix of un-symmetrised solved rows of the nodes `method.node_range` (all nodes by default), `structure` an
+R x P `UInt8` matrix of GML_PARAM_* kinds (0 excluded, 1 free, 2 penalised; `nothing` = the field free, the rest penalised).
+`se` is R x P (0 outside a row's support), `status[r]` 0 = ok, 1 = singular support, 2 = more than 512 entries (NaN in both cases).
+Conditional on the selected support: meant for refitted rows.  Marshalling only.
+Not exported: the name shadows `Base.stderr` inside this module only (which does not use the stream); call it as
+`GraphicalModelLearningHIP.stderr(...)`.
+"""
+function stderr(samples::Array{T,2}, formulation, rows::Array{Float64,2}; method::HIP=HIP(),
+                structure::Union{Nothing,Array{UInt8,2}}=nothing, order::Int=2) where T <: Real
+    s = T <: AbstractFloat ? convert(Array{Float64,2}, samples) : convert(Array{Int64,2}, samples)
+    dtype = eltype(s) == Float64 ? GML_F64 : GML_I64
+    K, n = size(s, 1), size(s, 2) - 1
+    n0, n1 = method.node_range === nothing ? (0, n) : (method.node_range[1] - 1, method.node_range[2])
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:gml_problem_create, libgml), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Cint, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+               s, dtype, K, n, K, 1 #= column-major =#, order, n0, n1, method.device, handle)
+    rc == GML_OK || error("gml_problem_create: $(lasterr())")
+    try
+        R, P = n1 - n0, size(rows, 2)
+        size(rows, 1) == R || throw(ArgumentError("stderr: rows has $(size(rows, 1)) rows, the node range has $R"))
+        x = permutedims(rows)                             # Julia (P x R) == C row-major (R x P)
+        st = structure === nothing ? nothing : permutedims(structure)
+        se = Array{Float64}(undef, P, R)
+        status = zeros(Int32, R)
+        rc = ccall((:gml_stderr, libgml), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64, Ptr{UInt8}, Int64, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}),
+                   handle[], formulation_id(formulation), x, P, st === nothing ? C_NULL : st, P, se, status, C_NULL)
+        rc == GML_OK || error("gml_stderr: $(lasterr())")
+        return permutedims(se), status
+    finally
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
+    end
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

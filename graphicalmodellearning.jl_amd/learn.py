@@ -29,7 +29,7 @@ DICT_TERMS_MAX = 1 << 17
 
 
 def _local_solve_hip(samples, formulation, method, order, node_range, device, terms=None, packed=None, matrix=None, structure=None,
-                     refit=None):
+                     refit=None, stderr=False):
     """rows of the local node range through libgml_hip: (out, kkt, stats).  terms = True / False (all nodes, multiRISE): the
     model's weight array instead of the rows -- solve and assembly in one library call, the rows never leave the device.
     packed = (sign_bits, counts or None, K): the handle is built from the packed form (gml_problem_create_packed) and `samples`
@@ -37,7 +37,8 @@ def _local_solve_hip(samples, formulation, method, order, node_range, device, te
     pairwise): the n x n result of gml_learn_matrix, symmetrised on the device (True).  structure: the rows of HIP.structure for
     this node range (gml_learn_structured).  refit = (tau, rule) (all nodes): the rows of a second solve on the same handle, whose
     structure is the first solve's support (structure_from_rows: kept FREE, dropped EXCLUDED, fields FREE) and which starts from the
-    first solve's rows; st is the first solve's, st["refit"] the second's, st["support"] the number of kept entries."""
+    first solve's rows; st is the first solve's, st["refit"] the second's, st["support"] the number of kept entries.  stderr: gml_stderr
+    of the returned rows on the same handle, under the structure of the solve that produced them: st["stderr"], st["stderr_status"]."""
     src = {"packed": packed} if packed is not None else {"samples": samples}
     with _lib.Problem(order=order, node_range=node_range, device=device, **src) as prob:
         opts = dict(tol=method.tol, max_iter=method.max_iter, precision=method.precision, max_working=method.max_working,
@@ -51,6 +52,9 @@ def _local_solve_hip(samples, formulation, method, order, node_range, device, te
                 support = np.where(structure == _lib.EXCLUDED, np.uint8(_lib.EXCLUDED), support)
             out, kkt, st2 = prob.learn(_form_name(formulation), formulation.regularizer, structure=support, x0=out, **opts)
             st["refit"], st["support"] = st2, kept
+            structure = support
+        if stderr:
+            st["stderr"], st["stderr_status"] = prob.stderr(_form_name(formulation), out, structure=structure)
     return out, kkt, st
 
 
@@ -177,6 +181,8 @@ def learn(samples, formulation=None, method=None):
             raise ValueError("HIP: refit thresholds the rows of ALL nodes: one process, one GPU, no node_range")
         if not (float(method.refit) >= 0.0) or not np.isfinite(method.refit):
             raise ValueError(f"HIP: refit is the threshold of the support, finite and >= 0, not {method.refit!r}")
+    if method.stderr and (method.devices is not None or method.distributed or method.node_range is not None):
+        raise ValueError("HIP: stderr is computed on the handle that solved ALL nodes: one process, one GPU, no node_range")
     if method.refit_rule is not None and method.refit_rule not in _lib.RULES:
         raise ValueError(f"HIP: unknown refit_rule {method.refit_rule!r} (use 'mean', 'row', 'all' or 'any')")
     if method.precision not in _lib.PRECISIONS:
@@ -218,6 +224,8 @@ def learn(samples, formulation=None, method=None):
         extra["structure"] = np.ascontiguousarray(whole[node_range[0]:node_range[1]])
     if method.refit is not None:
         extra["refit"] = (float(method.refit), method.refit_rule or ("mean" if formulation.symmetrization else "row"))
+    if method.stderr:
+        extra["stderr"] = True  # (rows are needed: not the fused one-call routes)
     if multi and not (method.distributed and world > 1) and method.devices is None and tuple(node_range) != (0, n):
         raise ValueError("multiRISE assembles a FactorGraph from the rows of ALL nodes (:129-151): solve node shards with "
                          "Problem.learn and hand the gathered rows to _lib.terms_assemble")
@@ -246,6 +254,13 @@ def learn(samples, formulation=None, method=None):
     method.stats.clear()
     method.stats.update(st or {})
     method.stats["kkt"] = kkt
+    if method.stderr and "stderr" in method.stats:
+        se, x = np.asarray(method.stats["stderr"]), np.asarray(out)
+        method.stats["z"] = np.divide(x, se, out=np.zeros_like(x), where=se > 0)
+        if not multi and formulation.symmetrization and se.shape[0] == se.shape[1]:
+            # an upper bound on the se of (x_uv + x_vu) / 2, whatever the correlation between the two nodes' estimates (not computed);
+            # the diagonal is the fields' own se
+            method.stats["stderr_sym_bound"] = 0.5 * (se + se.T)
     if start is not None:
         method.stats.update(start)  # pack_s (rank 0's one read of the matrix), bcast_s, bcast_bytes
 

@@ -487,6 +487,45 @@ int gml_learn_structured(gml_problem *p, int formulation, double regularizer_c, 
                          int64_t ld_s, const double *x0, double *out, double *kkt, gml_stats *stats);
 
 /*
+ * gml_stderr -- standard errors of solved rows (beyond the reference, which returns point estimates only): the M-estimator
+ * ("sandwich") covariance of every local node's solve, computed on the device from the handle's sign bits and weights.  For local row
+ * r = node u with solution x on its support S, s_k the reference's statistic vector of configuration k (`nodal_stat[k, :]`, :162;
+ * multi-body :106-108), a_k = x . s_k, w_k = count_k / M, every sum over ALL K configurations (no sub-sample):
+ *     Cov(x_S) ~ A^-1 B A^-1 / M,   se_j = sqrt of its diagonal
+ *     A = sum_k w_k phi''(a_k) s_k s_k^T (the Hessian on S),   B = sum_k w_k psi_k psi_k^T - m m^T,   m = sum_k w_k psi_k
+ *     RISE     phi'' = e_k = exp(-a_k);                 psi_k = -e_k s_k
+ *     RPLE     phi'' = 4 sg_k (1 - sg_k), sg_k = 1 / (1 + exp(-2 a_k));   psi_k = -2 (1 - sg_k) s_k
+ *     logRISE  A = (sum w e s s^T) / Z - gb gb^T, Z = sum w e, gb = grad log Z = -(sum w e s) / Z;   psi_k = -(e_k / Z)(s_k + gb), m = 0
+ *   x          (node1-node0) x P rows in the layout of gml_learn's `out`, leading dimension ld >= P
+ *   structure  as in gml_learn_structured (ld_s >= P); NULL = the reference's: the field free, the rest penalised.  The support of a
+ *              row is every GML_PARAM_FREE slot (also at x = 0) plus every GML_PARAM_PENALISED slot with x != 0
+ *   se         (node1-node0) x P, leading dimension ld: se_j at the slots of the support, 0.0 at every other slot
+ *   status     host, [node1-node0], may be NULL: GML_SE_OK; GML_SE_SINGULAR -- a pivot of the Cholesky of A is not above 1e-13 x the
+ *              largest diagonal entry of A (duplicated or constant statistics in the support): the se of that row's support is NaN;
+ *              GML_SE_TOO_LARGE -- a support of more than 512 entries (gml_opts.max_working's ceiling): NaN likewise.  Other rows are
+ *              not affected.  A row with an empty support: se = 0, GML_SE_OK
+ *   times      host, [3], may be NULL: seconds spent on the support lists, the Gram sweep, the factorisations
+ * x, se and structure: host pointers or device pointers on the handle's GPU, each detected on its own.
+ * What the numbers mean, and what they do not:
+ *   - with penalised active coordinates this is the covariance CONDITIONAL on the selected support and signs, not a post-selection
+ *     valid interval; the intended use is after a refit (gml_learn_structured on the kept support), where every parameter is FREE;
+ *   - the M samples are taken as independent draws: thinned-chain output with residual autocorrelation makes the se optimistic;
+ *   - covariances between the rows of different nodes are not computed, so there is no exact se of a symmetrised coupling
+ *     (x_uv + x_vu) / 2; (se_uv + se_vu) / 2 bounds it from above whatever the correlation;
+ *   - the reference has nothing comparable: tests/_sandwich_reference.py (dense numpy) is the yardstick.
+ * The result does not depend on the handle's node range, on host or device pointers, or on what else the call computes: the
+ * partial sums of a row are combined in a fixed order that depends on the row's support size and K only.
+ * GML_EINVAL, before any device work: NULL p / x / se, ld < P, ld_s < P, an unknown formulation, a structure byte outside {0, 1, 2}
+ * or a non-finite x in a host array (device arrays are checked by the kernels that read them).  GML_EINVAL after the lists are built: a
+ * non-zero x at a GML_PARAM_EXCLUDED slot (the text names row and slot).  GML_EUNSUPPORTED: logRISE / RPLE on a multi-body handle.
+ */
+#define GML_SE_OK 0
+#define GML_SE_SINGULAR 1
+#define GML_SE_TOO_LARGE 2
+int gml_stderr(gml_problem *p, int formulation, const double *x, int64_t ld, const uint8_t *structure, int64_t ld_s,
+               double *se, int32_t *status, double *times);
+
+/*
  * Structures for gml_learn_structured, built on the device in the (node, slot) layout of the rows (closed-form for multi-body models:
  * no key table).  `structure` is n x P bytes with leading dimension ld_s >= P, host or device pointer; bytes [P, ld_s) of a row are
  * not written.  `device`: where the kernels run when no argument is a device pointer.
