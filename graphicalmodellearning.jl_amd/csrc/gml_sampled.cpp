@@ -189,15 +189,12 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
         while (parent[a] != a) a = parent[a] = parent[parent[a]];
         return a;
     };
+    // (a term joins the spins that remain after cancellation: a spin named twice is not part of it)
+    std::vector<int> sp;
     for (int64_t t = 0; t < nterms; ++t) {
         if (weights[t] == 0.0) continue;
-        int64_t first = -1;
-        for (int a = 0; a < stride; ++a) {
-            const int32_t v = keys[t * stride + a];
-            if (v < 0) continue;
-            if (first < 0) first = v;
-            else parent[find(v)] = find(first);
-        }
+        reduce_key(keys + t * stride, stride, sp);
+        for (size_t a = 1; a < sp.size(); ++a) parent[find(sp[a])] = find(sp[0]);
     }
     std::vector<std::vector<int>> blocks;
     std::vector<int64_t> id((size_t)n, -1);
@@ -221,14 +218,13 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
     std::vector<std::vector<unsigned>> bmask(blocks.size());
     std::vector<std::vector<double>> bwt(blocks.size());
     size_t maxnt = 1;
-    std::vector<int> sp;
     for (int64_t t = 0; t < nterms; ++t) {
         if (weights[t] == 0.0) continue;
-        const int named = reduce_key(keys + t * stride, stride, sp);
-        if (named < 0) continue; // the empty term: a constant energy
+        reduce_key(keys + t * stride, stride, sp);
+        if (sp.empty()) continue; // the empty term, or one whose spins all cancel: a constant energy
         unsigned mask = 0;
         for (int v : sp) mask |= 1u << local[(size_t)v];
-        const size_t b = (size_t)id[find(named)];
+        const size_t b = (size_t)id[find(sp[0])];
         bmask[b].push_back(mask);
         bwt[b].push_back(weights[t]);
         maxnt = std::max(maxnt, bmask[b].size());

@@ -74,7 +74,9 @@ __global__ __launch_bounds__(1024) void k_block_cdf(const double *__restrict__ e
     }
     __syncthreads();
     const double inv = 1.0 / total;
-    for (int64_t i = b0; i < b1; ++i) cdf[i] *= inv;
+    // (the last entry is 1 by definition: total * (1 / total) can round to 1 - 2^-53, and with two or more entries per thread the
+    // last running sum is not `total` bit for bit)
+    for (int64_t i = b0; i < b1; ++i) cdf[i] = i + 1 < ns ? cdf[i] * inv : 1.0;
 }
 
 // one thread per sample: CDF inversion by binary search, spins written sample-major

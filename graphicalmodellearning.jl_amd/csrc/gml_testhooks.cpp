@@ -673,3 +673,45 @@ extern "C" int gml_test_pcg(int R, int64_t Qp, int T, int nrows, const int *rows
     HIPCHK(A.down(static_cast<FaceOut *>(fout), dFo, (size_t)R));
     return GML_OK;
 }
+
+// The three kernels of the exact block sampler (gml_sampler.hip) on one caller-given block: masks, wts [nt] (the block's terms as bit
+// masks over its sb <= 22 spins), members [sb] (the global ids, each in [0, n)), N samples of n spins, the random stream `block`, on device 0.
+// One launch_block_sampler on a stream of its own; back come en, cdf [2^sb] as the kernels left them and S [N][n], zeroed first, so that
+// the spins outside `members` read 0.  tests/test_gpu_sampler_exact.py.
+extern "C" int gml_test_block_sampler(const unsigned *masks, const double *wts, int nt, int sb, const int *members, int64_t N, int64_t n,
+                                      uint64_t seed, int block, double *en_out, double *cdf_out, int8_t *S_out) {
+    if (nt < 0 || sb < 1 || sb > 22 || N < 1 || n < sb || !members || !en_out || !cdf_out || !S_out || (nt > 0 && (!masks || !wts)))
+        return fail(GML_EINVAL, "bad argument");
+    for (int t = 0; t < sb; ++t)
+        if (members[t] < 0 || members[t] >= n) return fail(GML_EINVAL, "member %d outside [0,%lld)", members[t], (long long)n);
+    for (int t = 0; t < nt; ++t)
+        if ((masks[t] >> sb) != 0) return fail(GML_EINVAL, "mask %d names a spin outside the block", t);
+    HIPCHK(hipSetDevice(0));
+    struct Stream {
+        hipStream_t st = nullptr;
+        ~Stream() {
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } s;
+    HIPCHK(hipStreamCreate(&s.st));
+    DevArrays A; // (freed before the stream goes: declared after it)
+    const size_t ns = (size_t)1 << sb;
+    unsigned *dMasks = nullptr;
+    double *dWts = nullptr, *dEn = nullptr, *dCdf = nullptr;
+    int *dMem = nullptr;
+    int8_t *dS = nullptr;
+    HIPCHK(A.up(&dMasks, masks, (size_t)nt));
+    HIPCHK(A.up(&dWts, wts, (size_t)nt));
+    HIPCHK(A.up(&dMem, members, (size_t)sb));
+    HIPCHK(A.up(&dEn, static_cast<const double *>(nullptr), ns));
+    HIPCHK(A.up(&dCdf, static_cast<const double *>(nullptr), ns));
+    HIPCHK(A.up(&dS, static_cast<const int8_t *>(nullptr), (size_t)N * (size_t)n));
+    HIPCHK(hipDeviceSynchronize()); // the uploads and the zeroing went through the null stream
+    launch_block_sampler(dMasks, dWts, nt, sb, dMem, N, n, (unsigned long long)seed, block, dEn, dCdf, dS, s.st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s.st));
+    HIPCHK(A.down(en_out, dEn, ns));
+    HIPCHK(A.down(cdf_out, dCdf, ns));
+    HIPCHK(A.down(S_out, dS, (size_t)N * (size_t)n));
+    return GML_OK;
+}

@@ -211,7 +211,9 @@ int gml_problem_create_sampled(const double *model, int64_t n, int64_t N, uint64
 /* Same for a model of any interaction order given as a term list (the reference's general sampler,
  * src/sampling.jl:60-88, dispatch :94-106): term t couples the spins keys[t*key_stride .. +key_stride)
  * (0-based, -1 = unused slot) with weight weights[t]; P(s) ~ exp(sum_t w_t prod_{i in t} s_i).  Exact per
- * connected component of the term hypergraph (<= 22 spins each). */
+ * connected component of the term hypergraph (<= 22 spins each).  A spin named twice in a key cancels (s^2 = 1) and is not part of
+ * the term: it joins no component through it.  Zero-weight terms join nothing either.  Component b, counted in the order of the
+ * components' smallest spins, draws sample k at u01(seed, b, k). */
 int gml_problem_create_sampled_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,
                                      int64_t n, int64_t N, uint64_t seed, int order, int64_t node0,
                                      int64_t node1, int device, gml_problem **out);
