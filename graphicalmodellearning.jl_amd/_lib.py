@@ -96,6 +96,8 @@ def lib():
     L.gml_problem_get_spins.argtypes = [p, p]
     L.gml_problem_moments.argtypes = [p, p, p]
     L.gml_problem_term_moments.argtypes = [p, p, i32, i64, p]
+    L.gml_problem_fold_sizes.argtypes = [p, i32, C.c_uint64, p]
+    L.gml_problem_split.argtypes = [p, i32, i32, C.c_uint64, i32, C.POINTER(p)]
     L.gml_problem_destroy.argtypes = [p]
     L.gml_problem_destroy.restype = None
     L.gml_problem_info.argtypes = [p] + [p] * 6
@@ -456,12 +458,38 @@ class Problem:
             n0, n1 = _node_range(node_range, n)
             check(L.gml_problem_create_spins(_ptr(counts), _ptr(spins), K, n, int(order), n0, n1, int(device),
                                              C.byref(h)))
+        self._adopt(h, order)
+
+    def _adopt(self, h, order):
+        """take ownership of the handle h (a c_void_p) and read its sizes"""
         self._h = h
         nn, KK, PP, a, b = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         M = C.c_double()
-        check(L.gml_problem_info(h, C.byref(nn), C.byref(KK), C.byref(M), C.byref(PP), C.byref(a), C.byref(b)))
+        check(lib().gml_problem_info(h, C.byref(nn), C.byref(KK), C.byref(M), C.byref(PP), C.byref(a), C.byref(b)))
         self.n, self.K, self.M, self.P, self.node0, self.node1 = nn.value, KK.value, M.value, PP.value, a.value, b.value
         self.order = int(order)
+
+    @classmethod
+    def _from_handle(cls, h, order):
+        """a Problem around a handle the library has already made (split): no creator runs"""
+        self = cls.__new__(cls)
+        self.swap_counts = None
+        self._adopt(h, order)
+        return self
+
+    def fold_sizes(self, folds, seed=0):
+        """the number of the handle's samples in each of `folds` folds (gml_problem_fold_sizes): int64 [folds], summing to M"""
+        out = np.zeros(64, dtype=np.int64)  # (the library refuses folds outside [2, 64] before it writes)
+        check(lib().gml_problem_fold_sizes(self._h, int(folds), int(seed), _ptr(out)))
+        return out[:int(folds)].copy()
+
+    def split(self, folds, fold, seed=0, complement=False):
+        """A new Problem holding the samples of fold `fold` of `folds` (complement=True: all the others), split on the device
+        (gml_problem_split; include/gml.h defines the fold of every sample from the seed).  Same device, order and node range;
+        independent of this handle, and the same handle as Problem(packed=...) of the selected rows and their new counts."""
+        h = C.c_void_p()
+        check(lib().gml_problem_split(self._h, int(folds), int(fold), int(seed), int(bool(complement)), C.byref(h)))
+        return Problem._from_handle(h, self.order)
 
     def close(self):
         if getattr(self, "_h", None):

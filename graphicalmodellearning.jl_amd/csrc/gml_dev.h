@@ -185,6 +185,11 @@ int dedupe_samples(const int8_t *dS, bool spin_major, int64_t ld, int64_t N, int
                    int **dcounts_out, int64_t *K_out, std::string *err);
 void launch_bits_from_keys(const unsigned long long *dkeys, int64_t K, int64_t n, int64_t Kp, unsigned *Sb, hipStream_t st);
 
+// Row compaction of the sign bits (gml_split.hip): Sb_out [n][Kp_out / 32] row k' = row src[k'] of Sb [n][Kp_src / 32] for k' < Kout; Sb_out
+// zeroed by the caller (rows >= Kout stay 0), Kp_out a multiple of 1024.
+void launch_gather_bits(const unsigned *Sb, int64_t Kp_src, const int *src, int64_t Kout, int64_t n, int64_t Kp_out, unsigned *Sb_out,
+                        hipStream_t st);
+
 // Exact sample moments from the sign bits (gml_moments.hip): XOR of sign rows + population counts, integer sums throughout.
 // planes [nplanes][Kp / 32]: bit b of every count c_k = rint(w_k M), packed like a sign row (launch_count_planes); nplanes = 0:
 // all counts equal (the common count is applied by the caller / the finishing kernel).

@@ -76,7 +76,7 @@ static int upload_pageable(void *dst, const void *src, size_t bytes, hipStream_t
 //   (Sb is filled by the host packer through the pinned stages below, or on the device from sampled bytes)
 //   prob_images   Sb, keys -> Xb, Xtb
 // ------------------------------------------------------------------------------------------
-static int prob_layout(gml_problem *p) {
+static int prob_layout(gml_problem *p, unsigned *adopt_sb = nullptr /* the handle's Sb, already on the device */) {
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipStreamCreate(&p->st));
     DevProblem &d = p->d;
@@ -127,7 +127,8 @@ static int prob_layout(gml_problem *p) {
         }
     }
     d.Xt = nullptr; // FP64 path only, built on first use (ensure_f64)
-    HIPCHK(dev_malloc(&d.Sb, (size_t)p->n * (d.Kp / 8)));
+    if (adopt_sb) d.Sb = adopt_sb;
+    else HIPCHK(dev_malloc(&d.Sb, (size_t)p->n * (d.Kp / 8)));
     HIPCHK(dev_malloc(&d.keys, sizeof(int32_t) * p->gkeys.size()));
     HIPCHK(dev_malloc(&d.Xb, (size_t)d.Kp * (d.Qfp / 8)));
     HIPCHK(dev_malloc(&d.Xtb, (size_t)xtb_bytes(d)));
@@ -264,6 +265,39 @@ int gml_create_from_device_bytes(gml_problem *p, int8_t *dbytes, bool spin_major
     if (rc == GML_OK) {
         if (dedupe) launch_bits_from_keys(dkeys, p->K, p->n, p->d.Kp, p->d.Sb, p->st);
         else launch_spin_bits(dbytes, spin_major, p->K, p->n, ld, p->d.Kp, p->d.Sb, p->st);
+        const double t1 = now_s();
+        rc = prob_images(p);
+        if (rc == GML_OK && hipStreamSynchronize(p->st) != hipSuccess) rc = fail(GML_EHIP, "building the bit images failed: %s", hipGetErrorString(hipGetLastError()));
+        p->t_ingest[2] = now_s() - t1;
+    }
+    p->t_ingest[3] = now_s() - t0;
+    if (rc != GML_OK) {
+        const std::string keep = gml_last_error();
+        gml_problem_destroy(p);
+        return fail(rc, "%s", keep.c_str());
+    }
+    *out = p;
+    return GML_OK;
+}
+
+// Handle from sign bits that are already on the device in the handle's own layout (a part of a split handle, gml_split.hip): the
+// same tail as above with nothing to pack.
+int gml_create_from_device_bits(gml_problem *p, unsigned *dSb, const double *counts, gml_problem **out) {
+    struct Guard {
+        void *b;
+        ~Guard() {
+            if (b) (void)dev_free(b);
+        }
+    } guard{dSb};
+    const double t0 = now_s();
+    int rc = prob_layout(p, dSb);
+    if (p->d.Sb == dSb) guard.b = nullptr; // the handle owns it now (gml_problem_destroy)
+    if (rc == GML_OK) {
+        WeightInfo wi;
+        weight_info(counts, p->K, p->d.Kp, p->M, wi);
+        rc = prob_weights(p, wi);
+    }
+    if (rc == GML_OK) {
         const double t1 = now_s();
         rc = prob_images(p);
         if (rc == GML_OK && hipStreamSynchronize(p->st) != hipSuccess) rc = fail(GML_EHIP, "building the bit images failed: %s", hipGetErrorString(hipGetLastError()));

@@ -109,6 +109,10 @@ int gml_check_create_args(int64_t K, int64_t n, int order, int64_t node0, int64_
 gml_problem *gml_new_problem(int64_t K, int64_t n, double M, int order, int64_t node0, int64_t node1, int device);
 int gml_create_from_device_bytes(gml_problem *p, int8_t *dbytes, bool spin_major, int64_t ld, const double *counts, gml_problem **out,
                                  bool dedupe = false);
+// Its sibling for sign bits that are already on the device in the handle's own layout (gml_split.hip): dSb [n][round_up(K, 1024) / 32],
+// bits of the rows >= K zero, written and synchronised by the caller; it becomes the handle's Sb (owned from here on, freed on every
+// path).  counts [K] host (NULL: all ones), p->M their sum.
+int gml_create_from_device_bits(gml_problem *p, unsigned *dSb, const double *counts, gml_problem **out);
 
 // gml_stderr and its test hook behind one body (gml_sandwich.hip).  hook != NULL: the finish kernel stops after the per-formulation
 // corrections, and the support lists (reference slots), sizes and the A, B, g blocks of the local rows hook->rows are copied out

@@ -598,14 +598,27 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                                     : (unsigned)fmin(fma(ymax, 3.5527136788005009e-15 /* 2^-48 */, 7.62939453125e-06 /* 2^-17 */), 4294967295.0);
         if (active && h == 0) atomicMax(&mmax[r], mxu);
     } else {
+        // RPLE: f as an exact integer sum, so that its bits do not depend on the order in which the waves' parts arrive.  The part fp
+        // goes in two words -- rint(fp 2^32) into asum2, the remainder (at most 2^-33) in units of 2^-72 into asum; this form uses
+        // neither otherwise -- which holds up to 2^23 parts of a row; k_finalize_i8w puts the two together.  A part that is not
+        // finite or not below 2^30 keeps the FP64 atomic, so that f still says what happened.
         fp = half_sum(fp);
-        if (active && h == 0) unsafeAtomicAdd(&fsum[r], fp);
+        if (active && h == 0) {
+            if (fabs(fp) < 0x1p30) {
+                const long long hi = __double2ll_rn(fp * 0x1p32);
+                const long long lo = __double2ll_rn(fma(-(double)hi, 0x1p-32, fp) * 0x1p72);
+                atomicAdd(reinterpret_cast<unsigned long long *>(&asum2[r]), (unsigned long long)hi);
+                atomicAdd(reinterpret_cast<unsigned long long *>(&asum[r]), (unsigned long long)lo);
+            } else {
+                unsafeAtomicAdd(&fsum[r], fp);
+            }
+        }
     }
 }
 
 // G[row][c] = tau_r (C_lo - 2 S_lo + 2^24 (C_hi - 2 S_hi)),  S_half = sum_l 256^l Gacc_l over the half's three planes (x = 1 - 2b),
 // C_half = sum_k of the half's digits; G[row][cconst] = tau_r (C_lo + 2^24 C_hi).  f: RISE / logRISE from the gradient's own
-// column (with the gradient) or from sum |V| (objective-only passes); RPLE keeps the forward kernel's FP64 sum.
+// column (with the gradient) or from sum |V| (objective-only passes); RPLE from the forward kernel's two-word integer sum.
 __global__ __launch_bounds__(256) void k_finalize_i8w(const int32_t *__restrict__ Gacc, const double *__restrict__ tau,
                                                       const long long *__restrict__ csum, const long long *__restrict__ csum2,
                                                       const long long *__restrict__ asum, const long long *__restrict__ asum2,
@@ -634,10 +647,13 @@ __global__ __launch_bounds__(256) void k_finalize_i8w(const int32_t *__restrict_
         return fma((double)(csum2[r] - 2 * s[1]), 16777216.0, coarse ? 0.0 : (double)(csum[r] - 2 * s[0]));
     };
     if (c == 0) {
-        double fv = f ? f[r] : 0.0; // RPLE: the forward kernel's FP64 sum
+        double fv = f ? f[r] : 0.0;
         if (form != 2) {
             if (want_grad) fv = -t * gcol(rowcol[r]); // f = sum_k w exp(-E) = -sum_k V_k s_k = -G[r][u]
             else fv = t * (coarse ? 16777216.0 : 1.0) * fma((double)asum2[r], 4294967296.0, (double)asum[r]);
+            f[r] = fv;
+        } else if (f) { // RPLE: the forward kernel's exact two-word sum (f[r] itself holds only parts that did not fit: normally 0)
+            fv += fma((double)asum[r], 0x1p-72, (double)asum2[r] * 0x1p-32);
             f[r] = fv;
         }
         if (res) res[r] = SlotResult{fv, t, mmax[r], 0u};

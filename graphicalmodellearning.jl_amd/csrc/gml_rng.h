@@ -8,6 +8,9 @@ namespace gml {
 
 constexpr unsigned long long kU01Step = 0x9E3779B97F4A7C15ull;   // per counter k
 constexpr unsigned long long kU01Stream = 0xD1B54A32D192ED03ull; // per stream (block / sweep)
+// The stream of the fold labels (gml_split.hip: unit g of a handle lies in fold floor(nfolds u01(seed, kU01FoldStream, g))).  The
+// samplers count their streams up from 0: a handle sampled with seed s and split with seed s shares no draw with its sampler.
+constexpr unsigned long long kU01FoldStream = 0x8000000000000000ull;
 
 // the hash of a counter word z = seed + kU01Step (k + 1) + kU01Stream (stream + 1)  (mod 2^64)
 __device__ __forceinline__ double u01_mix(unsigned long long z) {

@@ -361,6 +361,33 @@ int gml_problem_get_counts(gml_problem *p, double *counts);
 int gml_problem_moments(gml_problem *p, int64_t *sum1 /* [n] */, int64_t *sum2 /* [n][n] row-major, or NULL */);
 int gml_problem_term_moments(gml_problem *p, const int32_t *keys, int key_stride, int64_t nterms, int64_t *sums /* [nterms] */);
 
+/*
+ * gml_problem_fold_sizes, gml_problem_split -- a resident handle split into folds on the device (cross-validation; gml_split.hip).
+ *
+ * The definition.  The handle's M samples are its UNITS: configuration k (the handle's row order) with the integer count c_k owns
+ * the units g = C_k .. C_k + c_k - 1, C_k = c_0 + .. + c_(k-1).  Unit g belongs to fold
+ *     min(nfolds - 1, (int)floor(nfolds * u01(seed, kU01FoldStream, g)))
+ * with u01 the samplers' counter hash (gml_rng.h: splitmix64 of seed + kU01Step (g + 1) + kU01Stream (stream + 1), top 53 bits) and
+ * kU01FoldStream = 0x8000000000000000: the samplers count their streams up from 0, so a handle sampled with seed s and split with
+ * seed s shares no draw with its sampler.  The labels depend on (seed, nfolds, g) alone -- not on a launch shape, the device or the
+ * order of a reduction (integer tallies throughout).
+ *
+ * gml_problem_fold_sizes: sizes[f] = the number of units in fold f (host pointer, nfolds values; they sum to M).
+ * gml_problem_split: *out = a NEW handle, independent of p (p may be destroyed first), on p's device, with p's order and node range.
+ * It holds exactly the configurations with a positive new count c'_k, in source order, where c'_k = the units of k whose fold ==
+ * `fold` (complement = 0: the held-out part) or != `fold` (complement != 0: the training part); M' = sum c'_k.  The handle is
+ * indistinguishable from gml_problem_create_packed(bits', counts', K'): the same sign words (bits of the rows >= K' zero), weights,
+ * summaries and bit images, hence bit-identical results from every call.  The held-out and the training part of one (nfolds, fold,
+ * seed) partition the source's counts.
+ * GML_EINVAL (checked before any device work): NULL p / sizes / out, nfolds outside [2, 64], fold outside [0, nfolds); and, from the
+ * split itself, an empty part (M' = 0; the text names the fold).  GML_EUNSUPPORTED: a handle created with a fractional count, M >=
+ * 2^40 (the work is per unit), K >= 2^31 - 1.  Handles of gml_multi are not covered.
+ * Cost: one hash per unit (a wave per configuration, its lanes striding over the units), two scans over K, and the compaction of
+ * the sign bits, which reads n K / 8 and writes n K' / 8 bytes; then the bit images of the new handle, as for every creator.
+ */
+int gml_problem_fold_sizes(gml_problem *p, int nfolds, uint64_t seed, int64_t *sizes /* [nfolds] */);
+int gml_problem_split(gml_problem *p, int nfolds, int fold, uint64_t seed, int complement, gml_problem **out);
+
 /* The +-1 configurations held by a handle, K x n row-major (host pointer). */
 int gml_problem_get_spins(gml_problem *p, int8_t *spins);
 
