@@ -307,6 +307,28 @@ extern "C" int gml_test_i8_pack_state(gml_problem *p, int64_t xc_tile, int64_t *
     return GML_OK;
 }
 
+// Test hook (not part of include/gml.h): what the backward GEMM and the finalisation of the last int8-limb pass left on the device -- the
+// i32 accumulator planes Gacc, and the operator workspace's rows of G and f in the internal column layout, before any gather into the
+// caller's order.  Read only: synchronises the handle's stream and copies; launches nothing.
+//   dims [8]: 0 gplanes (sets of accumulators, one per 2^24 configurations), 1 plane_stride (elements between two sets = slots * LBT * Qfp),
+//             2 Qfp, 3 slots, 4 LBT (accumulator planes per slot: 4 i8x, 6 i8w), 5 rows of the operator workspace, 6 Qp, 7 0
+//   gacc int32 [dims 0][dims 3 / 32][dims 4][32][dims 2] or NULL;  G double [dims 5][dims 6] or NULL;  F double [dims 5] or NULL
+extern "C" int gml_test_i8_gacc(gml_problem *p, int64_t *dims, int32_t *gacc, double *G, double *F) {
+    if (!p || !dims) return fail(GML_EINVAL, "bad argument");
+    const gml::I8Ws *w = static_cast<const gml::I8Ws *>(p->i8ws);
+    const DevProblem &d = p->d;
+    const int64_t stride = w ? w->slots * w->LBT * d.Qfp : 0;
+    const int64_t v[8] = {w ? w->gplanes : 0, stride, d.Qfp, w ? w->slots : 0, w ? w->LBT : 0, p->ws_rows, d.Qp, 0};
+    std::copy(v, v + 8, dims);
+    if (!gacc && !G && !F) return GML_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->st));
+    if (gacc && w && w->Gacc && stride) HIPCHK(hipMemcpy(gacc, w->Gacc, sizeof(int32_t) * (size_t)w->gplanes * (size_t)stride, hipMemcpyDeviceToHost));
+    if (G && p->dG && p->ws_rows) HIPCHK(hipMemcpy(G, p->dG, sizeof(double) * (size_t)p->ws_rows * d.Qp, hipMemcpyDeviceToHost));
+    if (F && p->dF && p->ws_rows) HIPCHK(hipMemcpy(F, p->dF, sizeof(double) * (size_t)p->ws_rows, hipMemcpyDeviceToHost));
+    return GML_OK;
+}
+
 // Test hook (not part of include/gml.h): what the last working-set Hessian call (i8_hessian, gml_i8_hess.hip) left in the handle's int8
 // workspace.  Read only: synchronises the handle's stream and copies; launches nothing.
 //   dims [8]: 0 pitch of the weight planes (= Kp; 0: no Hessian call yet), 1 rows the planes are sized for (a multiple of 32), 2 elements
