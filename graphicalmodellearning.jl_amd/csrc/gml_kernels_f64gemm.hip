@@ -133,7 +133,9 @@ __global__ __launch_bounds__(64 * F64_FWD_WAVES, 8 / F64_FWD_WAVES) void k_fwd_f
                         fpart += wk * sp;
                         val = -2.0 * wk * sg * s; // d/dE of w log(1+exp(-2E)), times s
                     } else { // RISE (:196) / logRISE Z (:279)
-                        const double e = wk * exp(-E);
+                        // (w = 0 -- the padding samples, whose energy is the plain sum of the row -- contributes 0 whatever exp(-E) is:
+                        // beyond E = -709.8 the product would be 0 * inf)
+                        const double e = wk != 0.0 ? wk * exp(-E) : 0.0;
                         fpart += e;
                         val = -e * s; // partial_obj (:204) times the node's sign
                     }

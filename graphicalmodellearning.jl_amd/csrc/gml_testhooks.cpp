@@ -329,6 +329,23 @@ extern "C" int gml_test_i8_gacc(gml_problem *p, int64_t *dims, int32_t *gacc, do
     return GML_OK;
 }
 
+// Test hook (not part of include/gml.h): V of the FP64 pass (k_fwd_f64 writes it, k_bwd_f64 and k_hess_f64 read it) as the last pass
+// left it.  Read only: synchronises the handle's stream and copies; launches nothing.
+//   dims [3]: 0 rows V is sized for (0: no FP64 pass yet), 1 Kp, 2 K
+//   V double [dims 0][dims 1] or NULL (only the sizes)
+extern "C" int gml_test_f64_v(gml_problem *p, int64_t *dims, double *V) {
+    if (!p || !dims) return fail(GML_EINVAL, "bad argument");
+    const int64_t rows = p->dV ? p->dVrows : 0;
+    dims[0] = rows;
+    dims[1] = p->d.Kp;
+    dims[2] = p->d.K;
+    if (!V || !rows) return GML_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->st));
+    HIPCHK(hipMemcpy(V, p->dV, sizeof(double) * (size_t)rows * (size_t)p->d.Kp, hipMemcpyDeviceToHost));
+    return GML_OK;
+}
+
 // Test hook (not part of include/gml.h): what the last working-set Hessian call (i8_hessian, gml_i8_hess.hip) left in the handle's int8
 // workspace.  Read only: synchronises the handle's stream and copies; launches nothing.
 //   dims [8]: 0 pitch of the weight planes (= Kp; 0: no Hessian call yet), 1 rows the planes are sized for (a multiple of 32), 2 elements
