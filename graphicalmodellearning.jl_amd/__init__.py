@@ -10,10 +10,12 @@ from .factor_graph import FactorGraph, matrix_to_terms, permutations, check_mode
 from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, GMLMethod,  # noqa: F401
                            logRISE, multiRISE)
 from .learn import learn  # noqa: F401
+from .likelihood import AIS, LogLikelihood, LogPartition, log_likelihood, log_partition  # noqa: F401
 from .path import PathResult, learn_path  # noqa: F401
 from .sampling import GMSampler, Gibbs, Glauber, GlauberChains, GlauberTermChains, TemperedTermChains, sample  # noqa: F401
 
 __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multiRISE", "ISODUS", "GMLMethod",
            "NLP", "HIP", "FactorGraph", "Problem", "MultiProblem", "GMLError", "GMLConvergenceError", "sample", "GMSampler", "Gibbs",
            "Glauber", "GlauberChains", "GlauberTermChains", "TemperedTermChains", "moments", "EXCLUDED", "FREE", "PENALISED",
-           "structure_from_rows", "structure_from_keys", "learn_path", "PathResult"]
+           "structure_from_rows", "structure_from_keys", "learn_path", "PathResult", "AIS", "log_partition", "log_likelihood", "LogPartition",
+           "LogLikelihood"]

@@ -91,6 +91,7 @@ def lib():
                                                        C.POINTER(p)]
     L.gml_problem_create_mcmc_terms_tempered.argtypes = [p, i32, p, i64, i64, i64, i64, i32, i32, p, i32, i32, C.c_uint64, i32, i32, i64,
                                                          i64, i32, p, C.POINTER(p)]
+    L.gml_log_partition_ais.argtypes = [p, i32, p, i64, i64, i64, p, i64, i32, C.c_uint64, i32, p, p, p, p]
     L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -313,6 +314,53 @@ def moment_key_windows(terms, chunk=1 << 22):
     yield keys
 
 
+def term_arrays(terms, n=None):
+    """(keys int32 [T, stride] 0-based with -1 = unused slot, weights float64 [T], stride, n) of a model given as {1-based key tuple:
+    weight} or as an array-backed TermArray: the term list as the C ABI takes it.  n: the number of spins, by default the largest
+    spin named.  Host only."""
+    if hasattr(terms, "keys_array"):
+        # an array-backed learned model (factor_graph.TermArray: millions of terms): its non-zero terms, without a Python loop
+        nz = np.flatnonzero(terms.weights != 0.0)
+        if n is None:
+            n = terms.varible_count
+        stride = terms.order
+        wts = np.ascontiguousarray(terms.weights[nz])
+        keys = np.empty((len(nz), stride), dtype=np.int32)
+        chunk = 1 << 22
+        for a in range(0, len(terms), chunk):  # (the key table is generated window by window: it is never held whole)
+            lo, hi = np.searchsorted(nz, (a, min(len(terms), a + chunk)))
+            if hi > lo:
+                keys[lo:hi] = terms.keys_array(a, min(chunk, len(terms) - a))[nz[lo:hi] - a] - 1
+        if len(nz) == 0:
+            keys, wts = np.array([[0] + [-1] * (stride - 1)], dtype=np.int32), np.zeros(1)
+    else:
+        if n is None:
+            n = max(max(k) for k in terms if len(k))
+        stride = max(1, max(len(k) for k in terms))
+        keys = np.full((len(terms), stride), -1, dtype=np.int32)
+        wts = np.zeros(len(terms), dtype=np.float64)
+        for t, (k, v) in enumerate(terms.items()):
+            keys[t, :len(k)] = np.asarray(k, dtype=np.int64) - 1
+            wts[t] = v
+    return keys, wts, stride, n
+
+
+def log_partition_ais(terms, n, chains, betas, sweeps_per_step=1, seed=0, device=0, return_states=False):
+    """gml_log_partition_ais on a term list as term_arrays takes it: (result [3] = log Z, its standard error, the effective sample
+    size; log_weights [chains]; energies [chains] and spins [chains, n] int8 with return_states, else None)."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    betas = np.ascontiguousarray(betas, dtype=np.float64).ravel()
+    chains = int(chains)
+    if not 1 <= chains <= 2 ** 31:  # (the library's own check, made before the output arrays are)
+        raise GMLError(GML_EINVAL, f"chains must lie in [1, 2^31] (given {chains})")
+    logw, result = np.zeros(chains), np.zeros(3)
+    energies = np.zeros(chains) if return_states else None
+    spins = np.zeros((chains, int(n)), dtype=np.int8) if return_states else None
+    check(lib().gml_log_partition_ais(_ptr(keys), stride, _ptr(wts), len(wts), int(n), chains, _ptr(betas), len(betas),
+                                      int(sweeps_per_step), int(seed), int(device), _ptr(logw), _ptr(energies), _ptr(spins), _ptr(result)))
+    return result, logw, energies, spins
+
+
 class Problem:
     """RAII wrapper of a gml_problem handle (packed spins + weights resident in HBM)."""
 
@@ -389,30 +437,7 @@ class Problem:
                                               C.byref(h)))
         elif terms is not None:
             # sample on the device from a model of any order given as {1-based key tuple: weight}: sampling.jl:60-88
-            if hasattr(terms, "keys_array"):
-                # an array-backed learned model (factor_graph.TermArray: millions of terms): its non-zero terms, without a Python loop
-                nz = np.flatnonzero(terms.weights != 0.0)
-                if n is None:
-                    n = terms.varible_count
-                stride = terms.order
-                wts = np.ascontiguousarray(terms.weights[nz])
-                keys = np.empty((len(nz), stride), dtype=np.int32)
-                chunk = 1 << 22
-                for a in range(0, len(terms), chunk):  # (the key table is generated window by window: it is never held whole)
-                    lo, hi = np.searchsorted(nz, (a, min(len(terms), a + chunk)))
-                    if hi > lo:
-                        keys[lo:hi] = terms.keys_array(a, min(chunk, len(terms) - a))[nz[lo:hi] - a] - 1
-                if len(nz) == 0:
-                    keys, wts = np.array([[0] + [-1] * (stride - 1)], dtype=np.int32), np.zeros(1)
-            else:
-                if n is None:
-                    n = max(max(k) for k in terms if len(k))
-                stride = max(1, max(len(k) for k in terms))
-                keys = np.full((len(terms), stride), -1, dtype=np.int32)
-                wts = np.zeros(len(terms), dtype=np.float64)
-                for t, (k, v) in enumerate(terms.items()):
-                    keys[t, :len(k)] = np.asarray(k, dtype=np.int64) - 1
-                    wts[t] = v
+            keys, wts, stride, n = term_arrays(terms, n)
             n0, n1 = _node_range(node_range, n)
             if mcmc_betas is not None:  # replica exchange on the same chains: ladders of len(betas) rungs, rung 0 recorded
                 betas = np.ascontiguousarray(mcmc_betas, dtype=np.float64).ravel()

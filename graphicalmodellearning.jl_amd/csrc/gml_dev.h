@@ -235,6 +235,13 @@ void launch_term_chains(const TermChainSpin *dspin, const unsigned *drec, int64_
 void launch_tempered_chains(const TermChainSpin *dspin, const unsigned *drec, int64_t n, int64_t ladders, int replicas,
                             const double *dbetas, int swap_every, int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout,
                             int64_t ld, unsigned long long *dswap_counts, hipStream_t st);
+// Annealed importance sampling on the same records (gml_ais_chains.hip): one lane per chain on the tile term_chains_tile(n, chains),
+// walked along dbetas[0 .. nbetas) with `sps` sweeps per step.  dspin0: the spin records of the start energy -- a_i, sigma_i of
+// dspin, Q and record offsets over the incidences whose other spins are all above i -- into the same stream drec.  dlogw / dE
+// [chains]; dstates [chains][n] row-major +-1 bytes, or NULL.
+void launch_ais_chains(const TermChainSpin *dspin, const TermChainSpin *dspin0, const unsigned *drec, int64_t n, int64_t chains,
+                       const double *dbetas, int64_t nbetas, int sps, unsigned long long seed, double *dlogw, double *dE,
+                       int8_t *dstates, hipStream_t st);
 
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].

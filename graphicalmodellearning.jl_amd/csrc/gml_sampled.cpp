@@ -125,6 +125,11 @@ struct SamplerStaging {
             rc = fail(e == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", call, hipGetErrorString(e));
         return rc == GML_OK;
     }
+    // no handle (gml_log_partition_ais): the device and a stream for upload / alloc / sync; the destructor releases as always
+    int open(int device) {
+        if (ok(hipSetDevice(device), "hipSetDevice")) ok(hipStreamCreate(&st), "hipStreamCreate");
+        return rc;
+    }
     // the handle's K rows of n spins; out_bytes of output, cleared if the sampler does not write all of them
     int begin(int device, int64_t K, int64_t n, int order, int64_t node0, int64_t node1, size_t out_bytes, bool clear) {
         if (!ok(hipSetDevice(device), "hipSetDevice")) return rc;
@@ -367,7 +372,9 @@ extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, in
 // The model of gml_problem_create_mcmc_terms_chains.  The couplings of every spin are quantised: sigma_i = 2^(E - 38) with
 // max_e |w_e| < 2^E over its incidences with other spins, q_e = rint(w_e / sigma_i), and the incidences grouped by arity into the
 // record stream of TermChainSpin (gml_dev.h): per spin a_i, sigma_i, Q_i and the records (q_e 2^24 + j_1 as two words, then j_2 .. j_k).
-static void build_spin_records(const Incidences &inc, std::vector<TermChainSpin> &spin, std::vector<unsigned> &rec) {
+// The records are appended to rec.  upper: a_i and sigma_i as always, but Q_i and the records cover only the incidences whose other
+// spins are all above i -- every term once, at its smallest spin (the start energy of gml_log_partition_ais).
+static void build_spin_records(const Incidences &inc, std::vector<TermChainSpin> &spin, std::vector<unsigned> &rec, bool upper = false) {
     const int64_t n = (int64_t)inc.size();
     spin.assign((size_t)n, TermChainSpin{});
     for (int64_t i = 0; i < n; ++i) {
@@ -386,6 +393,7 @@ static void build_spin_records(const Incidences &inc, std::vector<TermChainSpin>
         for (int k = 1; k <= kTermChainsMaxOthers; ++k) {
             for (auto &e : inc[(size_t)i]) {
                 if (e.second.size() != (size_t)k) continue;
+                if (upper && *std::min_element(e.second.begin(), e.second.end()) < i) continue;
                 const long long q = (long long)std::nearbyint(std::ldexp(e.first, 38 - ex));
                 Q += q;
                 const unsigned long long P = ((unsigned long long)q << 24) | (unsigned long long)e.second[0];
@@ -502,6 +510,74 @@ extern "C" int gml_problem_create_mcmc_terms_tempered(const int32_t *keys, int k
     if (int rc = s.finish(true, ld, histogram != 0, out)) return rc; // the recorded states of rung 0, spin-major
     if (swap_counts)
         for (size_t k = 0; k < ncounts; ++k) swap_counts[k] = (int64_t)counts[k];
+    return GML_OK;
+}
+
+// the schedule of gml_log_partition_ais: at least two finite betas >= 0, the first 0; a sweep count that fits the chains' counter
+static int check_schedule(const double *betas, int64_t nbetas, int sweeps_per_step) {
+    if (!betas) return fail(GML_EINVAL, "betas is NULL");
+    if (nbetas < 2) return fail(GML_EINVAL, "nbetas must be at least 2 (given %lld)", (long long)nbetas);
+    if (sweeps_per_step < 1) return fail(GML_EINVAL, "sweeps_per_step must be at least 1");
+    if (nbetas - 1 > (int64_t)INT32_MAX / sweeps_per_step) return fail(GML_EINVAL, "(nbetas - 1) * sweeps_per_step exceeds 2^31 - 1 sweeps");
+    for (int64_t t = 0; t < nbetas; ++t)
+        if (!std::isfinite(betas[t]) || betas[t] < 0.0) return fail(GML_EINVAL, "betas[%lld] is negative or not finite", (long long)t);
+    if (betas[0] != 0.0) return fail(GML_EINVAL, "betas[0] must be 0 (the chains start from an exact draw at beta = 0)");
+    return GML_OK;
+}
+
+// gml_log_partition_ais: annealed importance sampling of any term list (gml_ais_chains.hip); the estimate itself on the host.
+extern "C" int gml_log_partition_ais(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t chains,
+                                     const double *betas, int64_t nbetas, int sweeps_per_step, uint64_t seed, int device,
+                                     double *log_weights, double *energies, int8_t *spins, double *result) {
+    if (!log_weights) return fail(GML_EINVAL, "log_weights is NULL");
+    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
+    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
+    if (chains < 1 || chains > (int64_t)1 << 31) return fail(GML_EINVAL, "chains must lie in [1, 2^31] (given %lld)", (long long)chains);
+    if (int rc = check_schedule(betas, nbetas, sweeps_per_step)) return rc;
+    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
+    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
+        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
+                    (long long)n);
+    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
+    // one stream of records, two sets of spin records into it: the fields, and every term once for the start energy
+    std::vector<TermChainSpin> spin, spin0;
+    std::vector<unsigned> rec;
+    {
+        const Incidences inc = build_incidences(keys, key_stride, weights, nterms, n);
+        build_spin_records(inc, spin, rec);
+        build_spin_records(inc, spin0, rec, true);
+    }
+    if (int rc = gml_check_device(device)) return rc;
+    const std::vector<double> schedule(betas, betas + nbetas);
+    SamplerStaging s;
+    if (int rc = s.open(device)) return rc;
+    const TermChainSpin *dspin = s.upload(spin), *dspin0 = s.upload(spin0);
+    const unsigned *drec = s.upload(rec);
+    const double *dbetas = s.upload(schedule);
+    double *dlogw = s.alloc<double>((size_t)chains), *dE = energies ? s.alloc<double>((size_t)chains) : nullptr;
+    int8_t *dstates = spins ? s.alloc<int8_t>((size_t)chains * (size_t)n) : nullptr;
+    if (s.rc) return s.rc;
+    launch_ais_chains(dspin, dspin0, drec, n, chains, dbetas, nbetas, sweeps_per_step, (unsigned long long)seed, dlogw, dE, dstates, s.st);
+    s.ok(hipGetLastError(), "the sampler's launch");
+    s.ok(hipMemcpyAsync(log_weights, dlogw, sizeof(double) * (size_t)chains, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    if (energies) s.ok(hipMemcpyAsync(energies, dE, sizeof(double) * (size_t)chains, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    if (spins) s.ok(hipMemcpyAsync(spins, dstates, (size_t)chains * (size_t)n, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    if (s.sync()) return s.rc;
+    if (result) {
+        // log of the mean weight around the largest one, its delta-method standard error, the effective sample size; chain order
+        double m = log_weights[0];
+        for (int64_t c = 1; c < chains; ++c) m = std::max(m, log_weights[c]);
+        double s1 = 0.0, s2 = 0.0;
+        for (int64_t c = 0; c < chains; ++c) {
+            const double x = std::exp(log_weights[c] - m);
+            s1 += x;
+            s2 += x * x;
+        }
+        const double mean = s1 / (double)chains;
+        result[0] = (double)n * std::log(2.0) + m + std::log(mean);
+        result[1] = chains > 1 ? std::sqrt(std::max(s2 / (double)chains - mean * mean, 0.0) / (double)(chains - 1)) / mean : 0.0;
+        result[2] = s1 * s1 / s2;
+    }
     return GML_OK;
 }
 

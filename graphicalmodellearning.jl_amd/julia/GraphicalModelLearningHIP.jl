@@ -16,7 +16,7 @@ module GraphicalModelLearningHIP
 using GraphicalModelLearning
 import GraphicalModelLearning: learn, GMLMethod, GMLFormulation, RISE, RISEA, logRISE, RPLE, multiRISE, FactorGraph
 
-export HIP, trim_cache
+export HIP, trim_cache, log_partition
 
 const libgml = get(ENV, "LIBGML_HIP", "libgml_hip.so")
 
@@ -182,6 +182,39 @@ function stderr(samples::Array{T,2}, formulation, rows::Array{Float64,2}; method
     finally
         ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
     end
+end
+
+"""
+    log_partition(terms::Dict, n; chains=4096, steps=1000, sweeps_per_step=1, betas=nothing, seed=0, device=0)
+        -> (log_z, stderr, ess, log_weights)
+
+log Z of a model of `n` spins given as `Dict(key tuple (1-based spins) => weight)` by annealed importance sampling on the device
+(gml_log_partition_ais, include/gml.h): `chains` chains walked along `betas` (default `range(0, 1; length = steps + 1)`; the first
+must be 0) with `sweeps_per_step` sweeps at each.  AIS is unbiased for Z, so log_z is biased low; `stderr` is the delta-method
+standard error of the chains' weights and does not see a well that no chain found; `ess` near 1 asks for a longer schedule.
+Marshalling only.
+"""
+function log_partition(terms::Dict, n::Integer; chains::Integer=4096, steps::Integer=1000, sweeps_per_step::Integer=1,
+                       betas::Union{Nothing,AbstractVector{<:Real}}=nothing, seed::Integer=0, device::Integer=0)
+    stride = max(1, maximum(length, keys(terms); init=1))
+    keymat = fill(Int32(-1), stride, length(terms))       # Julia (stride x T) == C row-major (T x stride); 0-based, -1 = unused
+    weights = Vector{Float64}(undef, length(terms))
+    for (t, (key, w)) in enumerate(terms)
+        for (a, v) in enumerate(key)
+            keymat[a, t] = Int32(v - 1)
+        end
+        weights[t] = w
+    end
+    b = betas === nothing ? collect(range(0.0, 1.0; length=steps + 1)) : convert(Vector{Float64}, betas)
+    logw = Vector{Float64}(undef, chains)
+    result = zeros(Float64, 3)
+    rc = ccall((:gml_log_partition_ais, libgml), Cint,
+               (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Int64, Cint, UInt64, Cint,
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int8}, Ptr{Cdouble}),
+               keymat, stride, weights, length(weights), n, chains, b, length(b), sweeps_per_step, seed, device,
+               logw, C_NULL, C_NULL, result)
+    rc == GML_OK || error("gml_log_partition_ais: $(lasterr())")
+    return result[1], result[2], result[3], logw
 end
 
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)

@@ -1,0 +1,93 @@
+"""log_partition(model) and log_likelihood(data, model): how well a model explains data.
+
+(1/M) sum_k c_k log P(s_k) = sum_t w_t <prod_{i in t} s_i>_data - log Z.  The first part is exact (Problem.term_moments: integer
+sums on the device); log Z is estimated by annealed importance sampling on the device (gml_log_partition_ais: the term-list chains
+walked from beta = 0 to beta = 1 with a running weight).  AIS is unbiased for Z, hence biased low for log Z: the likelihood is an
+optimistic one, and the standard error does not see a well that no chain found (include/gml.h)."""
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .sampling import _problem_args, _term_list_args
+
+
+class AIS:
+    """Annealed importance sampling: `chains` chains, each walked along the inverse temperatures `betas` with `sweeps_per_step`
+    sweeps at each.  betas=None: `steps` equal steps from 0 to 1, np.linspace(0, 1, steps + 1).  A given schedule starts at 0, has at
+    least two values, all finite and >= 0; it need not be monotone, and its last value is the beta whose log Z is estimated."""
+
+    def __init__(self, chains=4096, steps=1000, sweeps_per_step=1, betas=None):
+        self.chains, self.sweeps_per_step = int(chains), int(sweeps_per_step)
+        if self.chains < 1 or self.sweeps_per_step < 1:
+            raise ValueError(f"chains and sweeps_per_step must be at least 1 (given {chains}, {sweeps_per_step})")
+        if betas is None:
+            if int(steps) < 1:
+                raise ValueError(f"steps must be at least 1 (given {steps})")
+            self.betas = np.linspace(0.0, 1.0, int(steps) + 1)
+        else:
+            self.betas = np.array(betas, dtype=np.float64).ravel()
+            if len(self.betas) < 2 or self.betas[0] != 0.0 or not np.isfinite(self.betas).all() or (self.betas < 0.0).any():
+                raise ValueError("betas must start at 0, have at least two values and be finite and non-negative")
+        self.steps = len(self.betas) - 1
+
+
+@dataclass
+class LogPartition:
+    """log_z: the estimate; stderr: its delta-method standard error; ess: the effective sample size of the chains' weights (near 1:
+    the schedule is too short); log_weights [chains].  energies [chains] and spins [chains, n] (the chains' final states and their
+    energies) with return_states, else None."""
+    log_z: float
+    stderr: float
+    ess: float
+    log_weights: np.ndarray
+    energies: np.ndarray = None
+    spins: np.ndarray = None
+
+
+@dataclass
+class LogLikelihood:
+    """mean: the log-likelihood per sample, data_term - log_z; total = M mean; data_term = sum_t w_t <prod s>_data (exact sums);
+    log_z and stderr: the estimate of log Z used and its standard error (NaN for a log_z given as a plain number)."""
+    mean: float
+    total: float
+    data_term: float
+    log_z: float
+    stderr: float
+
+
+def _model_terms(model):
+    """(terms, n) of a FactorGraph, a term dict or a matrix: the term list the chains run on (n None: the largest spin named)"""
+    args = _term_list_args(model, _problem_args(model))
+    return args["terms"], args.get("n")
+
+
+def log_partition(model, method=None, *, seed=0, device=0, return_states=False):
+    """log Z of `model` (a FactorGraph, a {1-based key tuple: weight} dict or a matrix with the fields on its diagonal) by annealed
+    importance sampling on the device; method: an AIS (default AIS()).  Returns a LogPartition."""
+    method = AIS() if method is None else method
+    if not isinstance(method, AIS):
+        raise ValueError(f"log_partition takes an AIS method, given {type(method).__name__}")
+    terms, n = _model_terms(model)
+    result, logw, energies, spins = _lib.log_partition_ais(terms, n, method.chains, method.betas, method.sweeps_per_step, seed=seed,
+                                                           device=device, return_states=return_states)
+    return LogPartition(float(result[0]), float(result[1]), float(result[2]), logw, energies, spins)
+
+
+def log_likelihood(data, model, method=None, *, log_z=None, seed=0, device=0):
+    """The log-likelihood of `data` (a K x (1+n) histogram matrix as learn() takes, or an open Problem) under `model`.  log_z: a
+    LogPartition (or a number) to reuse across data sets -- the folds of Problem.split, say; None: log_partition(model, method).
+    Handles with fractional counts are refused by term_moments, whose error comes through unchanged.  Returns a LogLikelihood."""
+    terms, _ = _model_terms(model)
+    w = np.ascontiguousarray(terms.weights if hasattr(terms, "keys_array") else list(terms.values()), dtype=np.float64)
+    if isinstance(data, _lib.Problem):
+        sums, M = data.term_moments(terms, raw=True), data.M
+    else:
+        with _lib.Problem(data, device=device) as p:
+            sums, M = p.term_moments(terms, raw=True), p.M
+    data_term = float(np.dot(w, sums.astype(np.float64))) / M
+    if log_z is None:
+        log_z = log_partition(model, method, seed=seed, device=device)
+    lz, se = (log_z.log_z, log_z.stderr) if isinstance(log_z, LogPartition) else (float(log_z), float("nan"))
+    mean = data_term - lz
+    return LogLikelihood(mean, M * mean, data_term, lz, se)

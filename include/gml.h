@@ -317,6 +317,54 @@ int gml_problem_create_mcmc_terms_tempered(const int32_t *keys, int key_stride, 
                                            int64_t node1, int device, int64_t *swap_counts, gml_problem **out);
 
 /*
+ * gml_log_partition_ais -- log Z of ANY term list by annealed importance sampling (AIS): the missing half of the log-likelihood
+ *   (1/M) sum_k c_k log P(s_k) = sum_t w_t <prod_{i in t} s_i>_data - log Z,
+ * whose first half gml_problem_term_moments gives exactly.  Enumeration stops at about 22 spins; this is the term-list chain walked
+ * from beta = 0 to the last beta with a running weight.  No handle is made; all pointers are host pointers.
+ * Model.  The term list, incidences, a_i, sigma_i, q_e and the exact int64 field h_i are those of
+ * gml_problem_create_mcmc_terms_chains.  E(s) = - sum_t w_t prod_{i in t} s_i.
+ * Arguments and start.  betas[0 .. nbetas) must have nbetas >= 2 and betas[0] == 0.0.  Every value must be finite and >= 0.  The
+ * sequence need not be monotone.  The estimate is of log Z(betas[nbetas-1]), normally 1.0.  Chain c starts like every chain here:
+ * spin i is +1 iff u01(seed, 0xFFFFFFFF, c n + i) < 0.5.  That is an exact draw at beta = 0.
+ * Start energy.  Every term is counted once, at the smallest spin it names, with that spin's quantisation.
+ *   S_i = sum q_e prod_{j in others(e)} s_j over the incidences e of spin i whose other spins are all > i.  The sum is exact in
+ *         int64 and converted to double once.
+ *   t_i = a_i + sigma_i * (double)S_i.  sigma_i is a power of two, so this is one rounding.
+ *   E = 0.0, then for i = 0 .. n-1 in order: E = E - s_i * t_i.  The product is exact.
+ * Steps.  logw = 0.0, sw = 0.  For t = 1 .. nbetas-1:
+ *   logw = logw - (betas[t] - betas[t-1]) * E.  The difference is rounded, the product is rounded, then the subtraction is rounded.
+ *         No fused multiply-add is allowed on this line.  Every other FP64 product in the contract is exact, so contraction cannot
+ *         change it.
+ *   Then sweeps_per_step sweeps.  Each sweep updates spins 0 .. n-1 in order:
+ *         pup = 1.0 / (1.0 + exp(-2.0 * (betas[t] * h_i))),  s_i = +1 iff u01(seed, sw, c n + i) < pup,
+ *         E = E - (s_new - s_old) * h_i;
+ *         sw += 1 after each sweep.
+ * Outputs.  log_weights[c] = logw.  energies[c] = E at the end.  spins holds the final states.  All three depend only on (model,
+ * seed, betas, sweeps_per_step, chain index).  They do not depend on the order of terms with other spins, the tile, the grid or the
+ * device.
+ * result.  Computed on the host in FP64, in chain order:
+ *   m = max logw, x_c = exp(logw_c - m), s1 = sum x_c, s2 = sum x_c^2.
+ *   result[0] = n * log(2.0) + m + log(s1 / chains).
+ *   result[1] is the delta-method standard error sqrt((s2/chains - (s1/chains)^2) / (chains - 1)) / (s1/chains).  It is 0 when
+ *             chains = 1 (and a difference that rounds below 0 counts as 0).
+ *   result[2] = s1^2 / s2, the effective sample size.
+ * What the numbers mean.  AIS is unbiased for Z.  It is therefore biased LOW for log Z in expectation (Jensen), and a likelihood
+ * built on it is an optimistic one.  The standard error is that of the weights the chains produced: it does not see a well that no
+ * chain found.  An effective sample size near 1 says the schedule is too short.
+ * GML_EINVAL, before any HIP call: NULL keys, weights, betas or log_weights; key_stride < 1, nterms < 0, a spin outside [0, n), a
+ * non-finite weight, n < 1; chains < 1 or > 2^31; nbetas < 2; betas[0] != 0; a negative or non-finite beta; sweeps_per_step < 1;
+ * (nbetas - 1) * sweeps_per_step > 2^31 - 1.  GML_EUNSUPPORTED (before any HIP call, the limit named): n > 16384, a term with more than
+ * 8 distinct spins after cancellation, 2^24 or more incidences with other spins on one spin.  The device is looked for last.
+ * Cost: that of (nbetas - 1) * sweeps_per_step sweeps of gml_problem_create_mcmc_terms_chains over `chains` chains, plus one pass
+ * over the terms for the start energy.  Device memory (the model's records twice, 16 bytes and n bytes per chain) is released
+ * before the call returns.
+ */
+int gml_log_partition_ais(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t chains,
+                          const double *betas, int64_t nbetas, int sweeps_per_step, uint64_t seed, int device,
+                          double *log_weights /* [chains], host */, double *energies /* [chains] or NULL */,
+                          int8_t *spins /* [chains][n] row-major, +-1, or NULL */, double *result /* [3] or NULL */);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
