@@ -246,6 +246,15 @@ def learn_multi_rows(samples, c=0.4, order=2, tol=1e-12):
     return out, kkt
 
 
+def mean_in_order(v):
+    """`mean` of a Vector{Real} (:147): the sum taken left to right, one division.  np.mean is NOT that from eight values on -- numpy
+    sums on eight interleaved accumulators there -- and a key of eight spins has eight members."""
+    s = 0.0
+    for x in v:
+        s += float(x)
+    return s / len(v)
+
+
 def assemble_multi_dict(rows, keys, symmetrize):
     """The tail of learn(samples, ::multiRISE, ...) restated (:129-151): rows[r] holds the solved parameters of one node in the
     order of keys[r] (0-based tuples (u, ascending others)); returns the reference's Dict {1-based key tuple: value}, symmetrised
@@ -258,7 +267,7 @@ def assemble_multi_dict(rows, keys, symmetrize):
         groups = {}
         for k, v in rec.items():
             groups.setdefault(tuple(sorted(k)), []).append(v)
-        rec = {k: float(np.mean(v)) for k, v in groups.items()}
+        rec = {k: mean_in_order(v) for k, v in groups.items()}
     return rec
 
 
@@ -284,5 +293,5 @@ def learn_multi(samples, c=0.4, symmetrize=True, order=2, tol=1e-12):
         groups = {}
         for k, v in rec.items():
             groups.setdefault(tuple(sorted(k)), []).append(v)
-        rec = {k: float(np.mean(v)) for k, v in groups.items()}
+        rec = {k: mean_in_order(v) for k, v in groups.items()}
     return rec, kkt

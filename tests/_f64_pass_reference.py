@@ -1,6 +1,7 @@
 """Host model of the FP64 pass (k_fwd_f64 and k_bwd_f64, csrc/gml_kernels_f64gemm.hip) in np.longdouble, written from the kernels'
 comments; it imports and calls nothing compiled from them.  The design matrix in internal column order comes from
-tests/_i8_pack_reference.py (stat_keys, stat_bits), to which tests/test_gpu_i8_pack_state.py holds the device's Xb and Xtb images.
+tests/_i8_pack_reference.py (stat_keys, stat_bits), to which tests/test_gpu_i8_pack_state.py holds the device's Xb and Xtb images;
+a parameter's column is found by looking the other spins of its key up in stat_keys, at any interaction order (Shape.colidx).
 tests/test_host_f64_pass_reference.py holds this file to a brute-force triple loop; tests/test_gpu_f64_pass_exact.py holds the
 device to it.
 
@@ -104,7 +105,22 @@ def _row_list(n, count, seed):
 
 #        n, order, K, rows (None: all nodes), zero counts, seed
 SHAPES = {"S1": (5, 2, 37, None, 0, 1), "S2": (70, 2, 700, 45, 2, 2), "S3": (100, 2, 4500, None, 3, 3), "S4": (48, 3, 1100, 40, 2, 4),
-          "S5": (40, 2, 6200, None, 0, 5), "T2": (4, 2, 11, None, 1, 6), "T3": (4, 3, 11, None, 0, 7)}  # (T2, T3: the host test's)
+          "S5": (40, 2, 6200, None, 0, 5), "T2": (4, 2, 11, None, 1, 6), "T3": (4, 3, 11, None, 0, 7),  # (T2, T3: the host test's)
+          # orders 5 to 8: keys of four to seven spins besides the node's own, and an order above n (keys that are mostly -1)
+          "H5": (11, 5, 1500, None, 2, 8), "H6": (10, 6, 1100, None, 2, 9), "H7": (12, 7, 700, None, 1, 10), "H8": (9, 8, 2100, None, 2, 11),
+          "E7": (7, 8, 300, None, 1, 12), "E3": (3, 8, 40, None, 1, 13), "T5": (5, 5, 13, None, 0, 14)}  # (T5: the host test's)
+HIGH = ["H5", "H6", "H7", "H8", "E7", "E3"]
+
+
+def closed_form_column(n, rest, cconst):
+    """the column of the statistic of the spins `rest` (ascending, at most two) in closed form: what Shape.column computed before it
+    looked the key up in stat_keys; tests/test_host_f64_pass_reference.py holds the lookup to it at orders 2 and 3"""
+    if not rest:
+        return cconst
+    if len(rest) == 1:
+        return rest[0]
+    a, b = rest
+    return n + a * n - a * (a + 1) // 2 + (b - a - 1)
 
 
 class Shape:
@@ -134,6 +150,7 @@ class Shape:
         sb[:, :K] = self.spins.T
         self.S = sb[self.nodes]  # [R][Kp] the rows' own spins
         self.real = np.arange(self.Kp) < K
+        self.colidx = {tuple(int(i) for i in k if i >= 0): c for c, k in enumerate(self.keys)}  # sorted key -> column, any order
         if self.order == 2:
             self.P = n
         else:
@@ -145,13 +162,8 @@ class Shape:
         """internal column of parameter j (reference order) of node u"""
         if self.order == 2:
             return self.cconst if j == u else j
-        rest = sorted(i for i in self.pkeys[u][j] if i != u)
-        if not rest:
-            return self.cconst
-        if len(rest) == 1:
-            return rest[0]
-        a, b = rest
-        return self.n + a * self.n - a * (a + 1) // 2 + (b - a - 1)
+        rest = tuple(sorted(i for i in self.pkeys[u][j] if i != u))
+        return self.colidx[rest] if rest else self.cconst
 
     def cols(self, u):
         return np.array([self.column(int(u), j) for j in range(self.P)])

@@ -7,6 +7,7 @@ import itertools
 
 import numpy as np
 
+import _high_order_cases as H
 import _sampler_reference as R
 from conftest import MODELS
 
@@ -61,6 +62,16 @@ def _steep10():
     return [((2 * i,), 80.0 * (-1) ** i) for i in range(5)] + [((2 * i + 1,), 0.3) for i in range(5)]
 
 
+def _wide12():
+    """terms of 5 to 8 spins on 12: masks of five to eight bits (the keys that name a spin twice are reduced here, as the host half
+    reduces them before the kernels see a mask)"""
+    out = []
+    for key, w in H.wide_terms(12, 12, scale=0.15).items():
+        odd = sorted(i - 1 for i in set(key) if key.count(i) % 2)
+        out.append((tuple(odd), w))
+    return out
+
+
 BLOCK_MODELS = {
     "isolated_sb1": (1, lambda: []),
     "field_sb1": (1, lambda: [((0,), 0.7)]),
@@ -70,6 +81,7 @@ BLOCK_MODELS = {
     "subsets_sb13": (13, _subsets13),
     "chain_sb22": (22, _chain22),
     "steep_sb10": (10, _steep10),
+    "wide_sb12": (12, _wide12),
 }
 # (N, seed, block) of the launches of every block model: each N, each seed and each stream at least once
 BLOCK_RUNS = ((1, SEEDS[0], 0), (257, SEEDS[1], 3), (20000, SEEDS[0], 3), (20000, SEEDS[1], 0))
@@ -183,6 +195,18 @@ def _twins():
     return terms, 8, 2000
 
 
+def _wide19():
+    """a component of 12 spins held together by terms of 5 to 8 spins (cancellations included), one of 6 spins under a single
+    6-spin term and its fields, and spin 19 alone; the spins of the two components interleaved"""
+    big = [1, 2, 4, 5, 7, 8, 10, 11, 13, 14, 16, 17]
+    small = [3, 6, 9, 12, 15, 18]
+    terms = H.wide_terms(19, 19, spins=big, scale=0.15)
+    terms[tuple(reversed(small))] = 0.4
+    terms[(3,)] = -0.2
+    terms[(19, 19)] = 0.3  # the empty term
+    return terms, 19, 3001
+
+
 EXACT_CASES = {
     "interleaved29": _interleaved29,
     "blocks64": _blocks64,
@@ -191,6 +215,7 @@ EXACT_CASES = {
     "n1": lambda: ({(1,): 0.4}, 1, 2000),
     "rings33": lambda: ({k: w for off in (0, 11, 22) for k, w in
                          [((off + i + 1, off + (i + 1) % 11 + 1), 0.3 + 0.01 * i) for i in range(11)] + [((off + 1,), 0.2)]}, 33, 3000),
+    "wide19": _wide19,
 }
 
 
@@ -240,6 +265,7 @@ GLAUBER_CASES = {
     "one_chain12": lambda: (sparse3(12, 12), 12, 1, 1),
     "dyadic33": lambda: (sparse3(33, 34, dyadic=True, skip=(8,)), 33, 1000, 7),
     "ring64": lambda: (ring(64), 64, 5000, 6),
+    "wide24": lambda: (H.wide_terms(24, 24, scale=0.2), 24, 1000, 5),  # terms of 5 to 8 spins, cancellations included
 }
 
 

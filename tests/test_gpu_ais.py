@@ -8,6 +8,7 @@ import pytest
 
 import gml_amd as gml
 from gml_amd import _lib
+from _high_order_cases import wide_terms
 from _ais_reference import ais, exact_log_z, lattice, sparse_model, summary
 from _tempered_reference import bimodal_16
 
@@ -46,6 +47,7 @@ CASES = {
     "n1": lambda: ({(1,): 0.3}, 1),
     "n33": lambda: (sparse_model(33, 6, 4, 0.3, 4), 33),
     "two_8_spin_terms_n20": lambda: (two_8_spin_terms(), 20),
+    "orders_5_to_8_cancelled_n12": lambda: (wide_terms(12, 5), 12),  # terms of 5 to 8 spins, some through keys that name a spin twice
 }
 
 

@@ -11,6 +11,14 @@ Shapes (tests/_f64_pass_reference.py: SHAPES; counts are integers over three dec
   S4  n = 48,  order 3, K = 1100 (Kp 2048), 40 rows:      Qf = 1176 statistics columns: two backward column blocks, six waves of the
                                                           second leave at once beside two that reach the barriers; 19 forward column steps
   S5  n = 40,  order 2, K = 6200 (Kp 7168), all rows:     split-K with UNEQUAL chunks (2432, 2432, 2304): the smallest Kp that has them
+Orders 5 to 8, all rows, iid spins (keys of four to seven spins besides the node's own: stat_word's XOR of up to seven rows of Sb, the
+column walk of gml_node_cols up to q = 7):
+  H5  n = 11, order 5, K = 1500 (Kp 2048): Qf = 561 -> 576 (15 padding columns, 9 column steps), P = 386
+  H6  n = 10, order 6, K = 1100 (Kp 2048): Qf = 637 -> 640 (3 padding columns), P = 382
+  H7  n = 12, order 7, K = 700  (Kp 1024): Qf = 2509 -> 2560 (40 column steps, a third 1024-column block in k_bwd_f64), P = 1486
+  H8  n = 9,  order 8, K = 2100 (Kp 3072): Qf = 501 -> 512, P = 255: the largest order
+  E7  n = 7,  order 8, K = 300:  order = n + 1: every non-empty subset is a column (127 -> 128), P = 64
+  E3  n = 3,  order 8, K = 40:   order far above n: seven key slots, at most three used; Qf = 7 -> 64, P = 4
 The long-double comparisons and the exact tests cover every row of every shape (S4's 40 rows in long double take about a second
 per case on the host).
 
@@ -38,7 +46,7 @@ from test_gpu_i8_pass_variants import i8_pass, need_ld
 _lib = importlib.import_module("gml_amd._lib")
 LD = np.longdouble
 U = F.U
-NAMES = ["S1", "S2", "S3", "S4", "S5"]
+NAMES = ["S1", "S2", "S3", "S4", "S5"] + F.HIGH
 FORMS = ["RISE", "logRISE", "RPLE"]
 FAMILIES = ["dyadic", "dense", "sparse", "big"]
 

@@ -27,6 +27,7 @@ import math
 import numpy as np
 import pytest
 
+import _f64_pass_reference as F
 import _i8_pack_reference as R
 import gml_amd as gml
 from oracle import oracle as O
@@ -254,6 +255,40 @@ def test_bit_images_order3():
         want = R.xc_image(B, st.Kp, 1, cm)
         assert want.any() and np.array_equal(st.xc[:want.size], want), "Xc"
     _report_tau("bit images, order 3")
+
+
+@pytest.mark.parametrize("name", F.HIGH)
+def test_layout_keys_and_bit_images_orders_5_to_8(name):
+    """The shapes H5 .. H8, E7, E3 of tests/_f64_pass_reference.py (orders 5 to 8; E7, E3: an order above n): P and every node's keys
+    against the oracle's, then Sb, Xb and Xtb -- padding columns and padding samples included -- against the images of
+    stat_bits over stat_keys (itertools.combinations by size): a statistic's bit is the XOR of up to seven rows of Sb."""
+    sh = F.Shape(name, O.multi_keys)
+    n, order = sh.n, sh.order
+    with gml.Problem(spins=sh.spins, counts=sh.counts, order=order) as p:
+        assert p.P == sh.P == len(O.multi_keys(n, order, 0))
+        for u in range(n):
+            ka = p.multi_keys_array(u)
+            want = O.multi_keys(n, order, u)
+            assert ka.shape == (sh.P, order)
+            assert [tuple(int(v) for v in row if v >= 0) for row in ka] == want, (name, u)
+            assert all((row[len(k):] == -1).all() and (row[:len(k)] >= 0).all() for row, k in zip(ka, want)), (name, u, "unused slots")
+        assert np.array_equal(p.spins(), sh.spins)
+        sb = np.zeros((n, sh.Kp // 32), dtype=np.uint32)
+        neg = np.zeros((n, sh.Kp), dtype=np.uint32)
+        neg[:, :sh.K] = sh.spins.T < 0
+        for b in range(32):
+            sb |= neg[:, b::32] << np.uint32(b)
+        assert np.array_equal(p.sign_bits(), sb), "Sb"  # (bit b of word w: sample 32 w + b; the padding samples are zero bits)
+        th = np.random.default_rng(50).normal(scale=0.01, size=(n, sh.P))
+        i8_pass(p, "RISE", "i8w", np.arange(n, dtype=np.int64), th)
+        st = State(p)
+        assert (st.Kp, st.K, st.Qf, st.Qfp, st.cconst, st.Qp) == (sh.Kp, sh.K, sh.Qf, sh.Qfp, sh.cconst, sh.Qp)
+        assert sh.keys.shape == (sh.Qf, order - 1) and (sh.keys[-1] >= 0).sum() == min(order - 1, n)
+        B = R.stat_bits(sh.spins, sh.keys, st.Qfp, st.Kp)
+        assert B[:sh.Qf, :sh.K].any(axis=1).all() and not B[sh.Qf:].any() and not B[:, sh.K:].any()
+        assert np.array_equal(st.xb, R.xb_image(B, st.Kp, st.Qfp)), "Xb"
+        assert np.array_equal(st.xtb, R.xtb_image(B, st.Kp, st.Qfp)), "Xtb"
+        assert np.array_equal(st.theta[:n], sh.internal(th)), "the rows the pass read: gml_node_cols against the key lookup"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

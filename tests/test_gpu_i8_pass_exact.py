@@ -50,6 +50,8 @@ Shapes: pairwise n = 97, K = 10007 (not a multiple of 32, 256 or 1024; Kp = 1024
 uniform counts (the UNIW instances and their padding guard) and once with counts floor(10^U(0,3)), 3 % of them zero; rows
 _rows(n, 45, seed): node 0, node n - 1, a repeated node, two slot tiles, the second partial.  Order 3 at n = 20: 210 statistics columns
 (20 + 190), Qfp = 256, four 64-column steps, 46 padding columns; K = 4099 (Kp = 5120: three chunks of 2048, the last partial).
+Order 6 at n = 10 (`order6`): 637 statistics columns (10 + 45 + 120 + 210 + 252), Qfp = 640, ten steps, keys of up to five spins
+besides the node's own, P = 382; K = 4099, rows _rows(n, 45, 4).  The SCALE table and the caps are those of the other problems.
 test_split_k_last_chunk_partial: pairwise n = 40, K = 2049 -- the smallest K whose backward launch has two chunks with the last one
 partial: Kp = 3072 (K rounded up to 1024), plan kchunk = 2048 (i8_split_plan: two node tiles give nsplit = 256, ceil(Kp / 256) = 12 rounded
 up to 256 samples, raised to the minimum chunk of 2048), chunks
@@ -80,7 +82,7 @@ FAMILIES = ["sparse", "dense", "dyn", "zero"]
 OBJ_FORMS = [("i8x/3", "i8x", False, 3), ("i8x/4", "i8x", False, 4), ("i8x/5", "i8x", False, 5), ("i8x/coarse", "i8x", True, 0),
              ("i8w", "i8w", False, 0), ("i8w/coarse", "i8w", True, 0)]
 CASES = [(form, fl) for form in ("RISE", "RPLE") for fl in OBJ_FORMS if not (fl[2] and form == "RPLE")]
-PROBLEMS = ["narrow-uniform", "narrow-counts", "order3"]
+PROBLEMS = ["narrow-uniform", "narrow-counts", "order3", "order6"]
 # theta of a family times this, per (precision, exp form?, family), so that the decidable share meets the caps (docstring, B)
 SCALE = {("i8x", True, False, "sparse"): 32.0, ("i8x", True, False, "dense"): 4.0, ("i8w", True, False, "sparse"): 2.0, ("i8w", True, False, "dense"): 2.0}
 
@@ -112,6 +114,12 @@ class Prob:
             self.spins = np.where(rng.random((self.K, self.n)) < 0.5, 1, -1).astype(np.int8)
             self.counts = _counts(self.K, 12)
             self.nodes = _rows(self.n, 45, 3)
+        elif name == "order6":  # keys of up to five spins besides the node's own: 637 statistics columns, Qfp = 640, ten steps
+            self.n, self.K, self.order = 10, 4099, 6
+            rng = np.random.default_rng(13)
+            self.spins = np.where(rng.random((self.K, self.n)) < 0.5, 1, -1).astype(np.int8)
+            self.counts = _counts(self.K, 14)
+            self.nodes = _rows(self.n, 45, 4)
         else:
             self.n, self.K, self.order = 40, 2049, 2
             rng = np.random.default_rng(17)
@@ -126,7 +134,8 @@ class Prob:
         self.w = np.zeros(self.Kp)
         self.w[:self.K] = c / c.sum()
         self.wmax = float(self.w.max())
-        self.pkeys = None if self.order == 2 else {int(u): O.multi_keys(n, 3, int(u)) for u in set(self.nodes.tolist())}
+        self.colidx = {tuple(int(i) for i in k if i >= 0): c for c, k in enumerate(self.keys)}  # sorted key -> column, any order
+        self.pkeys = None if self.order == 2 else {int(u): O.multi_keys(n, self.order, int(u)) for u in set(self.nodes.tolist())}
         self.P = n if self.order == 2 else len(self.pkeys[int(self.nodes[0])])
         self._bits = {}
         self.sb = np.zeros((n, self.Kp), dtype=np.uint8)
@@ -141,13 +150,8 @@ class Prob:
     def column(self, u, key):
         """internal column of the parameter of node u with the reference key `key` (which holds u): the statistic of the other spins;
         -1: the constant column"""
-        rest = sorted(i for i in key if i != u)
-        if not rest:
-            return -1
-        if len(rest) == 1:
-            return rest[0]
-        i, j = rest
-        return self.n + i * self.n - i * (i + 1) // 2 + (j - i - 1)
+        rest = tuple(sorted(i for i in key if i != u))
+        return self.colidx[rest] if rest else -1
 
     def internal(self, th, Qp, cconst):
         """the rows th [R][P] (reference order) in the internal column layout"""
@@ -218,6 +222,22 @@ def host_tau(pb, prec, form, coarse, lf, theta_int, Qfp, cconst):
         sc = R.row_scalars(theta_int[r], Qfp, cconst, lfq)
         out.append(float(R.tau(sc["sabs"], sc["sx"], pb.wmax, form, lbt)))
     return np.array(out)
+
+
+def test_key_lookup_gives_the_closed_form_columns():
+    """Prob.column looks a parameter's other spins up in stat_keys; at order 3 that is the closed form it replaced"""
+    pb = prob("order3")
+    n = pb.n
+    for u, keys in pb.pkeys.items():
+        for key in keys:
+            rest = sorted(i for i in key if i != u)
+            want = -1 if not rest else rest[0] if len(rest) == 1 else n + rest[0] * n - rest[0] * (rest[0] + 1) // 2 + (rest[1] - rest[0] - 1)
+            assert pb.column(u, key) == want, (u, key)
+    p6 = prob("order6")
+    assert (p6.Qf, p6.P, max(len(k) for k in p6.pkeys[0])) == (637, 382, 6)
+    for u, keys in p6.pkeys.items():
+        cols = [p6.column(u, k) for k in keys]
+        assert len(set(cols)) == p6.P and cols.count(-1) == 1 and all(u not in p6.keys[c] for c in cols if c >= 0)
 
 
 @need_ld
@@ -412,7 +432,7 @@ def reference(p, pb, name, form, th_key, th):
                     keys[u] = p.multi_keys_array(u)
                 return keys[u]
 
-            ref = Ref(pb.spins, pb.counts, order=3, keys=karr)
+            ref = Ref(pb.spins, pb.counts, order=pb.order, keys=karr)
         _refs[key] = ref.run(pb.nodes, [dict(form=form, theta=th, vec=None, keep=[])])[0]
     return _refs[key]
 

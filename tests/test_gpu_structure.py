@@ -22,7 +22,9 @@ EXCLUDED, FREE, PENALISED = gml.EXCLUDED, gml.FREE, gml.PENALISED
 FORMS = ["RISE", "logRISE", "RPLE"]
 PRECS = ["f64", "i8w", "i8x"]
 RULES = ["row", "mean", "all", "any"]
-SHAPES = {"pairwise": (40, 2), "order3": (40, 3), "order4": (9, 4)}  # order 3: P = 781, the triples cross the kernels' 32-wide tiles
+# order 3: P = 781, the triples cross the kernels' 32-wide tiles; wide6, wide8: keys of up to six and eight spins (P = 382, 255), named
+# so that they sort behind the older shapes, whose seeds are their positions in the sorted list
+SHAPES = {"pairwise": (40, 2), "order3": (40, 3), "order4": (9, 4), "wide6": (10, 6), "wide8": (9, 8)}
 N, K, C_PEN = 40, 3000, 0.4
 
 

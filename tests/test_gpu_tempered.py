@@ -9,6 +9,7 @@ import pytest
 
 import gml_amd as gml
 from gml_amd import _lib
+from _high_order_cases import wide_terms
 from _tempered_reference import bimodal_16, exact_moments, tempered
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +75,8 @@ CASES = {
     "order4_cancelled_n30": lambda: (order4_with_cancellations(30, 3), 30),
     "n1": lambda: ({(1,): 0.3}, 1),
     "n33": lambda: (sparse_model(33, 6, 4, 0.3, 4), 33),
+    # terms of 5 to 8 spins, some through keys that name a spin twice; the handle is one of order 8 (n = 12: 3301 statistics columns)
+    "orders_5_to_8_cancelled_n12": lambda: (wide_terms(12, 5), 12),
 }
 LADDERS = {2: 1001, 8: 251, 64: 37}  # about 2000 lanes; the last tile is partly empty (at R = 64 only for tiles above 64 lanes)
 

@@ -29,7 +29,7 @@ def dict_assembly(rows, n, order, sym):
     return rec, np.array([rec[k] for k in O.listing_order(rec)])
 
 
-@pytest.mark.parametrize("n,order", [(1, 1), (4, 1), (2, 2), (9, 2), (3, 3), (12, 3), (36, 3), (10, 4), (9, 5)])
+@pytest.mark.parametrize("n,order", [(1, 1), (4, 1), (2, 2), (9, 2), (3, 3), (12, 3), (36, 3), (10, 4), (9, 5), (10, 6), (9, 8), (7, 8), (3, 8)])
 @pytest.mark.parametrize("sym", [True, False])
 def test_assembly_kernel_equals_the_reference_dict_assembly(n, order, sym):
     P = n if order == 2 else sum(__import__("math").comb(n - 1, s - 1) for s in range(1, order + 1))

@@ -106,6 +106,8 @@ def test_margin_of_the_block_cases(name):
 def test_the_block_cases_are_the_shapes_they_claim():
     nts = {name: len(cases.block_model(name)[2]) for name in cases.BLOCK_MODELS}
     assert nts["isolated_sb1"] == 0 and nts["field_sb1"] == 1 and nts["subsets_sb13"] == 1092 and nts["chain_sb22"] == 43
+    masks = cases.block_model("wide_sb12")[1]
+    assert sorted({bin(int(m)).count("1") for m in masks}) == [1, 5, 6, 7, 8]
     sb, _, _, _, _, en, cdf = cases.block_model("steep_sb10")
     p = np.diff(np.concatenate([[0], cdf]))
     assert np.count_nonzero(p == 0) >= 2 ** 10 - 2 ** 6  # flat runs: states whose probability underflows
@@ -139,6 +141,11 @@ def test_margin_of_the_front_door_cases(name, seed):
         assert np.any(rows[:, 63] == -1) and len(rows) % 32 != 0  # bit 63 of a key, and a ragged last sign word
     if name == "twins":
         assert sizes == [4, 4] and not np.array_equal(S[:, :4], S[:, 4:])
+    if name == "wide19":
+        assert sizes == [1, 6, 12]
+        (_, masks, _), = [b for b in R.blocks(terms, n) if len(b[0]) == 12]
+        bits = sorted({bin(int(m)).count("1") for m in masks})
+        assert bits == [1, 5, 6, 7, 8] and any(len(set(k)) < len(k) for k in terms)
 
 
 @pytest.mark.parametrize("seed", cases.SEEDS)
@@ -150,6 +157,9 @@ def test_margin_of_the_glauber_cases(name, seed):
     if name == "sparse33":
         inc = R.incidences(list(terms.items()), n)
         assert inc[7] == [] and inc[21] == [] and any(len(set(k)) < len(k) for k in terms)
+    if name == "wide24":
+        inc = R.incidences(list(terms.items()), n)
+        assert {len(set(k)) for k in terms} >= {5, 6, 7, 8} and any(len(set(k)) < len(k) for k in terms) and all(inc)
     if name == "ring64":
         rows, _ = R.histogram(S)
         assert np.any(rows[:, 63] == -1) and len(rows) % 32 != 0

@@ -25,7 +25,7 @@ def reference_keys(n, order, symmetrize):
     return O.listing_order(rec)
 
 
-@pytest.mark.parametrize("n,order", [(1, 1), (3, 1), (2, 2), (5, 2), (3, 3), (7, 3), (9, 4), (6, 6), (8, 5)])
+@pytest.mark.parametrize("n,order", [(1, 1), (3, 1), (2, 2), (5, 2), (3, 3), (7, 3), (9, 4), (6, 6), (8, 5), (10, 6), (9, 8), (7, 8), (3, 8)])
 @pytest.mark.parametrize("sym", [True, False])
 def test_term_positions_follow_the_reference_listing_order(n, order, sym):
     want = reference_keys(n, order, sym)
