@@ -4,11 +4,13 @@ Same surface as the reference module (GraphicalModelLearning.jl:3-6, models.jl:3
 the GMLFormulation types, the GMLMethod types (NLP plus the new HIP), FactorGraph.  The compute
 path is libgml_hip.so (hand-written HIP kernels for gfx950 behind the C ABI in include/gml.h).
 """
+from . import inference  # noqa: F401
 from ._lib import (EXCLUDED, FREE, PENALISED, GMLConvergenceError, GMLError, MultiProblem, Problem, lib, moments,  # noqa: F401
                    structure_from_keys, structure_from_rows)
 from .factor_graph import FactorGraph, matrix_to_terms, permutations, check_model_data  # noqa: F401
 from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, GMLMethod,  # noqa: F401
                            logRISE, multiRISE)
+from .inference import ConditionalMeans, PredictiveCheck, conditional_means, conditional_sample, predictive_check  # noqa: F401
 from .learn import learn  # noqa: F401
 from .likelihood import AIS, LogLikelihood, LogPartition, log_likelihood, log_partition  # noqa: F401
 from .path import PathResult, learn_path  # noqa: F401
@@ -18,4 +20,4 @@ __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multi
            "NLP", "HIP", "FactorGraph", "Problem", "MultiProblem", "GMLError", "GMLConvergenceError", "sample", "GMSampler", "Gibbs",
            "Glauber", "GlauberChains", "GlauberTermChains", "TemperedTermChains", "moments", "EXCLUDED", "FREE", "PENALISED",
            "structure_from_rows", "structure_from_keys", "learn_path", "PathResult", "AIS", "log_partition", "log_likelihood", "LogPartition",
-           "LogLikelihood"]
+           "LogLikelihood", "conditional_sample", "conditional_means", "predictive_check", "ConditionalMeans", "PredictiveCheck"]

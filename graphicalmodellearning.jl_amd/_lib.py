@@ -92,6 +92,9 @@ def lib():
     L.gml_problem_create_mcmc_terms_tempered.argtypes = [p, i32, p, i64, i64, i64, i64, i32, i32, p, i32, i32, C.c_uint64, i32, i32, i64,
                                                          i64, i32, p, C.POINTER(p)]
     L.gml_log_partition_ais.argtypes = [p, i32, p, i64, i64, i64, p, i64, i32, C.c_uint64, i32, p, p, p, p]
+    L.gml_problem_create_mcmc_terms_conditional.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, i32, i64, i64,
+                                                            C.POINTER(p)]
+    L.gml_conditional_means.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
     L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -735,6 +738,30 @@ class Problem:
                                             int(warmup), _ptr(ms), _ptr(f), _ptr(g), _ptr(step)))
         out = {"fwd_ms": ms[0], "bwd_ms": ms[1], "pass_ms": ms[2], "device_ms_per_pass": ms[3], "step_ms": step}
         return (out, f, g) if want_output else out
+
+
+def conditional_chains(terms, n, evidence, hidden, replicas=1, samples_per_chain=1, burn_in=200, thin=10, seed=0, *, means=False,
+                       order=2, node_range=None):
+    """The conditional chains of a term list as term_arrays takes it (include/gml.h): evidence an open Problem, hidden the 0-BASED
+    hidden spins.  means=False: gml_problem_create_mcmc_terms_conditional, a Problem of K replicas samples_per_chain rows (row
+    (t, r, k) at (t replicas + r) K + k) on the evidence's device.  means=True: gml_conditional_means, float64 [H, K replicas], the
+    hidden spins in ascending order."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    mask = np.zeros(max(int(n), 0), dtype=np.uint8)
+    hidden = np.asarray(hidden, dtype=np.int64).ravel()
+    if len(hidden) and (hidden.min() < 0 or hidden.max() >= n):
+        raise GMLError(GML_EINVAL, f"a hidden spin lies outside [0, {int(n)})")
+    mask[hidden] = 1
+    common = (_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, _ptr(mask), int(replicas), int(samples_per_chain), int(burn_in),
+              int(thin), int(seed))
+    if means:
+        out = np.zeros((int(mask.sum()), evidence.K * max(int(replicas), 0)))
+        check(lib().gml_conditional_means(*common, _ptr(out)))
+        return out
+    h = C.c_void_p()
+    n0, n1 = _node_range(node_range, n)
+    check(lib().gml_problem_create_mcmc_terms_conditional(*common, int(order), n0, n1, C.byref(h)))
+    return Problem._from_handle(h, order)
 
 
 def moments(samples_or_problem, terms=None, raw=False, device=0):

@@ -35,6 +35,13 @@ __device__ __forceinline__ unsigned chain_heat_bath(unsigned long long z0, unsig
     return u01_mix(z0 + kU01Step * s) < pup ? 0u : 1u;
 }
 
+// the same heat bath, handing back the probability it used (the conditional chains average 2 pup - 1, gml_cond_chains.hip)
+__device__ __forceinline__ unsigned chain_heat_bath_pup(unsigned long long z0, unsigned long long s, double field, double *pup_out) {
+    const double pup = 1.0 / (1.0 + exp(-2.0 * field));
+    *pup_out = pup;
+    return u01_mix(z0 + kU01Step * s) < pup ? 0u : 1u;
+}
+
 // A recorded sweep of the bit-state chains: after `done` completed sweeps, chain c (a lane whose words are col[b * stride]) writes its
 // state as +-1 bytes, spin-major [n][ld], row (done - burn_in) / thin * chains + c -- if this sweep is recorded and the chain exists.
 __device__ __forceinline__ void chain_record(int done, int burn_in, int thin, int64_t c, int64_t chains, int n, int nw, const unsigned *col,

@@ -242,6 +242,17 @@ void launch_tempered_chains(const TermChainSpin *dspin, const unsigned *drec, in
 void launch_ais_chains(const TermChainSpin *dspin, const TermChainSpin *dspin0, const unsigned *drec, int64_t n, int64_t chains,
                        const double *dbetas, int64_t nbetas, int sps, unsigned long long seed, double *dlogw, double *dE,
                        int8_t *dstates, hipStream_t st);
+// Conditional chains on the same records (gml_cond_chains.hip): `chains` = K replicas chains, chain r K + k started from row k of the
+// sign bits dSb [n][wpr] on the visible spins and from chain_start_bit on the hidden ones (dhidden [n], non-zero = hidden; dhid [H]
+// their indices, ascending), swept over the hidden spins only.  dhspin [H]: the spin records of the hidden spins -- over all their
+// incidences (dcspin, dcst NULL), or over those with a hidden other spin, dcspin [H] then holding the rest and dcst [H][chains]
+// receiving their per-chain integer.  dout [n][ld] or NULL; dmeans [H][chains] (zeroed by the caller) or NULL.
+// g_cond_split (gml_testhooks.cpp): whether the host splits the records -- 0 never, 1 by its rule, 2 wherever it can.
+extern int g_cond_split;
+void launch_cond_chains(const TermChainSpin *dhspin, const TermChainSpin *dcspin, const int *dhid, const uint8_t *dhidden,
+                        const unsigned *drec, const unsigned *dSb, int64_t wpr, int64_t K, int64_t n, int64_t H, int64_t chains,
+                        int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout, int64_t ld, double *dmeans, long long *dcst,
+                        hipStream_t st);
 
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].

@@ -55,6 +55,18 @@ __device__ __forceinline__ long long odd_sum(const unsigned *__restrict__ rec, l
     return s;
 }
 
+// sum_e q_e prod_{j in others(e)} s_j of the spin record r as the exact int64 (k_cond_chains adds a per-chain constant before it converts)
+__device__ __forceinline__ long long term_field_int(const TermChainSpin &r, const unsigned *__restrict__ rec, const unsigned *my, int T) {
+    long long odd = odd_sum<1>(rec, r.off[0], r.off[1], my, T);
+    odd += odd_sum<2>(rec, r.off[1], r.off[2], my, T);
+    odd += odd_sum<3>(rec, r.off[2], r.off[3], my, T);
+    odd += odd_sum<4>(rec, r.off[3], r.off[4], my, T);
+    odd += odd_sum<5>(rec, r.off[4], r.off[5], my, T);
+    odd += odd_sum<6>(rec, r.off[5], r.off[6], my, T);
+    odd += odd_sum<7>(rec, r.off[6], r.off[7], my, T);
+    return r.Q - 2 * odd;
+}
+
 // sum_e q_e prod_{j in others(e)} s_j of the spin record r as a double: the int64 sum is exact and converts exactly
 __device__ __forceinline__ double term_field(const TermChainSpin &r, const unsigned *__restrict__ rec, const unsigned *my, int T) {
     long long odd = odd_sum<1>(rec, r.off[0], r.off[1], my, T);

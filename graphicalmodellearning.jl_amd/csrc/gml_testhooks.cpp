@@ -23,7 +23,8 @@ namespace gml {
 double g_hv_sparse_ratio = 0.3; // (config 5 at the default regulariser: 25.6 s never, 23.6 s at 0.3 and at 0.6)
 std::atomic<long long> g_hv_sparse_calls{0}; // (every part of a gml_multi_learn counts from its own host thread)
 int g_term_chains_tile = 0;                   // 0: the rule of term_chains_tile (gml_term_chains.hip)
-double g_tune[GML_NTUNE] = {};               // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
+int g_cond_split = 1;                         // the conditional chains' constant part: 0 never, 1 by the host's rule, 2 always
+double g_tune[GML_NTUNE] = {};             // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
 // the kernel instances the int8-limb launchers have run (gml_i8.h: kI8InstBits)
 static std::atomic<uint64_t> g_i8_inst[(kI8InstBits + 63) / 64];
 void i8_note_instance(int bit) { g_i8_inst[bit >> 6].fetch_or(1ull << (bit & 63), std::memory_order_relaxed); }
@@ -53,6 +54,15 @@ extern "C" int gml_test_term_chains_tile(int T) {
     if (T != 0 && T != 64 && T != 128 && T != 256) return -1;
     const int old = g_term_chains_tile;
     g_term_chains_tile = T;
+    return old;
+}
+// the constant part of the conditional chains' fields (gml_cond_chains.hip): 1 (default) the incidences of a hidden spin whose other
+// spins are all observed are summed once per chain where the host's rule expects that to pay (gml_sampled.cpp), 2 wherever there is
+// such an incidence, 0 never -- every sweep walks them; the same bits in all three.  Returns the old value, -1 for another value
+extern "C" int gml_test_cond_split(int on) {
+    if (on < 0 || on > 2) return -1;
+    const int old = g_cond_split;
+    g_cond_split = on;
     return old;
 }
 extern "C" double gml_test_hv_sparse_ratio(double ratio) {

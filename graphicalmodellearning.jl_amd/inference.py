@@ -1,0 +1,129 @@
+"""Conditional inference with a model: given some spins of a sample, what are the others?
+
+conditional_sample / conditional_means run Glauber chains on the device that start from the rows of the evidence and hold the observed
+spins fixed (gml_problem_create_mcmc_terms_conditional, gml_conditional_means: the term-list chains of GlauberTermChains, swept over
+the hidden spins only).  A conditional mean is Rao-Blackwellised: not the average of the sampled spin but of 2 pup - 1, the
+conditional expectation of the spin given all the others at the moment it was updated -- the same expectation with less variance,
+and exact (no sampling at all) when one spin is hidden.  predictive_check hides the same spins in every row of a data set and scores
+the predictions against the values the data hold: held-out predictive accuracy, the check of a fit that neither a
+pseudo-likelihood nor an AIS likelihood gives."""
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .sampling import GlauberTermChains, _problem_args, _term_list_args
+
+
+@dataclass
+class ConditionalMeans:
+    """means [K, H]: E[s_i | the visible spins of row k] for the hidden spins i (ascending), averaged over the replicas; stderr [K, H]:
+    the standard deviation over replicas / sqrt(replicas), NaN for one replica; per_replica [replicas, K, H]; hidden: the H hidden spins,
+    1-based, ascending; counts [K]: the counts of the evidence rows."""
+    means: np.ndarray
+    stderr: np.ndarray
+    per_replica: np.ndarray
+    hidden: list
+    counts: np.ndarray
+
+
+@dataclass
+class PredictiveCheck:
+    """Per hidden spin (1-based, ascending): accuracy, the count-weighted share of rows whose hidden value is sign(mean) (a mean of
+    exactly 0 predicts +1), and log_loss, the count-weighted mean of -log p with p = (1 + s mean) / 2 the probability given to the
+    value s the data hold.  means: the ConditionalMeans behind them."""
+    hidden: list
+    accuracy: np.ndarray
+    log_loss: np.ndarray
+    means: ConditionalMeans
+
+
+def _hidden_spins(hidden, n):
+    """the hidden spins as a sorted list of 1-based ints; empty, out-of-range and repeated entries are refused"""
+    spins = [int(i) for i in hidden]
+    if not spins:
+        raise ValueError("hidden names no spin")
+    if min(spins) < 1 or max(spins) > int(n):
+        raise ValueError(f"hidden spins are numbered from 1 to n = {int(n)} (given {spins})")
+    if len(set(spins)) != len(spins):
+        raise ValueError(f"hidden names a spin twice (given {spins})")
+    return sorted(spins)
+
+
+def _sampler(sampler):
+    sampler = GlauberTermChains() if sampler is None else sampler
+    if not isinstance(sampler, GlauberTermChains):
+        raise ValueError(f"conditional inference takes a GlauberTermChains sampler, given {type(sampler).__name__}")
+    return sampler
+
+
+class _Evidence:
+    """the evidence as an open Problem: the caller's own, or one opened from a histogram matrix and closed on exit"""
+
+    def __init__(self, evidence):
+        self.given = isinstance(evidence, _lib.Problem)
+        self.p, self.matrix = (evidence, None) if self.given else (None, np.asarray(evidence))
+        if not self.given and (self.matrix.ndim != 2 or self.matrix.shape[1] < 2):
+            raise ValueError("evidence must be an open Problem or a K x (1+n) histogram matrix")
+        self.n = evidence.n if self.given else self.matrix.shape[1] - 1
+
+    def __enter__(self):
+        if not self.given:
+            self.p = _lib.Problem(self.matrix)
+        return self.p
+
+    def __exit__(self, *a):
+        if not self.given:
+            self.p.close()
+
+
+def _run(model, evidence, hidden, sampler, replicas, seed, means):
+    sampler = _sampler(sampler)
+    if int(replicas) < 1:
+        raise ValueError(f"replicas must be at least 1 (given {replicas})")
+    ev = _Evidence(evidence)
+    spins = _hidden_spins(hidden, ev.n)
+    args = _term_list_args(model, _problem_args(model))
+    with ev as p:
+        out = _lib.conditional_chains(args["terms"], ev.n, p, np.asarray(spins) - 1, int(replicas), sampler.samples_per_chain,
+                                      sampler.burn_in, sampler.thin, seed, means=means, order=args.get("order", 2))
+        return out, spins, (p.counts() if means else None), p.K
+
+
+def conditional_sample(model, evidence, hidden, sampler=None, *, replicas=1, seed=0):
+    """Samples of the hidden spins (1-based, like FactorGraph keys) given the visible spins of every row of `evidence` (an open Problem or
+    a K x (1+n) histogram matrix; its counts play no part).  model: a FactorGraph, a {1-based key tuple: weight} dict or a matrix with the
+    fields on its diagonal; sampler: a GlauberTermChains (burn_in, thin, samples_per_chain).  Returns a Problem on the evidence's device
+    with K replicas samples_per_chain rows of count 1: row (t replicas + r) K + k is sample t of replica r of evidence row k, its
+    visible spins those of the evidence."""
+    return _run(model, evidence, hidden, sampler, replicas, seed, False)[0]
+
+
+def conditional_means(model, evidence, hidden, sampler=None, *, replicas=1, seed=0):
+    """Rao-Blackwellised conditional means of the hidden spins given the visible spins of every evidence row; arguments as
+    conditional_sample.  No handle is made.  Returns a ConditionalMeans (columns: the hidden spins in ascending order)."""
+    raw, spins, counts, K = _run(model, evidence, hidden, sampler, replicas, seed, True)
+    R = int(replicas)
+    per = np.ascontiguousarray(raw.reshape(len(spins), R, K).transpose(1, 2, 0))  # [H][r K + k] -> [r][k][a]
+    if R > 1:
+        stderr = per.std(axis=0, ddof=1) / np.sqrt(R)
+    else:
+        stderr = np.full(per.shape[1:], np.nan)
+    return ConditionalMeans(per.mean(axis=0), stderr, per, spins, counts)
+
+
+def predictive_check(model, data, hidden, sampler=None, *, replicas=1, seed=0):
+    """Hide the spins `hidden` in every row of `data` (an open Problem or a histogram matrix), predict them from the others under
+    `model`, and compare with the values the data hold.  Returns a PredictiveCheck.  It says how well each hidden spin is predicted
+    from the rest under the model; with several hidden spins each is predicted with the others hidden too (their joint uncertainty is
+    averaged over), and it says nothing about spins that were never hidden."""
+    ev = _Evidence(data)
+    _hidden_spins(hidden, ev.n)  # (refused before the data are opened)
+    with ev as p:
+        cm = conditional_means(model, p, hidden, sampler, replicas=replicas, seed=seed)
+        truth = p.spins()[:, np.asarray(cm.hidden) - 1].astype(np.float64)
+    w = cm.counts / cm.counts.sum()
+    predicted = np.where(cm.means >= 0.0, 1.0, -1.0)
+    accuracy = w @ (predicted == truth)
+    prob = np.maximum((1.0 + truth * cm.means) / 2.0, np.finfo(np.float64).tiny)
+    return PredictiveCheck(cm.hidden, accuracy, w @ (-np.log(prob)), cm)

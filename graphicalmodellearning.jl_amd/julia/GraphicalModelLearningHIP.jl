@@ -217,6 +217,53 @@ function log_partition(terms::Dict, n::Integer; chains::Integer=4096, steps::Int
     return result[1], result[2], result[3], logw
 end
 
+"""
+    conditional_means(terms::Dict, samples, hidden; replicas=1, samples_per_chain=1, burn_in=200, thin=10, seed=0, device=0)
+        -> means (K x H x replicas)
+
+Conditional means of the spins `hidden` (1-based) given the other spins of every row of the histogram `samples` (K x (1+n)), under the
+model `Dict(key tuple (1-based spins) => weight)` (gml_conditional_means, include/gml.h): `replicas` Glauber chains per row, started
+from the row, the observed spins held fixed, swept over the hidden spins only.  `means[k, a, r]` is the Rao-Blackwellised mean of the
+a-th hidden spin (ascending) in replica r of row k, the average of 2 pup - 1 over the recorded sweeps.  The counts of `samples` play no
+part.  Marshalling only.
+"""
+function conditional_means(terms::Dict, samples::Array{T,2}, hidden::AbstractVector{<:Integer}; replicas::Integer=1,
+                           samples_per_chain::Integer=1, burn_in::Integer=200, thin::Integer=10, seed::Integer=0,
+                           device::Integer=0) where T <: Real
+    s = T <: AbstractFloat ? convert(Array{Float64,2}, samples) : convert(Array{Int64,2}, samples)
+    dtype = eltype(s) == Float64 ? GML_F64 : GML_I64
+    K, n = size(s, 1), size(s, 2) - 1
+    all(i -> 1 <= i <= n, hidden) && !isempty(hidden) && allunique(hidden) ||
+        throw(ArgumentError("conditional_means: hidden must name distinct spins in 1:$n"))
+    mask = zeros(UInt8, n)
+    mask[hidden] .= 1
+    stride = max(1, maximum(length, keys(terms); init=1))
+    keymat = fill(Int32(-1), stride, length(terms))       # Julia (stride x T) == C row-major (T x stride); 0-based, -1 = unused
+    weights = Vector{Float64}(undef, length(terms))
+    for (t, (key, w)) in enumerate(terms)
+        for (a, v) in enumerate(key)
+            keymat[a, t] = Int32(v - 1)
+        end
+        weights[t] = w
+    end
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:gml_problem_create, libgml), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Cint, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+               s, dtype, K, n, K, 1 #= column-major =#, 2, 0, n, device, handle)
+    rc == GML_OK || error("gml_problem_create: $(lasterr())")
+    try
+        H = length(hidden)
+        means = Array{Float64}(undef, K, replicas, H)     # C row-major [H][replicas][K] == Julia (K x replicas x H)
+        rc = ccall((:gml_conditional_means, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{UInt8}, Cint, Int64, Cint, Cint, UInt64, Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, handle[], mask, replicas, samples_per_chain, burn_in, thin, seed, means)
+        rc == GML_OK || error("gml_conditional_means: $(lasterr())")
+        return permutedims(means, (1, 3, 2))
+    finally
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
+    end
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

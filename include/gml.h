@@ -365,6 +365,49 @@ int gml_log_partition_ais(const int32_t *keys, int key_stride, const double *wei
                           int8_t *spins /* [chains][n] row-major, +-1, or NULL */, double *result /* [3] or NULL */);
 
 /*
+ * gml_problem_create_mcmc_terms_conditional, gml_conditional_means -- conditional inference: Glauber chains of ANY term list that
+ * start from the rows of a resident handle and hold the observed spins fixed.  "Given these spins, what are the others?"
+ * Inputs: a term list (keys, key_stride, weights, nterms, n) as for gml_problem_create_mcmc_terms_chains; a resident handle `evidence`
+ * with the same n and K rows; a mask hidden [n] of uint8 (non-zero = hidden) with at least one hidden spin; replicas >= 1,
+ * samples_per_chain, burn_in, thin, seed.  Let the hidden spins in ascending order be i_0 < ... < i_{H-1}.
+ * Chains.  There are chains = K * replicas.  Chain c = r * K + k is replica r of evidence row k.  The counts of the evidence handle
+ *   play no part: every row gets `replicas` chains.
+ * Start.  A visible spin s has the value of row k of the evidence handle.  A hidden spin s starts as in every chain here:
+ *   chain_start_bit(seed, c, n, s), i.e. +1 iff u01(seed, 0xFFFFFFFF, c n + s) < 0.5.
+ * Sweep sw.  It is 0-based and burn-in is included.  For a = 0 .. H-1 in order, with i = i_a:  h = a_i + sigma_i * (double)S_i.
+ *   a_i, sigma_i, q_e are those of gml_problem_create_mcmc_terms_chains (unchanged).  S_i is the exact int64 sum over ALL incidences of
+ *   spin i at the current state.  pup = 1 / (1 + exp(-2 h)).  The new spin is +1 iff u01(seed, sw, c n + i) < pup.  Visible spins
+ *   are never visited.  The stream is that of gml_problem_create_mcmc_terms_chains, unchanged.
+ * Recording.  Recorded sweeps are those of gml_problem_create_mcmc_terms_chains: after done = sw + 1 completed sweeps with
+ *   done >= burn_in and (done - burn_in) % thin == 0, t = (done - burn_in) / thin.  The state is written at row t * chains + c.
+ * Conditional means (Rao-Blackwellised).  mean[a][c] = (1 / samples_per_chain) * sum over the recorded sweeps of (2 pup - 1), where
+ *   pup is the value the heat bath used for spin i_a in that sweep.  The sum is accumulated in FP64 in sweep order and multiplied by
+ *   the FP64 quotient 1.0 / samples_per_chain once.  Output layout is [H][chains], hidden-major.
+ * Consequence.  With every spin hidden and replicas = 1 the states are those of gml_problem_create_mcmc_terms_chains with chains = K
+ *   and the same seed, bit for bit.
+ * The results depend only on (model, evidence rows, hidden, replicas, samples_per_chain, burn_in, thin, seed): not on the order of
+ * the terms with other spins, the kernel's chain tile, the grid or the device, and not on whether the kernel sums the incidences
+ * whose other spins are all visible once per chain or in every sweep (both sums are exact integers).
+ * gml_problem_create_mcmc_terms_conditional: the new handle lives on the evidence handle's device and has chains * samples_per_chain
+ *   rows with count 1.  There is no histogram flag: row (t, r, k) of the result belongs to row k of the evidence, and deduplication
+ *   would break that.
+ * gml_conditional_means: means [H][K * replicas] (host).  It makes no handle and no state buffer; its device memory is released
+ *   before it returns.
+ * GML_EINVAL, before any device work: NULL evidence, hidden, out or means; no hidden spin; n different from the evidence handle's;
+ *   replicas < 1; everything gml_problem_create_mcmc_terms_chains rejects, with chains = K * replicas.  GML_EUNSUPPORTED: the limits of
+ *   gml_problem_create_mcmc_terms_chains (n > 16384, more than 8 distinct spins in a term, 2^24 incidences on a spin).
+ * Cost per chain-sweep: the incidences of the hidden spins -- where the all-visible ones are summed once per chain (the library does
+ *   so when they are many enough to pay), only those that name another hidden spin, plus one 8-byte load per hidden spin.
+ */
+int gml_problem_create_mcmc_terms_conditional(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                              gml_problem *evidence, const uint8_t *hidden /* [n], host */, int replicas,
+                                              int64_t samples_per_chain, int burn_in, int thin, uint64_t seed, int order, int64_t node0,
+                                              int64_t node1, gml_problem **out);
+int gml_conditional_means(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
+                          const uint8_t *hidden /* [n], host */, int replicas, int64_t samples_per_chain, int burn_in, int thin,
+                          uint64_t seed, double *means /* [H][K * replicas], host */);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
