@@ -40,6 +40,7 @@
 
 namespace gml {
 
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -144,6 +145,15 @@ __device__ __forceinline__ void dma16(const int8_t *ubase, int voff, unsigned ld
         asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(frag) : "n"(behind) : "memory"); \
         __builtin_amdgcn_sched_barrier(0);                                            \
     } while (0)
+// A fragment of two reads (the 32 K-contiguous bytes a lane hands the sparse MFMA as its dense operand: k_fwd_i8w's paired step):
+// the wait names both halves BEFORE they are put together as one v8i, so that a copy the register allocator might need for that
+// can only come behind the wait.  FRAG_READ64: the same pinned read for the 8 bytes of sample bits.
+#define FRAG_WAIT2(f0, f1, behind)                                                                \
+    do {                                                                                          \
+        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f0), "+v"(f1) : "n"(behind) : "memory");      \
+        __builtin_amdgcn_sched_barrier(0);                                                        \
+    } while (0)
+#define FRAG_READ64(dst, addr, off) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
 #ifdef GML_I8_PLAIN_FRAGS
 constexpr bool PINNED_FRAGS = false;
 #else

@@ -92,15 +92,16 @@ __device__ __forceinline__ void expand_bits(const unsigned (&vb)[WM], int t, v4i
 // Signed column pairs (gml_i8_pairs.h): the sparse A operand of v_smfmac_i32_32x32x64_i8 for a step, from the lane's bit dword.  Bits
 // 2 m and 2 m + 1 are the two columns of pair m; byte m of the fragment is x of the first (+1 / -1 for bit 0 / 1) and its 2-bit slot
 // index picks alpha (the bits agree) or beta (they differ) in the pair's half of a group of four slots: slots {0, 1} for even m,
-// {2, 3} for odd m.
-__device__ __forceinline__ void pair_picks(const unsigned (&vb)[WM], v4i (&fa)[WM], int (&ix)[WM]) {
+// {2, 3} for odd m.  `sel`: the byte selector of v_perm (a VOP3 instruction takes no literal on gfx9: a loop hands it in as a scalar
+// register it keeps, so that the constant costs no vector register).
+__device__ __forceinline__ void pair_picks(const unsigned (&vb)[WM], v4i (&fa)[WM], int (&ix)[WM], unsigned sel = 0x0000ff01u) {
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
         ix[i] = (int)(0x88888888u | ((vb[i] ^ (vb[i] >> 1)) & 0x55555555u));
 #pragma unroll
         for (int e = 0; e < 4; ++e) { // bits 8 e + {0, 2, 4, 6} -> bytes 0..3 as byte selectors 0 / 1 -> bytes 0x01 / 0xff
             const unsigned m = __umul24((vb[i] >> (8 * e)) & 0x55u, 0x41041u) & 0x01010101u;
-            fa[i][e] = (int)__builtin_amdgcn_perm(0u, 0x0000ff01u, m);
+            fa[i][e] = (int)__builtin_amdgcn_perm(0u, sel, m);
         }
     }
 }

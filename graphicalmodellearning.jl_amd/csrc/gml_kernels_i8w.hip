@@ -17,14 +17,16 @@
 // per step.  After the sweep the 7 accumulators of each element are folded into its energy, element by element.  Where the tile's
 // image holds signed column pairs (gml_i8_pairs.h: the planes of q + q', q - q'; full-width objective passes) the step runs on the 2:4
 // sparse MFMA, v_smfmac_i32_32x32x64_i8: one instruction per plane and sample tile covers the 64 columns, 14 per step instead of 28,
-// the fragment 8 registers instead of 4 (254 - 256 registers, no spill: profiles/r15_fwd_pairs_resources.txt).  The coarse
+// the fragment 8 registers instead of 4.  Two such fragments rotate, read with pinned ds_read ahead of the MFMAs that use them, the
+// step loop unrolled by the ring depth so that every LDS address is a loop-invariant register and an immediate (255 - 256
+// registers, no spill: profiles/r19_fwd_pairs_resources.txt; -DI8W_PLAIN_PAIR_FRAGS builds the step with plain loads).  The coarse
 // form sweeps only the top four planes (its own ring, two steps per stage).  -DI8W_TWO_SWEEPS builds the earlier form for A/B
 // runs: sweep A multiplies the planes 3..6 (128 accumulators), folds them into 32 FP64 partial energies per lane (64
 // registers), sweep B multiplies the planes 0..2 (96 accumulators), the sample bits loaded twice.  V is kept as two halves of 3
 // planes, V / tau = lo + 2^24 hi: the backward GEMM runs as two launches of the 3-plane form of k_bwd_i8 and every integer sum
 // (per half) stays far inside 64 bits.
 //
-// Build flags: -DI8W_TWO_SWEEPS (above; tests/test_gpu_i8w_single_sweep.py) and -DABL_TIMING (s_memrealtime stamps per phase,
+// Build flags: -DI8W_TWO_SWEEPS (above; tests/test_gpu_i8w_single_sweep.py), -DI8W_PLAIN_PAIR_FRAGS (above) and -DABL_TIMING (s_memrealtime stamps per phase,
 // read back through the V planes: scripts/gpu_fwd_timing.py).  Variants that were measured and no longer have a flag -- they live
 // in git history: the two-sweep kernel without its V stores, without its exp arithmetic, without both, and with sweep B cut to one
 // stage (forward 7.36 ms -> 6.48 / 6.83 / 6.11 / 5.63 ms: profiles/r4_ab_i8w_forward_ablation.txt); the epilogue's sign words and
@@ -50,6 +52,12 @@ static_assert(P1 % 4 == 0 && NL1 == 4, "one stage: 4 DMA instructions per wave")
 constexpr bool ONE_SWEEP = false;
 #else
 constexpr bool ONE_SWEEP = true;
+#endif
+// the paired step of the single sweep: LDS reads pinned ahead of the MFMAs, or (-DI8W_PLAIN_PAIR_FRAGS: A/B runs, tests) plain loads
+#ifdef I8W_PLAIN_PAIR_FRAGS
+constexpr bool PAIR_FRAGS_AHEAD = false;
+#else
+constexpr bool PAIR_FRAGS_AHEAD = true;
 #endif
 // the forms that take the single sweep: the full-width ones, but RPLE beyond 32768 columns (its epilogue keeps 2 more registers
 // through the fold, which spills them: it keeps the two sweeps)
@@ -117,8 +125,8 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
     const int8_t *const gT = Tq + (int64_t)mytile * nk_tq * BRT * 64;
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) int8_t *)lds;
     int r = mytile * 32 + lr;
-    const int rc = rowcol[r];
-    const bool active = rc >= 0;
+    int rc = rowcol[r];
+    bool active = rc >= 0;
 
 #ifdef ABL_TIMING
     unsigned long long tst[6];
@@ -138,8 +146,11 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
             adv1[j] = pc < 2 ? 1024 : BRT * 64;
         }
         const int voff0 = wave < 2 ? voffX : voffT;
+        const bool pairs = tdense && tdense[mytile] == 0; // (uniform over the workgroup)
+        // the stage of step 0: the unrolled paired sweep enters the ring where its last NS1 - 1 steps come to lie in the stages 0, 1, 2
+        const int rot = pairs && PAIR_FRAGS_AHEAD && nk >= NS1 - 1 ? (NS1 - 1 - nk) & (NS1 - 1) : 0;
         auto issue1 = [&](int ks) {
-            const unsigned stage_base = lds0 + (ks % NS1) * STEP1;
+            const unsigned stage_base = lds0 + ((ks + rot) % NS1) * STEP1;
 #pragma unroll
             for (int j = 0; j < NL1; ++j) dma16(base1[j] + (int64_t)ks * adv1[j], j == 0 ? voff0 : voffT, stage_base + (wave + 4 * j) * 1024);
         };
@@ -159,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             if (ks + NS1 - 1 < nk) issue1(ks + NS1 - 1); // (into the stage every wave finished reading before the barrier)
-            const int8_t *cur = lds + (ks % NS1) * STEP1;
+            const int8_t *cur = lds + ((ks + rot) % NS1) * STEP1;
             unsigned vb[WM];
             read_bits<true>(cur, wave, lr, h, vb);
 #pragma unroll
@@ -180,6 +191,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         // the same step on signed column pairs: the picks (+-1 bytes and their slot indices) come from the same bit dwords, one
         // plane's fragment is the lane's 32 K-contiguous bytes of the row (two reads), one sparse MFMA per plane and sample tile
         // covers the whole 64-column step: 14 where the dense step issues 28.  The sparse MFMA accumulates in place: no FIRST form.
+        // (This is the step written with plain loads, which -DI8W_PLAIN_PAIR_FRAGS builds: a read, a wait, two MFMAs, seven times.)
         auto step_pairs = [&](int ks) {
             if (ks + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL1) : "memory");
             else if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL1) : "memory");
@@ -187,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             if (ks + NS1 - 1 < nk) issue1(ks + NS1 - 1);
-            const int8_t *cur = lds + (ks % NS1) * STEP1;
+            const int8_t *cur = lds + ((ks + rot) % NS1) * STEP1;
             unsigned vb[WM];
             read_bits<true>(cur, wave, lr, h, vb);
             v4i fa[WM];
@@ -202,8 +214,109 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
                 for (int i = 0; i < WM; ++i) acc[i][l] = SMFMAC_I8(fa[i], fb, acc[i][l], ix[i]);
             }
         };
-        const bool pairs = tdense && tdense[mytile] == 0; // (uniform over the workgroup)
-        if (nk > 0 && pairs) {
+        if (nk > 0 && pairs && PAIR_FRAGS_AHEAD) {
+            clear_acc(acc);
+            // The paired step with its LDS reads kept ahead of its MFMAs (the idiom of k_bwd_i8: gml_i8.h, FRAG_READ).  Two fragments of
+            // Theta rotate: the bit dwords and the fragments of the planes 0 and 1 are read straight behind the barrier, the picks run
+            // under that round trip, and the read of plane l + 2 goes out right behind the two MFMAs of plane l; every use waits, with a
+            // counted lgkmcnt, for its own fragment only (LDS reads return in order: at most the next plane's two reads are behind it).
+            // A step's reads stay inside its own stage -- the next one is only known to have landed behind its own wait and barrier.
+            // The step loop is unrolled by the ring depth, so the stage is an immediate offset of the reads (at most 3 STEP1 + 2048 +
+            // 6 * 2048 + 16 bits) and the lane's addresses are three loop-invariant registers: the two halves of a row's 32 bytes
+            // (slots 2 h and 2 h + 1 of lds_off(), which differ in bit 4), a plane + 2048 bytes, and the bits.  The four DMA
+            // instructions of a step go out between the plane groups, off the front of the chain, in the same order and number, so
+            // the counted vmcnt waits hold as before; their target stage was read in the previous step, which every wave has left
+            // once this step's barrier has passed.
+            const unsigned a0 = lds0 + (unsigned)lds_off(lr, 2 * h), a1 = lds0 + (unsigned)lds_off(lr, 2 * h + 1);
+            const unsigned ab = lds0 + (unsigned)((wave >> 1) * 1024 + ((wave & 1) * 64 + lr) * 8); // (read_bits<true>: rows wave * 64 + lr, + 32)
+            const unsigned ldsw = lds0 + wave * 1024;
+            unsigned sel = 0x0000ff01u;
+            asm("" : "+s"(sel));
+            const unsigned long long hmask = __ballot(h != 0);
+            // the sources of the next stage to issue
+            const int npro = nk < NS1 - 1 ? nk : NS1 - 1;
+            const int8_t *nxt[NL1];
+#pragma unroll
+            for (int j = 0; j < NL1; ++j) nxt[j] = base1[j] + (int64_t)npro * adv1[j];
+            auto pstep = [&](auto stage, auto issues, int ahead /* stages behind this one still to come (!ISSUES) */) {
+                constexpr int S = decltype(stage)::value, OFF = S * STEP1, DST = ((S + NS1 - 1) % NS1) * STEP1;
+                constexpr bool ISSUES = decltype(issues)::value; // the step issues a stage, two more are in flight
+                if constexpr (ISSUES) {
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL1) : "memory");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                } else {
+                    ring_wait_ahead<NL1>(ahead);
+                }
+                v2u b0, b1;
+                v4i fA0, fA1, fB0, fB1, fa[WM];
+                int ix[WM];
+                FRAG_READ64(b0, ab, OFF);
+                FRAG_READ64(b1, ab, OFF + 256);
+                FRAG_READ(fA0, a0, OFF + 2048);
+                FRAG_READ(fA1, a1, OFF + 2048);
+                FRAG_READ(fB0, a0, OFF + 2 * 2048);
+                FRAG_READ(fB1, a1, OFF + 2 * 2048);
+                __builtin_amdgcn_sched_barrier(0);
+                FRAG_WAIT2(b0, b1, 4);
+                // (lane (lr, h) takes dword h: selected by a mask the loop keeps in scalar registers, so that no lane coordinate stays live)
+                unsigned vb[WM];
+                asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(vb[0]) : "v"(b0.x), "v"(b0.y), "s"(hmask));
+                asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(vb[1]) : "v"(b1.x), "v"(b1.y), "s"(hmask));
+                pair_picks(vb, fa, ix, sel);
+                __builtin_amdgcn_sched_barrier(0);
+#define PAIR_DMA(j)                                                                                                         \
+    if constexpr (ISSUES) {                                                                                                 \
+        dma16(nxt[j], (j) == 0 ? voff0 : voffT, ldsw + DST + 4 * (j) * 1024);                                               \
+        nxt[j] += adv1[j];                                                                                                  \
+    }
+#define PAIR_USE(l, f0, f1)                                                                                                 \
+    {                                                                                                                       \
+        FRAG_WAIT2(f0, f1, (l) + 1 < LFW ? 2 : 0);                                                                          \
+        const v8i fb = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};                                            \
+        _Pragma("unroll") for (int i = 0; i < WM; ++i) acc[i][l] = SMFMAC_I8(fa[i], fb, acc[i][l], ix[i]);                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                                  \
+        if constexpr ((l) + 2 < LFW) {                                                                                      \
+            FRAG_READ(f0, a0, OFF + ((l) + 3) * 2048);                                                                      \
+            FRAG_READ(f1, a1, OFF + ((l) + 3) * 2048);                                                                      \
+        }                                                                                                                   \
+    }
+                PAIR_USE(0, fA0, fA1)
+                PAIR_USE(1, fB0, fB1)
+                PAIR_DMA(0)
+                PAIR_USE(2, fA0, fA1)
+                PAIR_USE(3, fB0, fB1)
+                PAIR_DMA(1)
+                PAIR_USE(4, fA0, fA1)
+                PAIR_DMA(2)
+                PAIR_USE(5, fB0, fB1)
+                PAIR_USE(6, fA0, fA1)
+                PAIR_DMA(3)
+#undef PAIR_USE
+#undef PAIR_DMA
+            };
+            // The steps that issue a stage (all but the last NS1 - 1), a turn of the ring per trip of the loop, the odd ones in front;
+            // then the last NS1 - 1 (fewer when nk is), which issue nothing and wait for less each time.  The ring is entered at stage
+            // `rot`, so that these last steps always sit in the stages 0, 1, 2: ten bodies, each one basic block -- no fragment is in
+            // flight across a branch.
+            using std::integral_constant;
+            using std::true_type;
+            using std::false_type;
+            const int nis = nk - npro, odd = nis % NS1; // (npro < NS1 - 1: nis = 0)
+            if (odd >= 3) pstep(integral_constant<int, 1>{}, true_type{}, 0);
+            if (odd >= 2) pstep(integral_constant<int, 2>{}, true_type{}, 0);
+            if (odd >= 1) pstep(integral_constant<int, 3>{}, true_type{}, 0);
+            for (int turn = nis / NS1; turn > 0; --turn) {
+                pstep(integral_constant<int, 0>{}, true_type{}, 0);
+                pstep(integral_constant<int, 1>{}, true_type{}, 0);
+                pstep(integral_constant<int, 2>{}, true_type{}, 0);
+                pstep(integral_constant<int, 3>{}, true_type{}, 0);
+            }
+            static_assert(NS1 == 4, "the last NS1 - 1 steps are written out");
+            pstep(integral_constant<int, 0>{}, false_type{}, npro - 1);
+            if (npro > 1) pstep(integral_constant<int, 1>{}, false_type{}, npro - 2);
+            if (npro > 2) pstep(integral_constant<int, 2>{}, false_type{}, 0);
+        } else if (nk > 0 && pairs) {
             clear_acc(acc);
             for (int ks = 0; ks < nk; ++ks) step_pairs(ks);
         } else if (nk > 0) { // Qfp >= 64
@@ -220,6 +333,8 @@ __global__ __launch_bounds__(256, 2) void k_fwd_i8w(
         lr = lane & 31;
         h = lane >> 5;
         r = mytile * 32 + lr;
+        rc = rowcol[r];
+        active = rc >= 0;
         // what the fold needs is fetched behind the sweep: registers are what the sweep is short of, and the co-resident
         // workgroup covers the wait.  C0 = sum_c q_c + q_const = c_lo + 2^24 c_hi, 0 <= c_lo < 2^24 (see the two-sweep form).
         const double sg = active ? sigma[r] : 0.0;
