@@ -10,9 +10,11 @@ from ._lib import (EXCLUDED, FREE, PENALISED, GMLConvergenceError, GMLError, Mul
 from .factor_graph import FactorGraph, matrix_to_terms, permutations, check_model_data  # noqa: F401
 from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, GMLMethod,  # noqa: F401
                            logRISE, multiRISE)
-from .inference import ConditionalMeans, PredictiveCheck, conditional_means, conditional_sample, predictive_check  # noqa: F401
+from .inference import (ConditionalMeans, Imputation, PredictiveCheck, conditional_means, conditional_sample, impute,  # noqa: F401
+                        impute_sample, predictive_check)
 from .learn import learn  # noqa: F401
 from .likelihood import AIS, LogLikelihood, LogPartition, log_likelihood, log_partition  # noqa: F401
+from .missing import EMStep, ImputationEM, MissingDataResult, learn_missing  # noqa: F401
 from .path import PathResult, learn_path  # noqa: F401
 from .sampling import GMSampler, Gibbs, Glauber, GlauberChains, GlauberTermChains, TemperedTermChains, sample  # noqa: F401
 
@@ -20,4 +22,5 @@ __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multi
            "NLP", "HIP", "FactorGraph", "Problem", "MultiProblem", "GMLError", "GMLConvergenceError", "sample", "GMSampler", "Gibbs",
            "Glauber", "GlauberChains", "GlauberTermChains", "TemperedTermChains", "moments", "EXCLUDED", "FREE", "PENALISED",
            "structure_from_rows", "structure_from_keys", "learn_path", "PathResult", "AIS", "log_partition", "log_likelihood", "LogPartition",
-           "LogLikelihood", "conditional_sample", "conditional_means", "predictive_check", "ConditionalMeans", "PredictiveCheck"]
+           "LogLikelihood", "conditional_sample", "conditional_means", "predictive_check", "ConditionalMeans", "PredictiveCheck",
+           "impute", "impute_sample", "Imputation", "learn_missing", "ImputationEM", "EMStep", "MissingDataResult"]

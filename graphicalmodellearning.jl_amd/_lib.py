@@ -95,7 +95,9 @@ def lib():
     L.gml_problem_create_mcmc_terms_conditional.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, i32, i64, i64,
                                                             C.POINTER(p)]
     L.gml_conditional_means.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
-    L.gml_problem_create_sampled_hist.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
+    L.gml_problem_create_mcmc_terms_masked.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, i32, i64, i64, C.POINTER(p)]
+    L.gml_conditional_means_masked.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
+    L.gml_problem_create_sampled_hist.argtypes =[p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
     L.gml_problem_moments.argtypes = [p, p, p]
@@ -761,6 +763,25 @@ def conditional_chains(terms, n, evidence, hidden, replicas=1, samples_per_chain
     h = C.c_void_p()
     n0, n1 = _node_range(node_range, n)
     check(lib().gml_problem_create_mcmc_terms_conditional(*common, int(order), n0, n1, C.byref(h)))
+    return Problem._from_handle(h, order)
+
+
+def conditional_chains_masked(terms, n, evidence, mask, replicas=1, samples_per_chain=1, burn_in=200, thin=10, seed=0, *, means=False,
+                              order=2, node_range=None):
+    """The conditional chains whose hidden set is a property of the row (include/gml.h): evidence and mask two open Problems of the same
+    n, K and device; a -1 in row k of the mask hides that spin in row k of the evidence.  means=False:
+    gml_problem_create_mcmc_terms_masked, a Problem of K replicas samples_per_chain rows (row (t, r, k) at (t replicas + r) K + k).
+    means=True: gml_conditional_means_masked, float64 [n, K replicas] (observed entries hold the evidence value)."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    common = (_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, mask._h, int(replicas), int(samples_per_chain), int(burn_in),
+              int(thin), int(seed))
+    if means:
+        out = np.zeros((max(int(n), 0), evidence.K * max(int(replicas), 0)))
+        check(lib().gml_conditional_means_masked(*common, _ptr(out)))
+        return out
+    h = C.c_void_p()
+    n0, n1 = _node_range(node_range, n)
+    check(lib().gml_problem_create_mcmc_terms_masked(*common, int(order), n0, n1, C.byref(h)))
     return Problem._from_handle(h, order)
 
 

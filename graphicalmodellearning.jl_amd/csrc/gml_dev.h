@@ -253,6 +253,14 @@ void launch_cond_chains(const TermChainSpin *dhspin, const TermChainSpin *dcspin
                         const unsigned *drec, const unsigned *dSb, int64_t wpr, int64_t K, int64_t n, int64_t H, int64_t chains,
                         int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout, int64_t ld, double *dmeans, long long *dcst,
                         hipStream_t st);
+// Conditional chains whose hidden set is a property of the row (gml_masked_chains.hip): chain r K + k hides the spins whose bit is set
+// in row k of the sign bits dMb [n][mwpr] of a second handle and takes the others from row k of dSb [n][wpr].  dspin [n]: the spin
+// records of k_term_chains over all incidences.  dout [n][ld] or NULL; dmeans [n][chains] (every entry written) or NULL.  The tile is
+// masked_chains_tile(n, chains): term_chains_tile's rule (and its test hook) at twice the state words, 0 beyond n = 8192.
+int masked_chains_tile(int64_t n, int64_t chains);
+void launch_masked_chains(const TermChainSpin *dspin, const unsigned *drec, const unsigned *dSb, int64_t wpr, const unsigned *dMb,
+                          int64_t mwpr, int64_t K, int64_t n, int64_t chains, int burn_in, int thin, int spc, unsigned long long seed,
+                          int8_t *dout, int64_t ld, double *dmeans, hipStream_t st);
 
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].

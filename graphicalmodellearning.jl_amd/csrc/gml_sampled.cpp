@@ -587,29 +587,66 @@ extern "C" int gml_log_partition_ais(const int32_t *keys, int key_stride, const 
     return GML_OK;
 }
 
+// The device part of the _masked entry points (conditional_chains has made every check): the spin records of k_term_chains over all
+// incidences, the two handles' sign bits, one launch.  means [n][chains] (host) or NULL; out as conditional_chains.
+static int masked_chains(const Incidences &inc, int64_t n, gml_problem *evidence, gml_problem *mask, int64_t chains, int64_t samples_per_chain,
+                         int burn_in, int thin, uint64_t seed, int order, int64_t node0, int64_t node1, gml_problem **out, double *means) {
+    std::vector<TermChainSpin> spin;
+    std::vector<unsigned> rec;
+    build_spin_records(inc, spin, rec);
+    const int device = evidence->device;
+    if (int rc = gml_check_device(device)) return rc;
+    const int64_t M = chains * samples_per_chain, ld = round_up(M, 256);
+    SamplerStaging s;
+    if (out ? s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true) : s.open(device)) return s.rc;
+    s.ok(hipStreamSynchronize(evidence->st), "hipStreamSynchronize"); // (whatever the caller last ran on the two handles)
+    s.ok(hipStreamSynchronize(mask->st), "hipStreamSynchronize");
+    const TermChainSpin *dspin = s.upload(spin);
+    const unsigned *drec = s.upload(rec);
+    const size_t nmeans = (size_t)n * (size_t)chains;
+    double *dmeans = means ? s.alloc<double>(nmeans) : nullptr; // (the kernel writes every entry)
+    if (s.rc) return s.rc;
+    launch_masked_chains(dspin, drec, evidence->d.Sb, evidence->d.Kp / 32, mask->d.Sb, mask->d.Kp / 32, evidence->K, n, chains, burn_in, thin,
+                         (int)samples_per_chain, (unsigned long long)seed, s.out, ld, dmeans, s.st);
+    s.ok(hipGetLastError(), "the sampler's launch");
+    if (means) s.ok(hipMemcpyAsync(means, dmeans, sizeof(double) * nmeans, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    if (!out) return s.sync();
+    return s.finish(true, ld, false, out); // the recorded states, spin-major; row (t, r, k) belongs to evidence row k
+}
+
 // gml_problem_create_mcmc_terms_conditional and gml_conditional_means behind one body (gml_cond_chains.hip): out != NULL makes the handle
-// of the recorded states, means != NULL ([H][K replicas], host) receives the Rao-Blackwellised conditional means.
+// of the recorded states, means != NULL ([H][K replicas], host) receives the Rao-Blackwellised conditional means.  per_row: the
+// _masked entry points (gml_masked_chains.hip) -- the hidden set comes row by row from the sign bits of the handle `rowmask`, not from
+// hidden [n]; means is [n][K replicas].
 static int conditional_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
-                              const uint8_t *hidden, int replicas, int64_t samples_per_chain, int burn_in, int thin, uint64_t seed, int order,
-                              int64_t node0, int64_t node1, gml_problem **out, double *means) {
+                              const uint8_t *hidden, gml_problem *rowmask, bool per_row, int replicas, int64_t samples_per_chain, int burn_in,
+                              int thin, uint64_t seed, int order, int64_t node0, int64_t node1, gml_problem **out, double *means) {
     if (!evidence) return fail(GML_EINVAL, "evidence is NULL");
-    if (!hidden) return fail(GML_EINVAL, "hidden is NULL");
+    if (per_row ? !rowmask : !hidden) return fail(GML_EINVAL, per_row ? "mask is NULL" : "hidden is NULL");
     if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
     if (n != evidence->n) return fail(GML_EINVAL, "n = %lld differs from the evidence handle's %lld spins", (long long)n, (long long)evidence->n);
+    if (per_row && (rowmask->n != evidence->n || rowmask->K != evidence->K || rowmask->device != evidence->device))
+        return fail(GML_EINVAL, "the mask handle (n = %lld, %lld rows, device %d) differs from the evidence handle (n = %lld, %lld rows, device %d)",
+                    (long long)rowmask->n, (long long)rowmask->K, rowmask->device, (long long)evidence->n, (long long)evidence->K, evidence->device);
     if (replicas < 1) return fail(GML_EINVAL, "replicas must be at least 1 (given %d)", replicas);
     const int64_t K = evidence->K;
     if (K > ((int64_t)1 << 40) / replicas) return fail(GML_EINVAL, "the evidence handle's rows times replicas is too large");
     const int64_t chains = K * replicas;
     if (int rc = check_chain_args(n, chains, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
     std::vector<int> hid;
-    for (int64_t i = 0; i < n; ++i)
+    for (int64_t i = 0; !per_row && i < n; ++i)
         if (hidden[i]) hid.push_back((int)i);
-    if (hid.empty()) return fail(GML_EINVAL, "no spin is hidden");
+    if (!per_row && hid.empty()) return fail(GML_EINVAL, "no spin is hidden");
     if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
     if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
         return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
                     (long long)n);
+    if (per_row && masked_chains_tile(n, chains) == 0) // (state and mask words of 64 chains: twice the LDS of the other chain kernels)
+        return fail(GML_EUNSUPPORTED, "the per-row masked chain kernel supports n <= %lld spins (n = %lld)",
+                    (long long)(kMcmcChainsLds / (64 * 4 * 2) * 32), (long long)n);
     if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
+    if (per_row) return masked_chains(build_incidences(keys, key_stride, weights, nterms, n), n, evidence, rowmask, chains, samples_per_chain,
+                                      burn_in, thin, seed, order, node0, node1, out, means);
     // one stream of records for the hidden spins: all their incidences, or (the constant part of the field) those whose other spins are
     // all visible and those with a hidden other spin as two sets.  The constant costs an update one 8-byte global load and saves it
     // the LDS reads of the const records: the split is taken when these average kCondSplitReads per hidden spin (measured: a
@@ -666,16 +703,33 @@ extern "C" int gml_problem_create_mcmc_terms_conditional(const int32_t *keys, in
                                                          int64_t samples_per_chain, int burn_in, int thin, uint64_t seed, int order,
                                                          int64_t node0, int64_t node1, gml_problem **out) {
     if (int rc = check_out(out)) return rc;
-    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, hidden, replicas, samples_per_chain, burn_in, thin, seed, order,
-                              node0, node1, out, nullptr);
+    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, hidden, nullptr, false, replicas, samples_per_chain, burn_in, thin,
+                              seed, order, node0, node1, out, nullptr);
 }
 
 extern "C" int gml_conditional_means(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
                                      gml_problem *evidence, const uint8_t *hidden, int replicas, int64_t samples_per_chain, int burn_in,
                                      int thin, uint64_t seed, double *means) {
     if (!means) return fail(GML_EINVAL, "means is NULL");
-    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, hidden, replicas, samples_per_chain, burn_in, thin, seed, 2, 0,
-                              n, nullptr, means);
+    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, hidden, nullptr, false, replicas, samples_per_chain, burn_in, thin,
+                              seed, 2, 0, n, nullptr, means);
+}
+
+extern "C" int gml_problem_create_mcmc_terms_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                                    gml_problem *evidence, gml_problem *mask, int replicas, int64_t samples_per_chain,
+                                                    int burn_in, int thin, uint64_t seed, int order, int64_t node0, int64_t node1,
+                                                    gml_problem **out) {
+    if (int rc = check_out(out)) return rc;
+    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, nullptr, mask, true, replicas, samples_per_chain, burn_in, thin,
+                              seed, order, node0, node1, out, nullptr);
+}
+
+extern "C" int gml_conditional_means_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                            gml_problem *evidence, gml_problem *mask, int replicas, int64_t samples_per_chain, int burn_in,
+                                            int thin, uint64_t seed, double *means) {
+    if (!means) return fail(GML_EINVAL, "means is NULL");
+    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, nullptr, mask, true, replicas, samples_per_chain, burn_in, thin,
+                              seed, 2, 0, n, nullptr, means);
 }
 
 extern "C" int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,

@@ -6,7 +6,11 @@ the hidden spins only).  A conditional mean is Rao-Blackwellised: not the averag
 conditional expectation of the spin given all the others at the moment it was updated -- the same expectation with less variance,
 and exact (no sampling at all) when one spin is hidden.  predictive_check hides the same spins in every row of a data set and scores
 the predictions against the values the data hold: held-out predictive accuracy, the check of a fit that neither a
-pseudo-likelihood nor an AIS likelihood gives."""
+pseudo-likelihood nor an AIS likelihood gives.
+
+impute / impute_sample are the same two for data with holes, where every row lacks its own set of spins (0 in the histogram matrix):
+the hidden set is read per row from a second resident handle (gml_conditional_means_masked, gml_problem_create_mcmc_terms_masked).
+missing.learn_missing builds stochastic-imputation EM on them."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -110,6 +114,113 @@ def conditional_means(model, evidence, hidden, sampler=None, *, replicas=1, seed
     else:
         stderr = np.full(per.shape[1:], np.nan)
     return ConditionalMeans(per.mean(axis=0), stderr, per, spins, counts)
+
+
+@dataclass
+class Imputation:
+    """means [K', n]: E[s_i | the observed spins of row k] where row k lacks spin i, averaged over the replicas, and the observed value
+    (+-1) where it does not; stderr [K', n]: the standard deviation over replicas / sqrt(replicas) -- 0 for an observed entry, NaN for
+    one replica; missing [K', n] bool.  K' rows: the rows of the given matrix, one of count c expanded into c consecutive rows."""
+    means: np.ndarray
+    stderr: np.ndarray
+    missing: np.ndarray
+
+
+def _missing_rows(samples):
+    """(values int8 [K', n] with +1 in place of a hole, missing bool [K', n]) of a K x (1+n) histogram matrix whose spin entries are in
+    {-1, 0, +1}, 0 = missing.  A row of count c becomes c consecutive rows: every original sample has its own holes to fill.  Counts that
+    are not positive integers and any other spin entry are refused."""
+    s = np.asarray(samples)
+    if s.ndim != 2 or s.shape[1] < 2:
+        raise ValueError("samples must be a K x (1+n) histogram matrix")
+    counts, spins = s[:, 0], s[:, 1:]
+    if not np.all(np.isfinite(counts)) or np.any(counts < 1) or np.any(counts != np.floor(counts)):
+        raise ValueError("the counts of data with missing entries must be positive integers (a row of count c is expanded into c rows)")
+    if not np.all((spins == -1) | (spins == 0) | (spins == 1)):
+        raise ValueError("the spin entries of data with missing entries must be -1, +1 or 0 (0 = missing)")
+    rows = np.repeat(np.arange(s.shape[0]), counts.astype(np.int64))
+    missing = (spins == 0)[rows]
+    return np.where(missing, 1, spins[rows]).astype(np.int8), missing
+
+
+def _mask_order(missing):
+    """the stable order of the rows by their packed masks (spin 0 the most significant bit): rows that lack the same spins become
+    neighbours, and a wave of 64 chains sweeps the union of what its rows lack"""
+    return np.lexsort(np.packbits(missing, axis=1).T[::-1])
+
+
+class _Holes:
+    """data with holes as two open handles of the same rows: `evidence` (a hole holds +1, which plays no part) and `mask` (-1 = missing);
+    closed on exit.  The handles hold the rows in the order of _mask_order (row j of the handles is the caller's row perm[j], and
+    caller's row i is handle row inverse[i]); the chains are numbered in that order, r K + j, and so are their random streams."""
+
+    def __init__(self, values, missing, order=2, device=0):
+        self.perm = _mask_order(missing)
+        self.inverse = np.argsort(self.perm)
+        self.values, self.missing, self.order, self.device = values[self.perm], missing[self.perm], int(order), int(device)
+        self.K, self.n = values.shape
+        self.evidence = self.mask = None
+
+    def __enter__(self):
+        self.evidence = _lib.Problem(spins=self.values, order=self.order, device=self.device)
+        try:
+            self.mask = _lib.Problem(spins=np.where(self.missing, -1, 1).astype(np.int8), device=self.device)
+        except Exception:
+            self.evidence.close()
+            raise
+        return self
+
+    def __exit__(self, *a):
+        for p in (self.mask, self.evidence):
+            if p is not None:
+                p.close()
+
+    def chains(self, model, sampler, replicas, seed, means, order=None):
+        """_lib.conditional_chains_masked of `model` on the two handles: rows in the handles' order"""
+        args = _term_list_args(model, _problem_args(model))
+        terms = args["terms"] if len(args["terms"]) else {(1,): 0.0}  # (a model without a term: every update is a coin flip)
+        return _lib.conditional_chains_masked(terms, self.n, self.evidence, self.mask, int(replicas), sampler.samples_per_chain,
+                                              sampler.burn_in, sampler.thin, seed, means=means,
+                                              order=args.get("order", 2) if order is None else order)
+
+
+def _impute_args(samples, sampler, replicas):
+    sampler = _sampler(sampler)
+    if int(replicas) < 1:
+        raise ValueError(f"replicas must be at least 1 (given {replicas})")
+    return sampler, _missing_rows(samples)  # (refused before a handle is opened)
+
+
+def impute_sample(model, samples, sampler=None, *, replicas=1, seed=0):
+    """Completions of data with holes: `samples` is a K x (1+n) histogram matrix whose spin entries are -1, +1 or 0 = missing (counts:
+    positive integers; a row of count c stands for c samples, each completed on its own).  Every row keeps its observed spins and has
+    its missing ones drawn from the model's conditional distribution given them, by Glauber chains whose hidden set is the row's own
+    (gml_problem_create_mcmc_terms_masked).  model, sampler as conditional_sample.  Returns a Problem of K' replicas samples_per_chain rows
+    of count 1, K' the number of expanded rows: row (t replicas + r) K' + k is sample t of replica r of expanded row k, in the caller's
+    order.  On the device the rows run in the stable order of their packed masks, so that the 64 chains of a wave lack similar spins;
+    chain numbers, and so the random streams, follow that order, and the completed rows are put back into the caller's order through
+    the host (learn_missing, which does not care about the order, skips that)."""
+    sampler, (values, missing) = _impute_args(samples, sampler, replicas)
+    with _Holes(values, missing) as holes:
+        with holes.chains(model, sampler, replicas, seed, False) as q:
+            states, order = q.spins(), q.order
+    states = states.reshape(-1, holes.K, holes.n)[:, holes.inverse].reshape(-1, holes.n)
+    return _lib.Problem(spins=states, order=order)
+
+
+def impute(model, samples, sampler=None, *, replicas=1, seed=0):
+    """Rao-Blackwellised conditional means of the missing entries of `samples` (as impute_sample) given the observed entries of the
+    same row (gml_conditional_means_masked).  No handle is returned.  Returns an Imputation, its rows in the caller's order."""
+    sampler, (values, missing) = _impute_args(samples, sampler, replicas)
+    with _Holes(values, missing) as holes:
+        raw = holes.chains(model, sampler, replicas, seed, True)
+    R, (K, n) = int(replicas), values.shape
+    per = raw.reshape(n, R, K).transpose(1, 2, 0)[:, holes.inverse]  # [n][r K + j] -> [r][k][i]
+    if R > 1:
+        stderr = per.std(axis=0, ddof=1) / np.sqrt(R)
+    else:
+        stderr = np.where(missing, np.nan, 0.0)
+    return Imputation(per.mean(axis=0), stderr, missing)
 
 
 def predictive_check(model, data, hidden, sampler=None, *, replicas=1, seed=0):

@@ -408,6 +408,43 @@ int gml_conditional_means(const int32_t *keys, int key_stride, const double *wei
                           uint64_t seed, double *means /* [H][K * replicas], host */);
 
 /*
+ * gml_problem_create_mcmc_terms_masked, gml_conditional_means_masked -- the conditional chains for data with holes: the hidden set is a
+ * property of the ROW.  "This sample lacks these spins, that sample lacks others: what are they?"
+ * Inputs.  A term list, as for gml_problem_create_mcmc_terms_conditional.  A resident handle `evidence` (n, K rows).  A resident handle
+ *   `mask` on the same device with the same n and K: in its sign bits a set bit (spin -1) means "hidden in this row" and +1 means
+ *   "observed".  replicas >= 1, samples_per_chain, burn_in, thin, seed.  The mask is a handle because that reuses the ingest and the
+ *   layout of the sign bits, because it stays resident, and because gml_problem_split with one seed cuts evidence and mask into matching
+ *   folds.  The counts of both handles play no part.  Where row k of the mask hides spin s, the value row k of the evidence holds for
+ *   s plays no part either.
+ * Everything else is the rule of gml_problem_create_mcmc_terms_conditional with "hidden" read per row.
+ * Chain index.  Chain c = r K + k is replica r of row k.
+ * Start.  Observed spins come from evidence row k.  Hidden spins come from chain_start_bit(seed, c, n, s).
+ * Sweep.  Sweep sw visits i = 0 .. n - 1 in ascending order.  Chain c updates spin i iff it is hidden in row k.
+ * Update.  h = a_i + sigma_i (double) S_i over all incidences of spin i, with the unfiltered records of
+ *   gml_problem_create_mcmc_terms_chains.  pup = 1 / (1 + exp(-2 h)).  The new spin is +1 iff u01(seed, sw, c n + i) < pup.
+ * Recorded sweeps.  As gml_problem_create_mcmc_terms_chains: row t * chains + c.
+ * Means.  Layout is [n][K * replicas], FP64.  For a hidden entry: the Rao-Blackwellised mean of 2 pup - 1 over the recorded sweeps,
+ *   summed in sweep order, times 1.0 / samples_per_chain.  For an observed entry: the evidence value, +-1.0.
+ * Rows without holes.  A row with no hidden spin is legal.  Its chains return the row.
+ * Consequence.  When every row of `mask` equals one vector, states and means (its rows i_0 < ... < i_{H-1}) are those of
+ *   gml_problem_create_mcmc_terms_conditional / gml_conditional_means with that vector as `hidden`, bit for bit.
+ * The random stream is counter based on (sw, c n + i): the library evaluates an update only where some chain of a group of 64
+ *   consecutive chains hides the spin, and what it skips changes no bit.  Cost per chain-sweep: the incidences of the spins hidden
+ *   by one of the 64 chains c .. c + 63 (c a multiple of 64) -- rows with similar masks are cheapest next to each other.
+ * GML_EINVAL, before any device work, in the order of gml_problem_create_mcmc_terms_conditional: NULL evidence, mask, out or means; n
+ *   different from the evidence handle's; a mask handle whose n, K or device differs from the evidence handle's; replicas < 1;
+ *   everything gml_problem_create_mcmc_terms_chains rejects, with chains = K * replicas.  GML_EUNSUPPORTED: the limits of
+ *   gml_problem_create_mcmc_terms_chains, and n > 8192 (a chain holds its state and its mask on chip: twice the words).
+ * gml_conditional_means_masked makes no handle and no state buffer; every device buffer of both is released on every path.
+ */
+int gml_problem_create_mcmc_terms_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                         gml_problem *evidence, gml_problem *mask, int replicas, int64_t samples_per_chain, int burn_in,
+                                         int thin, uint64_t seed, int order, int64_t node0, int64_t node1, gml_problem **out);
+int gml_conditional_means_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                 gml_problem *evidence, gml_problem *mask, int replicas, int64_t samples_per_chain, int burn_in, int thin,
+                                 uint64_t seed, double *means /* [n][K * replicas], host */);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
