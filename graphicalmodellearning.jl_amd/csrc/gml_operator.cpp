@@ -117,6 +117,7 @@ struct PassKnobs {
     int64_t kchunk = 0, kpart = 0;
     gml::SlotResult *res = nullptr;
     int64_t *plan_out = nullptr;
+    const int *vmap = nullptr; // a Hessian-vector pass: the slot whose V planes and tau each slot reads (device; NULL: its own)
 };
 static int launch_pass(gml_problem *p, int64_t Rp, int ngroups, int npad, int form, int precision, bool want_grad, bool hv,
                        const double *tauovr, bool compact, hipEvent_t *ev, const PassKnobs *kn = nullptr) {
@@ -149,6 +150,7 @@ static int launch_pass(gml_problem *p, int64_t Rp, int ngroups, int npad, int fo
             a.kpart = kn->kpart;
             a.res = kn->res;
             a.plan_out = kn->plan_out;
+            if (hv && kn->vmap) a.vmap = kn->vmap;
         }
         std::string err;
         const int rc = gml::i8_pass(&p->i8ws, p->d, p->ws_rows, a, st, ev, &err);
@@ -892,16 +894,19 @@ extern "C" int gml_test_hv_sparse(gml_problem *p, int formulation, int precision
 //            ksub, kchunk, kpart (0: planned in the pass)
 //   tauovr [nrows] or NULL: the per-row scale of V imposed on the objective pass (the operator's rescaled re-run), 0 = from the bound
 //   vec [nrows][ld]: the directions (read when hv)
+//   vslot [nrows] or NULL (gml_test_i8_pass: NULL): product row i, in slot i, multiplies the weights of slot vslot[i] -- its node is
+//            nodes[vslot[i]], in whose parameter order vec[i] and hv[i] are -- so that one slot's V can serve several directions
 // Out: f [nrows] and g [nrows][ld] (may be NULL) of the objective pass, hv [nrows][ld] of the products, all as the passes leave them
 // (logRISE: Z, grad Z and Hess Z v, without the log finish); slots [2][nrows][3] = {f, tau, mmax} of every row in each pass (each pass's
 // SlotResult); plan [2] = the kchunk, kpart of the product pass.
-extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, int64_t nrows, const int64_t *nodes, const double *theta,
-                                const double *tauovr, const double *vec, int64_t ld, const int64_t *kn, double *f, double *g, double *hv,
-                                double *slots, int64_t *plan) {
+extern "C" int gml_test_i8_pass_vslot(gml_problem *p, int formulation, int precision, int64_t nrows, const int64_t *nodes, const double *theta,
+                                      const double *tauovr, const double *vec, int64_t ld, const int64_t *kn, double *f, double *g, double *hv,
+                                      double *slots, int64_t *plan, const int32_t *vslot) {
     if (!p || !nodes || !theta || !kn || !f || !slots) return fail(GML_EINVAL, "NULL argument");
     if (precision != GML_PREC_F64 && !gml_is_i8(precision)) return fail(GML_EINVAL, "unknown precision %d", precision);
     const int hvk = (int)kn[5];
     if (hvk && (!vec || !hv)) return fail(GML_EINVAL, "a product pass needs vec and hv");
+    if (vslot && (!hvk || !gml_is_i8(precision))) return fail(GML_EINVAL, "a slot map belongs to a product pass of an int8-limb precision");
     bool dev = false;
     int rc = check_rows(p, formulation, nrows, nodes, ld, theta, f, nullptr, "theta and f", &dev);
     if (rc) return rc;
@@ -909,11 +914,24 @@ extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, 
     const int64_t Qp = p->d.Qp, Rp = gml_round_up(nrows, 32);
     if ((rc = gml_ensure_ws(p, nrows))) return rc;
     hipStream_t st = p->st;
-    std::vector<NodeLayout> lay;
+    std::vector<NodeLayout> lay, llay;
     std::vector<double> Th((size_t)nrows * Qp, 0.0), Vc((size_t)nrows * Qp, 0.0), Gi((size_t)nrows * Qp, 0.0), Hi((size_t)nrows * Qp, 0.0),
         fv((size_t)Rp, 0.0);
-    if (to_internal(p, nrows, nodes, lay, theta, ld, Th.data(), hvk ? vec : nullptr, hvk ? Vc.data() : nullptr) >= 0)
+    std::vector<int64_t> lnodes; // slot map: the node of every product row
+    std::vector<int> vm;
+    if (vslot) {
+        lnodes.resize((size_t)nrows);
+        vm.assign((size_t)Rp, 0);
+        for (int64_t i = 0; i < nrows; ++i) {
+            if (vslot[i] < 0 || vslot[i] >= nrows) return fail(GML_EINVAL, "slot map entry %lld out of range", (long long)i);
+            lnodes[i] = nodes[vslot[i]];
+            vm[i] = vslot[i];
+        }
+    }
+    const bool own = hvk && !vslot; // the directions in the layout of the rows' own nodes
+    if (to_internal(p, nrows, nodes, lay, theta, ld, Th.data(), own ? vec : nullptr, own ? Vc.data() : nullptr) >= 0)
         return fail(GML_EINVAL, "a row contains a non-finite value");
+    if (vslot && to_internal(p, nrows, lnodes.data(), llay, vec, ld, Vc.data()) >= 0) return fail(GML_EINVAL, "a direction contains a non-finite value");
     std::vector<uint8_t> act((size_t)nrows, 1);
     std::vector<int> groups;
     int npad = 0;
@@ -925,10 +943,16 @@ extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, 
         if ((rc = rs.upload(p, Rp))) return rc;
     }
     gml::SlotResult *dRes = nullptr;
+    int *dVmap = nullptr;
     HIPCHK(dev_malloc(&dRes, sizeof(gml::SlotResult) * 2 * Rp));
-    if (hipError_t e = hipMemsetAsync(dRes, 0, sizeof(gml::SlotResult) * 2 * Rp, st); e != hipSuccess) {
+    hipError_t e0 = hipMemsetAsync(dRes, 0, sizeof(gml::SlotResult) * 2 * Rp, st);
+    if (e0 == hipSuccess && vslot) e0 = dev_malloc(&dVmap, sizeof(int) * Rp);
+    if (e0 == hipSuccess && vslot) e0 = hipMemcpyAsync(dVmap, vm.data(), sizeof(int) * Rp, hipMemcpyHostToDevice, st);
+    if (e0 != hipSuccess) {
+        (void)hipStreamSynchronize(st);
         (void)dev_free(dRes);
-        return fail(GML_EHIP, "gml_test_i8_pass: %s", hipGetErrorString(e));
+        if (dVmap) (void)dev_free(dVmap);
+        return fail(GML_EHIP, "gml_test_i8_pass: %s", hipGetErrorString(e0));
     }
     std::vector<gml::SlotResult> res((size_t)2 * Rp);
     auto run = [&]() -> int {
@@ -957,6 +981,11 @@ extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, 
         k2.kpart = kn[9];
         k2.res = dRes + Rp;
         k2.plan_out = plan;
+        k2.vmap = dVmap;
+        if (vslot) { // (the stream is idle: the control block's pinned twin is free) slot i <- (row i, node of slot vslot[i])
+            int rc3 = upload_ctl(p, nrows, lnodes.data(), act, groups, &npad);
+            if (rc3) return rc3;
+        }
         std::memcpy(p->hTh, Vc.data(), sizeof(double) * nrows * Qp);
         HIPCHK(hipMemcpyAsync(p->dTheta, p->hTh, sizeof(double) * nrows * Qp, hipMemcpyHostToDevice, st));
         rc2 = launch_pass(p, Rp, (int)groups.size(), npad, formulation, precision, true, true, nullptr, false, nullptr, &k2);
@@ -974,10 +1003,11 @@ extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, 
     }
     (void)hipStreamSynchronize(st);
     (void)dev_free(dRes);
+    if (dVmap) (void)dev_free(dVmap);
     if (rc) return rc;
     // (raw sums: the layout gather of RISE, which leaves logRISE's Z and grad Z as they are)
     to_reference(lay, p->P, Qp, GML_RISE, fv.data(), Gi.data(), f, kn[2] ? g : nullptr, ld);
-    if (hvk) to_reference(lay, p->P, Qp, GML_RISE, fv.data(), Hi.data(), nullptr, hv, ld);
+    if (hvk) to_reference(vslot ? llay : lay, p->P, Qp, GML_RISE, fv.data(), Hi.data(), nullptr, hv, ld);
     for (int pass = 0; pass < 2; ++pass)
         for (int64_t r = 0; r < nrows; ++r) {
             const gml::SlotResult &s = res[(size_t)pass * Rp + r];
@@ -987,6 +1017,12 @@ extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, 
             o[2] = (double)s.mmax;
         }
     return GML_OK;
+}
+
+extern "C" int gml_test_i8_pass(gml_problem *p, int formulation, int precision, int64_t nrows, const int64_t *nodes, const double *theta,
+                                const double *tauovr, const double *vec, int64_t ld, const int64_t *kn, double *f, double *g, double *hv,
+                                double *slots, int64_t *plan) {
+    return gml_test_i8_pass_vslot(p, formulation, precision, nrows, nodes, theta, tauovr, vec, ld, kn, f, g, hv, slots, plan, nullptr);
 }
 
 // Timing hook with the parameters RESIDENT in HBM: Theta is uploaded once, then `warmup + steps` passes run back

@@ -339,6 +339,41 @@ extern "C" int gml_test_i8_gacc(gml_problem *p, int64_t *dims, int32_t *gacc, do
     return GML_OK;
 }
 
+// Test hook (not part of include/gml.h): what the last Hessian-vector (product) pass of the int8-limb GEMM kernels left on the device --
+// the limb planes Uq of the products u_k, the pass's own slot scalars (sc[1]) and the Tq image of the directions it quantised.  Read
+// only: synchronises the handle's stream and copies; launches nothing.  The V planes the pass read, its accumulators and G come back
+// through gml_test_i8_pass_state and gml_test_i8_gacc.
+//   dims [8]: 0 slots, 1 planes of Uq (LB = 4), 2 Kp, 3 K, 4 LF of the product pass that last wrote Tq (0: an objective pass has
+//             rewritten it since, or none ran), 5 Qfp, 6 bytes of the Tq image at that LF, 7 Uq exists
+//   out [9] or NULL (only the sizes); a NULL entry is skipped:
+//             0 Uq int8 [slots][4][Kp] in the layout of gml_i8.h (vq_off with 4 planes);  1 sigma, 2 tau, 3 invtau double [slots];
+//             4 qconst, 5 csum, 6 asum int64 [slots];  7 mmax uint32 [slots];  8 Tq int8 [dims 6] = [tile][Qfp / 64][LF][32][64]
+extern "C" int gml_test_i8_uq(gml_problem *p, int64_t *dims, void **out) {
+    if (!p || !dims) return fail(GML_EINVAL, "bad argument");
+    const gml::I8Ws *w = static_cast<const gml::I8Ws *>(p->i8ws);
+    const DevProblem &d = p->d;
+    const int64_t ns = w ? w->slots : 0;
+    const int64_t v[8] = {ns, gml::LB, d.Kp, d.K, w ? w->tq_hv_lf : 0, d.Qfp, w ? ns * w->tq_hv_lf * d.Qfp : 0, w && w->Uq};
+    std::copy(v, v + 8, dims);
+    if (!out || !w) return GML_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->st));
+    auto get = [&](int i, const void *src, size_t bytes) -> hipError_t {
+        return out[i] && src && bytes ? hipMemcpy(out[i], src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIPCHK(get(0, w->Uq, (size_t)ns * gml::LB * d.Kp));
+    const gml::SlotScalars &sc = w->sc[1];
+    HIPCHK(get(1, sc.sigma, sizeof(double) * ns));
+    HIPCHK(get(2, sc.tau, sizeof(double) * ns));
+    HIPCHK(get(3, sc.invtau, sizeof(double) * ns));
+    HIPCHK(get(4, sc.qconst, sizeof(long long) * ns));
+    HIPCHK(get(5, sc.csum, sizeof(long long) * ns));
+    HIPCHK(get(6, sc.asum, sizeof(long long) * ns));
+    HIPCHK(get(7, sc.mmax, sizeof(unsigned) * ns));
+    HIPCHK(get(8, w->Tq, (size_t)v[6])); // (the buffer is sized for the workspace's LF >= every product LF)
+    return GML_OK;
+}
+
 // Test hook (not part of include/gml.h): V of the FP64 pass (k_fwd_f64 writes it, k_bwd_f64 and k_hess_f64 read it) as the last pass
 // left it.  Read only: synchronises the handle's stream and copies; launches nothing.
 //   dims [3]: 0 rows V is sized for (0: no FP64 pass yet), 1 Kp, 2 K

@@ -57,7 +57,7 @@ partial: Kp = 3072 (K rounded up to 1024), plan kchunk = 2048 (i8_split_plan: tw
 up to 256 samples, raised to the minimum chunk of 2048), chunks
 [0, 2048) and [2048, 3072).  More than 2^24 configurations (gplanes > 1) are out of scope: their Vq read-back is gigabytes, and
 test_pass_forms_beyond_2p24_configurations (test_gpu_i8_pass_variants.py) stays their guard.  Product (Hessian-vector) passes write
-Uq, not Vq: they stay with test_gpu_i8_pass_variants.py and test_gpu_hv_sparse_direct.py."""
+Uq, not Vq: test_gpu_i8_hv_exact.py cuts them there, beside test_gpu_i8_pass_variants.py and test_gpu_hv_sparse_direct.py."""
 import ctypes as C
 import importlib
 
