@@ -81,6 +81,14 @@ extern "C" int gml_test_sandwich_grams(gml_problem *p, int formulation, const do
     const GmlSandwichHook hook{nrows, rows, cap, lists, msz, A, B, g};
     return gml_sandwich_run(p, formulation, x, ld, structure, ld_s, se.data(), nullptr, nullptr, &hook);
 }
+// 1 if everything queued on the handle's stream has completed, 0 while work is pending there (or the query fails).  Queues nothing and
+// waits for nothing.  tests/test_gpu_device_pointers.py: a call that "returns when its outputs are written" leaves the stream idle.
+extern "C" int gml_test_stream_idle(gml_problem *p) {
+    if (!p || hipSetDevice(p->device) != hipSuccess) return 0;
+    if (hipStreamQuery(p->st) == hipSuccess) return 1;
+    (void)hipGetLastError(); // (hipErrorNotReady is no failure of the caller's next HIP call)
+    return 0;
+}
 // A handle that holds sizes only -- no device, no samples -- for the tests of argument checks that run before any device work
 // (tests/test_host_sandwich.py).  Release it with gml_problem_destroy.
 extern "C" int gml_test_problem_stub(int64_t n, int64_t P, int order, int64_t node0, int64_t node1, gml_problem **out) {

@@ -607,6 +607,9 @@ int gml_hessvec_batch_prec(gml_problem *p, int formulation, int precision, int64
  * Symmetrisation (:184-186, :135-149) needs all rows: handles over all nodes take gml_learn_matrix / gml_learn_terms (solve and
  * result assembly in one call, on the device), node shards gather their rows and call gml_matrix_symmetrize / gml_terms_assemble.
  * Returns GML_ENOTCONV if some node stayed above opts->tol (out is still filled).
+ * Ordering, for gml_learn and every gml_learn_* below: the solve runs on the handle's own stream, a blocking stream -- ordered after
+ * everything the caller enqueued on the device's null stream before the call (a device x0 / structure / out written or filled there);
+ * work on other streams must have completed.  The call returns when out (terms) and kkt are written and that stream is idle.
  */
 int gml_learn(gml_problem *p, int formulation, double regularizer_c, const gml_opts *opts,
               double *out, double *kkt, gml_stats *stats);
@@ -663,6 +666,8 @@ int gml_learn_structured(gml_problem *p, int formulation, double regularizer_c, 
  *              not affected.  A row with an empty support: se = 0, GML_SE_OK
  *   times      host, [3], may be NULL: seconds spent on the support lists, the Gram sweep, the factorisations
  * x, se and structure: host pointers or device pointers on the handle's GPU, each detected on its own.
+ * Ordering: the kernels run on the handle's own stream, a blocking stream -- ordered after what the caller enqueued on the device's null
+ * stream before the call; the call returns when se and status are written and that stream is idle.
  * What the numbers mean, and what they do not:
  *   - with penalised active coordinates this is the covariance CONDITIONAL on the selected support and signs, not a post-selection
  *     valid interval; the intended use is after a refit (gml_learn_structured on the kept support), where every parameter is FREE;
@@ -686,6 +691,8 @@ int gml_stderr(gml_problem *p, int formulation, const double *x, int64_t ld, con
  * Structures for gml_learn_structured, built on the device in the (node, slot) layout of the rows (closed-form for multi-body models:
  * no key table).  `structure` is n x P bytes with leading dimension ld_s >= P, host or device pointer; bytes [P, ld_s) of a row are
  * not written.  `device`: where the kernels run when no argument is a device pointer.
+ * Ordering (gml_structure_from_rows, gml_structure_from_keys): the kernels run on the device's NULL stream -- ordered after what the
+ * caller enqueued there before the call; the call returns when structure (and kept) are written and the null stream is idle.
  *
  *   gml_structure_from_rows   from solved rows: rows = the n x P solved rows of all nodes (leading dimension ld, host or device
  *                             pointer; for order 2 also the symmetrised n x n matrix).  A non-field slot (u, S') -- the key S = {u} + S'
@@ -731,7 +738,9 @@ int gml_structure_from_keys(const int32_t *keys, int key_stride, int64_t nterms,
  *   gml_terms_count     number of terms (-1: unsupported order / overflow)
  *   gml_terms_assemble  rows: the n x P solved rows (row u in the layout of gml_learn's `out`, leading dimension ld), host OR device
  *                       pointer; out: gml_terms_count doubles, host OR device pointer.  One kernel launch on `device` (on the
- *                       device that holds rows / out when one of them is a device pointer); host rows are staged through it
+ *                       device that holds rows / out when one of them is a device pointer); host rows are staged through it.
+ *                       Ordering: it runs on the device's NULL stream -- ordered after what the caller enqueued there before the
+ *                       call; the call returns when out is written and the null stream is idle
  *   gml_terms_keys      host only: the keys of the terms [first, first + count), `order` int32 per term, 0-based spins, -1 = unused
  *   gml_terms_rank      host only: position of a key of `len` spins (0-based), -1 if the model has no such key
  *   gml_learn_terms     gml_learn over ALL nodes of the handle + the assembly, the rows never leaving the device: `terms` (host or
@@ -754,7 +763,8 @@ int gml_learn_terms(gml_problem *p, int formulation, double regularizer_c, int s
  *                           leaving the device: out = the n x n matrix the reference's learn returns (host or device pointer);
  *                           stats->t_assemble = the symmetrisation + the copy.  symmetrize == 0: plain gml_learn.
  *   gml_matrix_symmetrize   the same for rows gathered from node shards: rows n x n (leading dimension ld), out n x n, host or
- *                           device pointers, in place allowed
+ *                           device pointers, in place allowed.  Ordering: it runs on the device's NULL stream -- ordered after what
+ *                           the caller enqueued there before the call; the call returns when out is written and that stream is idle
  */
 int gml_learn_matrix(gml_problem *p, int formulation, double regularizer_c, int symmetrize, const gml_opts *opts, double *out,
                      double *kkt, gml_stats *stats);
