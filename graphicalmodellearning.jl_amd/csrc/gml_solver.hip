@@ -9,6 +9,7 @@
 #include "../../include/gml.h"
 #include "gml_dev.h"
 #include "gml_solver.h"
+#include "gml_wg.h"
 
 namespace gml {
 
@@ -19,28 +20,6 @@ __device__ __forceinline__ double pseudo_grad(double x, double g, double lam) {
     if (g + lam < 0) return g + lam;
     if (g - lam > 0) return g - lam;
     return 0.0;
-}
-
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ double block_max(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__device__ __forceinline__ int block_sum_i(int v, int *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
 }
 
 // kind[r][c] from the statistic keys: column c is a parameter of node u iff its key does not contain u and its size
@@ -774,9 +753,8 @@ __global__ __launch_bounds__(256) void k_pcg_faces(const int *__restrict__ rows,
         if (!Wm[i]) continue;
         const double x = X[i], dc = D[i], pg = PG[i];
         total += fabs(pg * dc);
-        if (kind[i] != 2) continue;
-        if (x == 0.0 ? dc * pg > 0.0 : (x + dc) * x < 0.0) {
-            const double fixed = x == 0.0 ? 0.0 : -x;
+        double fixed;
+        if (face_candidate(x, dc, pg, kind[i], &fixed)) {
             mass += fabs(pg * (dc - fixed));
             D[i] = fixed;
             Wm[i] = 0;

@@ -99,6 +99,49 @@ extern "C" int gml_test_problem_stub(int64_t n, int64_t P, int order, int64_t no
     return GML_OK;
 }
 
+namespace {
+// device arrays of one hook call: freed when the call returns, whichever way
+struct DevArrays {
+    std::vector<void *> ptrs;
+    ~DevArrays() {
+        for (void *q : ptrs) (void)dev_free(q);
+    }
+    // n elements on the device, copied from h (NULL: zeroed)
+    template <typename T> hipError_t up(T **d, const T *h, size_t n) {
+        const size_t bytes = sizeof(T) * std::max<size_t>(n, 1);
+        const hipError_t e = dev_malloc(d, bytes);
+        if (e != hipSuccess) return e;
+        ptrs.push_back(*d);
+        return h && n ? hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice) : hipMemset(*d, 0, bytes);
+    }
+    template <typename T> static hipError_t down(T *h, const T *d, size_t n) {
+        return h && n ? hipMemcpy(h, d, sizeof(T) * n, hipMemcpyDeviceToHost) : hipSuccess;
+    }
+};
+// blocks [R][cap][cap], block r being its leading m_r x m_r (0 <= m_r <= cap), into the ragged layout the solver keeps its Hessian
+// blocks in: block r at H + hoff[r] with pitch 32 mt[r], mt[r] = ceil(m_r / 32) tiles; the padding is the identity.  hoff gets R + 1
+// entries.  Returns the largest m_r.
+int pack_ragged_blocks(int R, const int *m, int cap, const double *blocks, std::vector<int> &mt, std::vector<long long> &hoff,
+                       std::vector<double> &H) {
+    mt.assign((size_t)R, 0);
+    hoff.assign((size_t)R + 1, 0);
+    int maxm = 0;
+    for (int r = 0; r < R; ++r) {
+        mt[r] = (m[r] + 31) / 32;
+        hoff[r + 1] = hoff[r] + (long long)mt[r] * 32 * mt[r] * 32;
+        maxm = std::max(maxm, m[r]);
+    }
+    H.assign((size_t)std::max<long long>(hoff[R], 1), 0.0);
+    for (int r = 0; r < R; ++r) {
+        const int hp = 32 * mt[r];
+        for (int i = 0; i < m[r]; ++i)
+            for (int j = 0; j < m[r]; ++j) H[(size_t)hoff[r] + (size_t)i * hp + j] = blocks[((size_t)r * cap + i) * cap + j];
+        for (int i = m[r]; i < hp; ++i) H[(size_t)hoff[r] + (size_t)i * hp + i] = 1.0; // padding: identity
+    }
+    return maxm;
+}
+} // namespace
+
 extern "C" int gml_test_tile_precond(int T, int ntiles, const int *m, const double *tiles /* ntiles x T x T */, double s1, double s2,
                                      const double *g /* ntiles x T */, const double *r /* ntiles x T */, double *z_out /* ntiles x T */,
                                      int device) {
@@ -106,51 +149,29 @@ extern "C" int gml_test_tile_precond(int T, int ntiles, const int *m, const doub
     HIPCHK(hipSetDevice(device));
     const size_t nt = (size_t)ntiles, ne = nt * T;
     std::vector<long long> hoff(nt);
-    std::vector<int> wrow(nt, 0), fv(ne), live(1, 1);
+    std::vector<int> wrow(nt, 0), fv(ne);
+    const int live = 1;
     for (size_t t = 0; t < nt; ++t) hoff[t] = (long long)t * T * T;
     for (size_t e = 0; e < ne; ++e) fv[e] = (int)e; // tile t owns the columns [t T, (t + 1) T) of the one row
+    DevArrays A;
     double *dH = nullptr, *dS1 = nullptr, *dG = nullptr, *dR = nullptr, *dZ = nullptr;
     long long *dHoff = nullptr;
     int *dM = nullptr, *dWrow = nullptr, *dFv = nullptr, *dLive = nullptr;
-    auto freeall = [&]() {
-        void *ptrs[] = {dH, dS1, dG, dR, dZ, dHoff, dM, dWrow, dFv, dLive};
-        for (void *q : ptrs)
-            if (q) (void)dev_free(q);
-    };
-#define TCHK2(expr)                                                                              \
-    do {                                                                                        \
-        if ((expr) != hipSuccess) {                                                             \
-            freeall();                                                                          \
-            return fail(GML_EHIP, "%s failed: %s", #expr, hipGetErrorString(hipGetLastError())); \
-        }                                                                                       \
-    } while (0)
-    TCHK2(dev_malloc(&dH, sizeof(double) * ne * T));
-    TCHK2(dev_malloc(&dS1, sizeof(double)));
-    TCHK2(dev_malloc(&dG, sizeof(double) * ne));
-    TCHK2(dev_malloc(&dR, sizeof(double) * ne));
-    TCHK2(dev_malloc(&dZ, sizeof(double) * ne));
-    TCHK2(dev_malloc(&dHoff, sizeof(long long) * nt));
-    TCHK2(dev_malloc(&dM, sizeof(int) * nt));
-    TCHK2(dev_malloc(&dWrow, sizeof(int) * nt));
-    TCHK2(dev_malloc(&dFv, sizeof(int) * ne));
-    TCHK2(dev_malloc(&dLive, sizeof(int)));
-    TCHK2(hipMemcpy(dH, tiles, sizeof(double) * ne * T, hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dS1, &s1, sizeof(double), hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dG, g, sizeof(double) * ne, hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dR, r, sizeof(double) * ne, hipMemcpyHostToDevice));
-    TCHK2(hipMemset(dZ, 0, sizeof(double) * ne));
-    TCHK2(hipMemcpy(dHoff, hoff.data(), sizeof(long long) * nt, hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dM, m, sizeof(int) * nt, hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dWrow, wrow.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dFv, fv.data(), sizeof(int) * ne, hipMemcpyHostToDevice));
-    TCHK2(hipMemcpy(dLive, live.data(), sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(A.up(&dH, tiles, ne * T));
+    HIPCHK(A.up(&dS1, &s1, 1));
+    HIPCHK(A.up(&dG, g, ne));
+    HIPCHK(A.up(&dR, r, ne));
+    HIPCHK(A.up(&dZ, static_cast<const double *>(nullptr), ne));
+    HIPCHK(A.up(&dHoff, hoff.data(), nt));
+    HIPCHK(A.up(&dM, m, nt));
+    HIPCHK(A.up(&dWrow, wrow.data(), nt));
+    HIPCHK(A.up(&dFv, fv.data(), ne));
+    HIPCHK(A.up(&dLive, &live, 1));
     launch_tile_inverse(T, dH, dHoff, dM, dWrow, dS1, s2, dG, ntiles, nullptr);
     launch_tile_apply(T, dH, dFv, dM, dWrow, dLive, ntiles, (int64_t)ne, dR, dZ, nullptr);
-    TCHK2(hipGetLastError());
-    TCHK2(hipDeviceSynchronize());
-    TCHK2(hipMemcpy(z_out, dZ, sizeof(double) * ne, hipMemcpyDeviceToHost));
-#undef TCHK2
-    freeall();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(A.down(z_out, dZ, ne));
     return GML_OK;
 }
 
@@ -159,67 +180,36 @@ extern "C" int gml_test_tile_precond(int T, int ntiles, const int *m, const doub
 static int test_newton_solve(int R, const int *m, int cap, const double *blocks, const double *pg, double s2, const double *g, double *d_out,
                              int device, const unsigned char *fix /* R x cap or NULL */, const double *dfix /* R x cap */) {
     HIPCHK(hipSetDevice(device));
-    std::vector<long long> hoff((size_t)R + 1, 0);
-    std::vector<int> mt((size_t)R);
-    int maxm = 0;
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < R; ++r)
         if (m[r] < 0 || m[r] > cap || cap > 512) return fail(GML_EINVAL, "bad block size");
-        mt[r] = (m[r] + 31) / 32;
-        hoff[r + 1] = hoff[r] + (long long)mt[r] * 32 * mt[r] * 32;
-        maxm = std::max(maxm, m[r]);
-    }
-    std::vector<double> H((size_t)std::max<long long>(hoff[R], 1), 0.0), s1((size_t)R, 1.0), gz((size_t)R * cap, 0.0);
-    for (int r = 0; r < R; ++r) {
-        const int hp = 32 * mt[r];
-        for (int i = 0; i < m[r]; ++i)
-            for (int j = 0; j < m[r]; ++j) H[(size_t)hoff[r] + (size_t)i * hp + j] = blocks[((size_t)r * cap + i) * cap + j];
-        for (int i = m[r]; i < hp; ++i) H[(size_t)hoff[r] + (size_t)i * hp + i] = 1.0; // padding: identity
-    }
+    std::vector<long long> hoff;
+    std::vector<int> mt;
+    std::vector<double> H;
+    const int maxm = pack_ragged_blocks(R, m, cap, blocks, mt, hoff, H);
+    const size_t nc = (size_t)R * cap;
+    const std::vector<double> s1((size_t)R, 1.0);
+    DevArrays A;
     double *dH = nullptr, *dS1 = nullptr, *dG = nullptr, *dPg = nullptr, *dOut = nullptr, *dSd = nullptr, *dDfix = nullptr;
     long long *dHoff = nullptr;
-    int *dMt = nullptr, *dM = nullptr, *dRedo = nullptr;
+    int *dMt = nullptr, *dM = nullptr;
     uint8_t *dFix = nullptr;
-    auto freeall = [&]() {
-        void *ptrs[] = {dH, dS1, dG, dPg, dOut, dSd, dHoff, dMt, dM, dDfix, dRedo, dFix};
-        for (void *q : ptrs)
-            if (q) (void)dev_free(q);
-    };
-#define TCHK(expr)                                                           \
-    do {                                                                     \
-        if ((expr) != hipSuccess) {                                          \
-            freeall();                                                       \
-            return fail(GML_EHIP, "%s failed: %s", #expr, hipGetErrorString(hipGetLastError())); \
-        }                                                                    \
-    } while (0)
-    TCHK(dev_malloc(&dH, sizeof(double) * H.size()));
-    TCHK(dev_malloc(&dS1, sizeof(double) * R));
-    TCHK(dev_malloc(&dG, sizeof(double) * R * cap));
-    TCHK(dev_malloc(&dPg, sizeof(double) * R * cap));
-    TCHK(dev_malloc(&dOut, sizeof(double) * R * cap));
-    TCHK(dev_malloc(&dSd, sizeof(double) * R));
-    TCHK(dev_malloc(&dHoff, sizeof(long long) * (R + 1)));
-    TCHK(dev_malloc(&dMt, sizeof(int) * R));
-    TCHK(dev_malloc(&dM, sizeof(int) * R));
-    TCHK(hipMemcpy(dH, H.data(), sizeof(double) * H.size(), hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(dS1, s1.data(), sizeof(double) * R, hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(dG, g ? g : gz.data(), sizeof(double) * R * cap, hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(dPg, pg, sizeof(double) * R * cap, hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(dHoff, hoff.data(), sizeof(long long) * (R + 1), hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(dMt, mt.data(), sizeof(int) * R, hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(dM, m, sizeof(int) * R, hipMemcpyHostToDevice));
-    TCHK(hipMemset(dOut, 0, sizeof(double) * R * cap));
+    HIPCHK(A.up(&dH, H.data(), H.size()));
+    HIPCHK(A.up(&dS1, s1.data(), (size_t)R));
+    HIPCHK(A.up(&dG, g, nc)); // (NULL: zeros)
+    HIPCHK(A.up(&dPg, pg, nc));
+    HIPCHK(A.up(&dOut, static_cast<const double *>(nullptr), nc));
+    HIPCHK(A.up(&dSd, static_cast<const double *>(nullptr), (size_t)R));
+    HIPCHK(A.up(&dHoff, hoff.data(), (size_t)R + 1));
+    HIPCHK(A.up(&dMt, mt.data(), (size_t)R));
+    HIPCHK(A.up(&dM, m, (size_t)R));
     if (fix) { // some entries fixed from the start
-        TCHK(dev_malloc(&dFix, (size_t)R * cap));
-        TCHK(dev_malloc(&dDfix, sizeof(double) * R * cap));
-        TCHK(hipMemcpy(dFix, fix, (size_t)R * cap, hipMemcpyHostToDevice));
-        TCHK(hipMemcpy(dDfix, dfix, sizeof(double) * R * cap, hipMemcpyHostToDevice));
+        HIPCHK(A.up(&dFix, fix, nc));
+        HIPCHK(A.up(&dDfix, dfix, nc));
     }
     launch_newton_solve(dH, dHoff, dMt, dM, dS1, s2, dG, dPg, R, cap, dOut, dSd, nullptr, maxm, nullptr, dFix, dDfix);
-    TCHK(hipGetLastError());
-    TCHK(hipDeviceSynchronize());
-    TCHK(hipMemcpy(d_out, dOut, sizeof(double) * R * cap, hipMemcpyDeviceToHost));
-#undef TCHK
-    freeall();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(A.down(d_out, dOut, nc));
     return GML_OK;
 }
 
@@ -431,24 +421,6 @@ extern "C" int gml_test_i8_hess_state(gml_problem *p, int64_t *dims, void **out)
 // carry from one iteration to the next goes in and out as arguments.  tests/test_gpu_solver_kernels.py, tests/test_gpu_newton_solve.py.
 // ------------------------------------------------------------------------------------------
 namespace {
-// device arrays of one hook call: freed when the call returns, whichever way
-struct DevArrays {
-    std::vector<void *> ptrs;
-    ~DevArrays() {
-        for (void *q : ptrs) (void)dev_free(q);
-    }
-    // n elements on the device, copied from h (NULL: zeroed)
-    template <typename T> hipError_t up(T **d, const T *h, size_t n) {
-        const size_t bytes = sizeof(T) * std::max<size_t>(n, 1);
-        const hipError_t e = dev_malloc(d, bytes);
-        if (e != hipSuccess) return e;
-        ptrs.push_back(*d);
-        return h && n ? hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice) : hipMemset(*d, 0, bytes);
-    }
-    template <typename T> static hipError_t down(T *h, const T *d, size_t n) {
-        return h && n ? hipMemcpy(h, d, sizeof(T) * n, hipMemcpyDeviceToHost) : hipSuccess;
-    }
-};
 bool rows_in_range(const int *rows, int nrows, int R) {
     for (int a = 0; a < nrows; ++a)
         if (rows[a] < 0 || rows[a] >= R) return false;
@@ -530,7 +502,7 @@ extern "C" int gml_test_solver_trial(int R, int64_t Qp, int nrows, const int *ro
 // caller's apply_above, launch_newton_solve over all R rows -- per-row s1, the rank-one term s2, (pairs != 0) the rows' secant pairs for
 // the blocks it corrects itself, (faces != 0) the orthant faces from F / X / kind with `share` and `rounds`, (fix != NULL) entries fixed
 // from the start -- and launch_scatter_dir on the listed rows.  blocks [R][cap][cap]: row r's leading m_r x m_r, packed to pitch 32 mt
-// as test_newton_solve does; on return the lower triangle the solve read (k_secant's correction included), mirrored.  The secant state
+// (pack_ragged_blocks); on return the lower triangle the solve read (k_secant's correction included), mirrored.  The secant state
 // (Fprev, xprev, gprev [R][cap], mprev, npairs [R], S, Y [2][R][cap]), dsol [R][cap], Sdiag [R] and D [R][Qp] are read from the caller and
 // written back.  A row that is not listed takes m = 0.
 extern "C" int gml_test_newton_direction(int R, int cap, int64_t Qp, int nrows, const int *rows, const int *m, const int *F, double *blocks,
@@ -540,25 +512,17 @@ extern "C" int gml_test_newton_direction(int R, int cap, int64_t Qp, int nrows, 
                                          int rounds, const unsigned char *fix, const double *dfix, double *dsol, double *Sdiag, double *D,
                                          int device) {
     if (R <= 0 || cap <= 0 || cap > 512 || Qp <= 0 || nrows < 0 || !rows_in_range(rows, nrows, R)) return fail(GML_EINVAL, "bad argument");
-    std::vector<long long> hoff((size_t)R + 1, 0);
-    std::vector<int> mt((size_t)R), listed((size_t)R, 0);
+    std::vector<int> listed((size_t)R, 0);
     for (int a = 0; a < nrows; ++a) listed[rows[a]] = 1;
-    int maxm = 1;
     for (int r = 0; r < R; ++r) {
         if (m[r] < 0 || m[r] > cap || (m[r] > 0 && !listed[r])) return fail(GML_EINVAL, "bad block size");
         for (int a = 0; a < m[r]; ++a)
             if (F[(size_t)r * cap + a] < 0 || F[(size_t)r * cap + a] >= Qp) return fail(GML_EINVAL, "working-set column out of range");
-        mt[r] = (m[r] + 31) / 32;
-        hoff[r + 1] = hoff[r] + (long long)mt[r] * 32 * mt[r] * 32;
-        maxm = std::max(maxm, m[r]);
     }
-    std::vector<double> H((size_t)std::max<long long>(hoff[R], 1), 0.0);
-    for (int r = 0; r < R; ++r) {
-        const int hp = 32 * mt[r];
-        for (int i = 0; i < m[r]; ++i)
-            for (int j = 0; j < m[r]; ++j) H[(size_t)hoff[r] + (size_t)i * hp + j] = blocks[((size_t)r * cap + i) * cap + j];
-        for (int i = m[r]; i < hp; ++i) H[(size_t)hoff[r] + (size_t)i * hp + i] = 1.0; // padding: identity
-    }
+    std::vector<long long> hoff;
+    std::vector<int> mt;
+    std::vector<double> H;
+    const int maxm = std::max(1, pack_ragged_blocks(R, m, cap, blocks, mt, hoff, H));
     HIPCHK(hipSetDevice(device));
     DevArrays A;
     const size_t nd = (size_t)R * Qp, nc = (size_t)R * cap;

@@ -1,4 +1,6 @@
-"""k_newton_solve on R blocks of m entries through the test hook (run under rocprofv3 --kernel-trace --stats for its time).
+"""The batched Newton solve (launch_newton_solve: k_newton_chol_lds up to 128 entries, k_newton_chol above) on R blocks of m entries
+through the test hook gml_test_newton_solve.  Prints the error against numpy; run it under rocprofv3 --kernel-trace --stats for the
+kernels' times.
 usage: gpu_newton_ubench.py R m [m2 ...]"""
 import ctypes as C, sys
 import numpy as np
@@ -20,5 +22,3 @@ for m in [int(v) for v in sys.argv[2:]]:
         _lib.check(L.gml_test_newton_solve(R, _lib._ptr(ms), cap, _lib._ptr(blocks), _lib._ptr(pg), 0.0, None, _lib._ptr(out), 0))
     want = np.linalg.solve(A, -pg[0, :m])
     print(m, "max rel err", np.abs(out[0, :m] - want).max() / np.abs(want).max())
-    if np.abs(out[0, 500:506]).max() > 0:  # a -DCHOL_TIMING build: phase times of row 0's workgroup, us
-        print("   phases us: load %.1f  diag %.1f  panel %.1f  trailing %.1f  back %.1f  out %.1f" % tuple(out[0, 500:506]))

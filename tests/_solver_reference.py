@@ -1,5 +1,5 @@
 """Host model of the solver's device kernels (csrc/gml_solver.hip) and of the direction phase around the batched solve
-(csrc/gml_kernels_f64.hip), written from the comments above the kernels and from the textbook definitions.  Numpy only; nothing of the
+(csrc/gml_newton_solve.hip), written from the comments above the kernels and from the textbook definitions.  Numpy only; nothing of the
 code under test is imported.  One row at a time: the tests loop over rows.
 
 Arithmetic: float64 where the kernel's result is one rounding (g +- lambda, x - xprev, lambda |x|); math.fsum / np.longdouble wherever
