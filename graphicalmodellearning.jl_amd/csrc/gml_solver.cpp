@@ -271,6 +271,15 @@ struct Solver {
     // sub-sampled Newton: Hessians over Kh configurations -- every kstride-th block of 512 (set_kh)
     int64_t Kh_base = 0, nblk512 = 0, Kh = 0, kstride = 1;
     double hscale = 1.0;
+    // the record of the outer iterations (gml_solver.h: TrajRecorder), NULL unless a test armed it before the solve began
+    TrajRecorder *rec = nullptr;
+    double *rec_row(int64_t r) { return rec->its.back().rows.data() + (size_t)r * TRR_N; }
+    int rec_select(int it, int64_t nactive);
+    int rec_download(void *host, const void *dev, size_t bytes) { // (armed only: waits for the stream)
+        HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return GML_OK;
+    }
 
     Solver(gml_problem *p_, int form, const gml_opts &o_, double lam)
         : p(p_), d(p_->d), formulation(form), o(o_), st(p_->st), R(p_->node1 - p_->node0), Rp(gml_round_up(R, 32)), Qp(p_->d.Qp), P(p_->P),
@@ -521,6 +530,46 @@ int Solver::init() {
     if (o.hess_samples != 0) Kh_base = o.hess_samples < 0 ? d.Kp : (int64_t)o.hess_samples;
     nblk512 = d.Kp / 512;
     set_kh(R);
+    if (g_traj.armed) { // (the record of an earlier solve goes)
+        rec = &g_traj;
+        rec->R = R;
+        rec->Qp = Qp;
+        rec->capP = capP;
+        rec->its.clear();
+        rec->from_best.clear();
+    }
+    return GML_OK;
+}
+
+// a new record: the header as far as it is known, and what select left per row (with the working sets, downloaded)
+int Solver::rec_select(int it, int64_t nactive) {
+    rec->its.emplace_back();
+    TrajIter &t = rec->its.back();
+    for (double &h : t.hdr) h = 0.0;
+    t.hdr[TRH_IT] = it;
+    t.hdr[TRH_NACTIVE] = (double)nactive;
+    t.hdr[TRH_SECANT] = t.hdr[TRH_FACE_ROUNDS] = -1.0;
+    t.hdr[TRH_STALL_CAP] = stall_cap;
+    t.hdr[TRH_PREC] = prec;
+    t.rows.assign((size_t)R * TRR_N, 0.0);
+    t.F.assign((size_t)R * capP, -1);
+    RCCHK(rec_download(t.F.data(), dFidx, sizeof(int) * (size_t)R * capP));
+    for (int64_t r = 0; r < R; ++r) {
+        double *q = rec_row(r);
+        q[TRR_DONE] = done[r];
+        q[TRR_ATFLOOR] = atfloor[r];
+        q[TRR_KKT] = kkt[r];
+        q[TRR_BEST] = best[r];
+        q[TRR_FOBJ] = Fobj[r];
+        q[TRR_STALL] = stall[r];
+        q[TRR_M] = sel[r].m;
+        q[TRR_NSUPP] = sel[r].nsupp;
+        q[TRR_NVIOL] = sel[r].nviol;
+        q[TRR_F] = f[r];
+        q[TRR_FN] = fn[r];
+        q[TRR_Z] = Z[r];
+        q[TRR_NPAIRS] = -1.0;
+    }
     return GML_OK;
 }
 
@@ -917,6 +966,11 @@ int Solver::direction_blocks(const std::vector<int> &cg_rows) {
         s1[r] = hscale * zi; // sub-sampled blocks
         s1cg[r] = zi;        // the Hessian-vector products use every configuration
     }
+    if (rec)
+        for (int64_t r = 0; r < R; ++r) {
+            rec_row(r)[TRR_S1] = s1[r];
+            rec_row(r)[TRR_YNOISE] = yn[r];
+        }
     // the tiles: kTile consecutive entries of W each, behind the rows' blocks
     constexpr int T = kTile;
     std::vector<long long> t0((size_t)R, 0);
@@ -1075,6 +1129,13 @@ int Solver::newton_blocks(const std::vector<int> &chol_rows) {
     // statistics: config 2 -- 1e5 x 256 -- is 0.4 ms faster without, the headline problem 4 % faster with)
     nf.rounds = (double)p->K * (double)Qp >= 268435456.0 ? face_rounds : 0;
     if (tune[GML_TUNE_FACE_ROUNDS] > 0) nf.rounds = (int)tune[GML_TUNE_FACE_ROUNDS] - 1;
+    if (rec) { // the pairs as k_secant left them (without a secant: as they were)
+        std::vector<int> npv((size_t)Rp);
+        RCCHK(rec_download(npv.data(), dNpairs, sizeof(int) * Rp));
+        for (int r : chol_rows) rec_row(r)[TRR_NPAIRS] = npv[r];
+        rec->its.back().hdr[TRH_SECANT] = secant;
+        rec->its.back().hdr[TRH_FACE_ROUNDS] = nf.rounds;
+    }
     // (blocks of up to kCholLds entries take the secant correction inside the solve, on the matrix in LDS; k_secant above kept the
     // pairs and corrected the larger blocks itself)
     SecantPairs sp;
@@ -1359,6 +1420,11 @@ int Solver::line_search() {
         std::vector<int> acc;
         for (int r : rows) {
             bool ok;
+            if (rec) {
+                rec_row(r)[TRR_TRIALS] += 1.0;
+                rec_row(r)[TRR_ALPHA] = alpha[r];
+                rec_row(r)[TRR_NREG] = nreg[r];
+            }
             if (nreg[r]) {
                 const double bk = trial[r].back;
                 ok = std::isfinite(ft[r]) && std::isfinite(bk) && bk >= -0.5 * std::fabs(dd[r]);
@@ -1377,6 +1443,10 @@ int Solver::line_search() {
                 acc.push_back(r);
                 if (!full) accepted_fwd[r] = 1; // (its V planes still belong to the old iterate)
                 need[r] = 0;
+                if (rec) {
+                    rec_row(r)[TRR_ACCEPTED] = 1.0;
+                    rec_row(r)[TRR_FULL] = full;
+                }
             } else {
                 if (!gml_is_i8(prec)) slots.mark_stale(r); // the FP64 path's V is indexed by row: every trial overwrites it
                 else if (full) slots.reject_trial(r);      // the planes just written belong to the rejected point
@@ -1384,6 +1454,7 @@ int Solver::line_search() {
                 if (nreg[r] && alpha[r] < 1.0 / 64) {
                     need[r] = 0;   // cannot improve along this direction: the stall counter ends the row,
                     stall[r] += 3; // after at most three such line searches (each costs ~7 passes)
+                    if (rec) rec_row(r)[TRR_GAVE_UP] = 1.0;
                 }
             }
         }
@@ -1403,6 +1474,12 @@ int Solver::line_search() {
         if (accepted_fwd[r]) rows.push_back((int)r);
     if (!rows.empty()) RCCHK(run_pass(rows, X, G, true, false, at_x));
     // rows whose line search failed entirely stay where they are; the stall counter ends them
+    if (rec) {
+        TrajIter &t = rec->its.back();
+        t.hdr[TRH_LINE_SEARCH] = 1.0;
+        t.X.assign((size_t)R * Qp, 0.0);
+        RCCHK(rec_download(t.X.data(), X, sizeof(double) * (size_t)R * Qp));
+    }
     return GML_OK;
 }
 
@@ -1417,6 +1494,10 @@ int Solver::finish(double *out, double *kkt_out, int iterations) {
         maxk = std::max(maxk, k);
         if (kkt_out) kkt_out[r] = k;
         (best[r] <= kkt[r] ? frombest : fromx).push_back((int)r);
+    }
+    if (rec) {
+        rec->from_best.assign((size_t)R, 0);
+        for (int r : frombest) rec->from_best[r] = 1;
     }
     // best iterate per row -> Xt (free now)
     RCCHK(upload_rows(frombest, dRows));
@@ -1560,6 +1641,7 @@ int Solver::iterate(double *out, double *kkt_out) {
                 RCCHK(select(it, &nactive));
             }
         }
+        if (rec) RCCHK(rec_select(it, nactive));
         if (nactive == 0) {
             bool polishing = false;
             RCCHK(start_polish(&polishing));
@@ -1567,6 +1649,12 @@ int Solver::iterate(double *out, double *kkt_out) {
             continue;
         }
         set_kh(nactive);
+        if (rec) {
+            double *h = rec->its.back().hdr;
+            h[TRH_KH] = (double)Kh;
+            h[TRH_KSTRIDE] = (double)kstride;
+            h[TRH_HSCALE] = hscale;
+        }
         trace("refresh");
         RCCHK(refresh_stale());
         trace("refreshed");

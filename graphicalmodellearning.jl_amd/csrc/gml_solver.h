@@ -3,6 +3,7 @@
 #include "gml_dev.h"
 
 #include <atomic>
+#include <vector>
 
 namespace gml {
 
@@ -22,6 +23,37 @@ extern std::atomic<long long> g_hv_sparse_calls; // products taken entry by entr
 // address the knobs by number, so an index never moves: 3 belonged to an experiment that was removed and stays reserved (unused)
 enum { GML_TUNE_KH_BASE = 0, GML_TUNE_FACE_ROUNDS = 1 /* value - 1 = rounds */, GML_TUNE_HESS_WGS = 2, GML_TUNE_NO_ZERO_SHORTCUT = 4 /* 1: the first pass runs its GEMM like any other */, GML_TUNE_NO_ZEROCOPY = 5 /* 1: results and row lists through device arrays and copies, as on handles too large for the pinned arena */, GML_TUNE_NO_COMPACT = 6 /* 1: the forward GEMMs of objective passes sweep all columns, always (A/B of the column compaction) */, GML_TUNE_BENCH_COMPACT = 7 /* 1: the timing hooks gml_bench_pass* compact too (they sweep all columns by default: the bench headline prices the dense contraction) */, GML_TUNE_SOLVER_COMPACT = 8 /* 1: gml_learn's own passes try the compaction whatever the column count.  By default they do from 4 096 statistics columns on (multi-body problems, thousands of spins: config 5 at c = 1.2 3.5 -> 2.2 s): measured (profiles/r6_compact_ab.txt) -- with the 1 024 columns of the headline problem a node's optimum keeps ~100 noise-level coefficients, a tile's 32 rows cover every column after the third pass: no gain, 1 - 5 % overhead */, GML_TUNE_NO_PAIRS = 9 /* 1: the forward sweep of precision i8w runs dense on plain digit planes in every tile, as it does where a column pair leaves the range of seven digits (gml_i8_pairs.h): the same result bits, so a test can hold the two paths against each other */, GML_TUNE_HESS_BLK_WGS = 10 /* workgroups the k-split of the blocked Hessian kernel aims at (0: 4096), as GML_TUNE_HESS_WGS for the one-workgroup kernel: tests reach long chunks at small shapes */, GML_NTUNE = 16 };
 extern double g_tune[GML_NTUNE];
+
+// (test hook, gml_testhooks.cpp: gml_test_traj_*) the record of a solve's outer iterations: what the host logic of gml_solver.cpp decided,
+// step by step, for tests/test_gpu_solver_trajectory.py.  Off by default; while it is armed a solve appends one TrajIter per outer iteration
+// (and waits for the stream and downloads to do so -- unarmed, the solver queues nothing more than it would without the recorder).  One
+// solve at a time: the record belongs to the last gml_learn of the process that began while it was armed.
+enum { // the header of an iteration
+    TRH_IT = 0, TRH_NACTIVE, TRH_KH, TRH_KSTRIDE, TRH_HSCALE, TRH_SECANT /* -1: no Cholesky row this iteration */, TRH_FACE_ROUNDS /* in force; -1 likewise */,
+    TRH_STALL_CAP, TRH_PREC, TRH_LINE_SEARCH /* 1: the iteration went on to directions and a line search */, TRH_N = 12 };
+enum { // per local row (doubles; the integers among them are exact)
+    // after select
+    TRR_DONE = 0, TRR_ATFLOOR, TRR_KKT, TRR_BEST, TRR_FOBJ, TRR_STALL, TRR_M /* sel.m */, TRR_NSUPP, TRR_NVIOL, TRR_F, TRR_FN, TRR_Z,
+    // before the solve (rows that are not done)
+    TRR_S1, TRR_YNOISE, TRR_NPAIRS /* after k_secant; -1: the row was in no Cholesky solve */,
+    // after the line search
+    TRR_TRIALS, TRR_ALPHA /* of the accepting trial; of the last one for a row that was not accepted */, TRR_NREG /* of that trial */,
+    TRR_FULL /* the accepting trial was a full pass (0: forward only, its gradient pass followed) */, TRR_ACCEPTED, TRR_GAVE_UP,
+    TRR_N = 24 };
+struct TrajIter {
+    double hdr[TRH_N];
+    std::vector<double> rows; // [R][TRR_N]
+    std::vector<int> F;       // [R][capP]: the working sets as k_select left them (F[0..m) of the Cholesky rows)
+    std::vector<double> X;    // [R][Qp]: the iterates after the line search (empty: no line search)
+};
+struct TrajRecorder {
+    bool armed = false;
+    int64_t R = 0, Qp = 0;
+    int capP = 0;
+    std::vector<TrajIter> its;
+    std::vector<uint8_t> from_best; // after finish, per row: 1 the result is the best iterate Xb, 0 the last iterate X
+};
+extern TrajRecorder g_traj;
 
 // the rows' lists of working-set columns (k_cg_tiles): row r's |W| = nw[r] columns, in column order, at FV + t0[r] * T
 struct WList {

@@ -48,6 +48,43 @@ extern "C" double gml_test_tune(int id, double value) {
     g_tune[id] = value;
     return old;
 }
+namespace gml {
+TrajRecorder g_traj; // the record of a solve's outer iterations (gml_solver.h), off by default
+}
+// Test hooks (not part of include/gml.h): the record of the outer iterations of the last solve that began while the recorder was armed
+// (gml_solver.h: TrajRecorder, TRH_*, TRR_*).  tests/test_gpu_solver_trajectory.py.  Arm between solves only; one solve at a time.
+// gml_test_traj_arm: arms (on != 0) or disarms the recorder and drops the record; returns the old state.
+extern "C" int gml_test_traj_arm(int on) {
+    const int old = g_traj.armed;
+    g_traj = TrajRecorder{};
+    g_traj.armed = on != 0;
+    return old;
+}
+// dims [8]: 0 iterations recorded, 1 R (local rows), 2 Qp, 3 capP, 4 TRH_N, 5 TRR_N, 6 finish was reached (from_best is there), 7 0
+extern "C" int gml_test_traj_dims(int64_t *dims) {
+    if (!dims) return fail(GML_EINVAL, "NULL argument");
+    const int64_t v[8] = {(int64_t)g_traj.its.size(), g_traj.R, g_traj.Qp, g_traj.capP, TRH_N, TRR_N, g_traj.from_best.empty() ? 0 : 1, 0};
+    std::memcpy(dims, v, sizeof v);
+    return GML_OK;
+}
+// record i: hdr [TRH_N], rows [R][TRR_N], F [R][capP], X [R][Qp] (a NULL output is skipped).  Returns in *has_x whether the iteration had a
+// line search (X is written only then).
+extern "C" int gml_test_traj_iter(int i, double *hdr, double *rows, int *F, double *X, int *has_x) {
+    if (i < 0 || (size_t)i >= g_traj.its.size()) return fail(GML_EINVAL, "no iteration %d in the record of %zu", i, g_traj.its.size());
+    const TrajIter &t = g_traj.its[(size_t)i];
+    if (hdr) std::memcpy(hdr, t.hdr, sizeof t.hdr);
+    if (rows) std::memcpy(rows, t.rows.data(), sizeof(double) * t.rows.size());
+    if (F) std::memcpy(F, t.F.data(), sizeof(int) * t.F.size());
+    if (X && !t.X.empty()) std::memcpy(X, t.X.data(), sizeof(double) * t.X.size());
+    if (has_x) *has_x = !t.X.empty();
+    return GML_OK;
+}
+// from_best [R]: 1 where finish took the row from the best iterate, 0 where from the last
+extern "C" int gml_test_traj_finish(unsigned char *from_best) {
+    if (!from_best || g_traj.from_best.empty()) return fail(GML_EINVAL, "the recorded solve did not reach its finish");
+    std::memcpy(from_best, g_traj.from_best.data(), g_traj.from_best.size());
+    return GML_OK;
+}
 // forces the chain tile of the term-list chain kernel (64, 128 or 256 chains; 0 = its rule); returns the old value, -1 for another T.
 // A forced tile whose state does not fit the kernel's LDS budget is not used.  Set between calls only
 extern "C" int gml_test_term_chains_tile(int T) {

@@ -68,9 +68,11 @@ typedef struct gml_opts {
     int32_t max_add;     /* new (violating) coordinates admitted per node per iteration (default 64; twice that while a node has
                             more than 16 max_working violators: a dense optimum) */
     int32_t verbose;     /* 0 silent, 1 per-iteration line on stderr                        */
-    int32_t hess_samples; /* Newton Hessians use the first hess_samples configurations (< 0 = all;
-                            0 = adaptive: 32768 x (local nodes / nodes still active), so the
-                            last few nodes get all of them); the gradient always uses all     */
+    int32_t hess_samples; /* Newton Hessians use hess_samples configurations, rounded up to nb blocks of 512 (at least 2): every
+                            kstride-th block of 512 of the histogram, kstride = blocks / nb rounded down (so the first nb blocks
+                            once nb exceeds half of them), rescaled by the weight of those blocks; all of them once nb x 512
+                            reaches the number of configurations (< 0 = all; 0 = adaptive: Kh_base x (local nodes / nodes still active), Kh_base = 32768 on
+                            the FP64 path, so the last few nodes get all of them); the gradient always uses all     */
     int32_t polish;      /* precision i8x only: 0 = rows that stall above tol at the noise floor of the int8-limb
                             arithmetic continue on the FP64 path when its workspaces fit (default); -1 = never */
     int32_t max_cg;      /* conjugate-gradient iterations per Newton step of the matrix-free rows (working sets above

@@ -275,7 +275,8 @@ def solve_faces(B, pg, x, kind, share, rounds, fix=None, dfix=None):
             break
         cand, fixed, mass, total, margin = face_candidates(x, d, pg, kind, ~fx)
         again = bool(cand.any()) and mass > share * total
-        log.append(dict(n=int(cand.sum()), mass=mass, total=total, margin=margin, again=again))
+        signs = np.where(x == 0, d * pg, (x + d) * x)[~fx & (kind == 2)]  # (the values whose signs pick the candidates)
+        log.append(dict(n=int(cand.sum()), mass=mass, total=total, margin=margin, again=again, signs=signs))
         if not again:
             break
         fx |= cand
