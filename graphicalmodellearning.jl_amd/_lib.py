@@ -92,6 +92,7 @@ def lib():
     L.gml_problem_create_mcmc_terms_tempered.argtypes = [p, i32, p, i64, i64, i64, i64, i32, i32, p, i32, i32, C.c_uint64, i32, i32, i64,
                                                          i64, i32, p, C.POINTER(p)]
     L.gml_log_partition_ais.argtypes = [p, i32, p, i64, i64, i64, p, i64, i32, C.c_uint64, i32, p, p, p, p]
+    L.gml_model_exact.argtypes = [p, i32, p, i64, i64, p, i32, i64, i32, C.POINTER(dbl), p, p, p]
     L.gml_problem_create_mcmc_terms_conditional.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, i32, i64, i64,
                                                             C.POINTER(p)]
     L.gml_conditional_means.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
@@ -364,6 +365,31 @@ def log_partition_ais(terms, n, chains, betas, sweeps_per_step=1, seed=0, device
     check(lib().gml_log_partition_ais(_ptr(keys), stride, _ptr(wts), len(wts), int(n), chains, _ptr(betas), len(betas),
                                       int(sweeps_per_step), int(seed), int(device), _ptr(logw), _ptr(energies), _ptr(spins), _ptr(result)))
     return result, logw, energies, spins
+
+
+def model_exact(terms, n, queries=None, pairs=True, device=0):
+    """gml_model_exact on a term list as term_arrays takes it: (log_z, m [n], C [n, n] or None without pairs, q [len(queries)] or
+    None without queries) -- exact log Z, means, pair correlations and the expectations of the query keys (what
+    Problem.term_moments takes for keys), by enumeration on the device; components of at most 40 spins."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    n = int(n)
+    qkeys = None
+    if queries is not None:
+        windows = list(moment_key_windows(queries)) or [np.zeros((0, 1), dtype=np.int32)]
+        width = max(w.shape[1] for w in windows)
+        qkeys = np.full((sum(len(w) for w in windows), width), -1, dtype=np.int32)
+        at = 0
+        for w in windows:
+            qkeys[at:at + len(w), :w.shape[1]] = w
+            at += len(w)
+    nq = 0 if qkeys is None else len(qkeys)
+    log_z = C.c_double()
+    m = np.zeros(max(n, 0))
+    corr = np.zeros((max(n, 0), max(n, 0))) if pairs else None
+    q = np.zeros(max(nq, 1)) if qkeys is not None else None
+    check(lib().gml_model_exact(_ptr(keys), stride, _ptr(wts), len(wts), n, _ptr(qkeys) if nq else None, qkeys.shape[1] if nq else 1, nq,
+                                int(device), C.byref(log_z), _ptr(m), _ptr(corr), _ptr(q) if nq else None))
+    return float(log_z.value), m, corr, (q[:nq] if q is not None else None)
 
 
 class Problem:

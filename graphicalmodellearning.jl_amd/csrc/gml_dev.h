@@ -262,6 +262,35 @@ void launch_masked_chains(const TermChainSpin *dspin, const unsigned *drec, cons
                           int64_t mwpr, int64_t K, int64_t n, int64_t chains, int burn_in, int thin, int spc, unsigned long long seed,
                           int8_t *dout, int64_t ld, double *dmeans, hipStream_t st);
 
+// Exact log Z and expectations of one connected component by streaming enumeration (gml_exact.hip).  The component's terms sorted by
+// their mask over the low chunk bits (w, hi = the mask over the high bits); the runs of equal low mask cut into items
+// [item_off[it], item_off[it + 1]) of at most 1024 terms: item_dst >= 0 is the padded slot (i + (i >> 4)) of the low mask whose only
+// item it is, item_dst < 0 the partial sum ~item_dst; the masks of several items add the partial sums [ms_off[s], ms_off[s + 1]) into
+// the padded slot ms_dst[s].  Queries (q_lo, q_hi), nq <= kExactWindow of them, query 0 the empty one (Z).  Group g of the grid takes
+// the chunks [g cpg, (g + 1) cpg); gm [G] and gacc [G][nq] receive its running maximum and sums, dres [nq + 1] the combined sums and,
+// last, their common maximum.
+constexpr int kExactChunkBits = 12;                      // low bits of a chunk: 4096 states per workgroup pass
+constexpr int kExactVec = 4096 + 256;                    // the padded vector
+constexpr int kExactParts = 512;                         // partial sums of one chunk's coefficient vector
+constexpr int kExactWindow = 1024;                       // queries accumulated in one enumeration, Z among them
+constexpr int kExactBlock = 1024;                        // chunks added serially into one accumulator
+constexpr int kExactGroups = 1024;                       // accumulation groups at most
+constexpr int kExactMaxSpins = 40;                       // spins of a component
+// g_exact_chunk_bits (gml_testhooks.cpp): 1 .. kExactChunkBits low bits instead of min(sb, kExactChunkBits); 0 = that default
+extern int g_exact_chunk_bits;
+struct ExactPlan {
+    const double *w;
+    const unsigned long long *hi;
+    const int *item_off, *item_dst, *ms_off, *ms_dst;
+    int ni, nm;
+    const int *q_lo;
+    const unsigned long long *q_hi;
+    int nq;
+    long long cpg;
+    double *gm, *gacc;
+};
+void launch_exact(const ExactPlan &P, int G, double *dres, hipStream_t st);
+
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].
 // faces: the orthant-face re-solves inside the kernel (working-set columns F [R][cap], iterates X [R][Qp] and their column kinds,

@@ -175,19 +175,13 @@ struct SamplerStaging {
     }
 };
 
-// ------------------------------------------------------------------------------------------
-// gml_problem_create_sampled: sample on the device, then build the handle from the device-resident
-// samples (the step before the path; src/sampling.jl:34-57, 94-106)
-// ------------------------------------------------------------------------------------------
-static int create_sampled_terms(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n,
-                                int64_t N, uint64_t seed, int order, int64_t node0, int64_t node1, int device,
-                                gml_problem **out, bool dedupe = false) {
-    if (int rc = check_out(out)) return rc;
-    if (int rc = check_term_pointers(keys, stride, weights, nterms)) return rc;
-    if (n <= 0 || N <= 0) return fail(GML_EINVAL, "n and N must be positive");
-    if (int rc = gml_check_handle_args(n, order, node0, node1)) return rc;
-    if (int rc = check_term_values(keys, stride, weights, nterms, n)) return rc;
-    // connected components of the term hypergraph
+// Connected components of the term hypergraph (the exact sampler, gml_model_exact): blocks[b] = the spins of component b in
+// ascending order, the components in the order of their smallest spin; id[i] = the component of spin i.
+struct TermComponents {
+    std::vector<std::vector<int>> blocks;
+    std::vector<int64_t> id;
+};
+static TermComponents term_components(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n) {
     std::vector<int64_t> parent((size_t)n);
     for (int64_t i = 0; i < n; ++i) parent[i] = i;
     std::function<int64_t(int64_t)> find = [&](int64_t a) {
@@ -201,16 +195,36 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
         reduce_key(keys + t * stride, stride, sp);
         for (size_t a = 1; a < sp.size(); ++a) parent[find(sp[a])] = find(sp[0]);
     }
-    std::vector<std::vector<int>> blocks;
-    std::vector<int64_t> id((size_t)n, -1);
+    TermComponents tc;
+    std::vector<int64_t> of_root((size_t)n, -1);
+    tc.id.assign((size_t)n, -1);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t r = find(i);
-        if (id[r] < 0) {
-            id[r] = (int64_t)blocks.size();
-            blocks.emplace_back();
+        if (of_root[r] < 0) {
+            of_root[r] = (int64_t)tc.blocks.size();
+            tc.blocks.emplace_back();
         }
-        blocks[(size_t)id[r]].push_back((int)i);
+        tc.id[(size_t)i] = of_root[r];
+        tc.blocks[(size_t)of_root[r]].push_back((int)i);
     }
+    return tc;
+}
+
+// ------------------------------------------------------------------------------------------
+// gml_problem_create_sampled: sample on the device, then build the handle from the device-resident
+// samples (the step before the path; src/sampling.jl:34-57, 94-106)
+// ------------------------------------------------------------------------------------------
+static int create_sampled_terms(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n,
+                                int64_t N, uint64_t seed, int order, int64_t node0, int64_t node1, int device,
+                                gml_problem **out, bool dedupe = false) {
+    if (int rc = check_out(out)) return rc;
+    if (int rc = check_term_pointers(keys, stride, weights, nterms)) return rc;
+    if (n <= 0 || N <= 0) return fail(GML_EINVAL, "n and N must be positive");
+    if (int rc = gml_check_handle_args(n, order, node0, node1)) return rc;
+    if (int rc = check_term_values(keys, stride, weights, nterms, n)) return rc;
+    const TermComponents tc = term_components(keys, stride, weights, nterms, n);
+    const std::vector<std::vector<int>> &blocks = tc.blocks;
+    std::vector<int> sp;
     size_t maxsb = 0;
     for (auto &b : blocks) maxsb = std::max(maxsb, b.size());
     if (maxsb > 22)
@@ -229,7 +243,7 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
         if (sp.empty()) continue; // the empty term, or one whose spins all cancel: a constant energy
         unsigned mask = 0;
         for (int v : sp) mask |= 1u << local[(size_t)v];
-        const size_t b = (size_t)id[find(sp[0])];
+        const size_t b = (size_t)tc.id[(size_t)sp[0]];
         bmask[b].push_back(mask);
         bwt[b].push_back(weights[t]);
         maxnt = std::max(maxnt, bmask[b].size());
@@ -919,4 +933,244 @@ extern "C" int gml_problem_get_spins(gml_problem *p, int8_t *spins) {
     }
     (void)dev_free(dT);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// gml_model_exact: exact log Z and exact expectations, component by component (gml_exact.hip)
+// ------------------------------------------------------------------------------------------
+// sum of v with at most 1024 terms added serially into one accumulator: halves above that
+static double pairwise_sum(const double *v, size_t count) {
+    if (count <= 1024) {
+        double s = 0.0;
+        for (size_t i = 0; i < count; ++i) s += v[i];
+        return s;
+    }
+    const size_t half = count / 2;
+    return pairwise_sum(v, half) + pairwise_sum(v + half, count - half);
+}
+
+// One component as the kernel takes it (gml_dev.h: ExactPlan): c low bits, the terms sorted by low mask (stable: the order of the
+// caller's list within a mask), items, partial sums.  mask: the terms over the component's own spins.
+struct ExactComponent {
+    int sb = 0, c = 0;
+    std::vector<double> w;
+    std::vector<unsigned long long> hi;
+    std::vector<int> item_off, item_dst, ms_off, ms_dst;
+    std::vector<unsigned long long> queries; // masks over the component's spins whose expectations are wanted
+    std::vector<double> expect;              // their expectations
+    double log_z = 0.0;
+};
+static int plan_exact_component(const std::vector<unsigned long long> &mask, const std::vector<double> &wt, ExactComponent &pc) {
+    const size_t T = mask.size();
+    if (T > ((size_t)1 << 20))
+        return fail(GML_EUNSUPPORTED, "a connected component of the model has %zu terms: exact enumeration takes at most 2^20", T);
+    pc.c = std::min(pc.sb, g_exact_chunk_bits > 0 ? g_exact_chunk_bits : kExactChunkBits);
+    pc.c = std::max(pc.c, pc.sb - 30); // (a hooked c: at most 2^20 chunks per group, kExactBlock blocks of kExactBlock chunks)
+    const unsigned long long low = ((unsigned long long)1 << pc.c) - 1;
+    std::vector<int> idx(T);
+    for (size_t t = 0; t < T; ++t) idx[t] = (int)t;
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return (mask[(size_t)a] & low) < (mask[(size_t)b] & low); });
+    std::vector<int> lo(T);
+    pc.w.resize(T);
+    pc.hi.resize(T);
+    for (size_t t = 0; t < T; ++t) {
+        lo[t] = (int)(mask[(size_t)idx[t]] & low);
+        pc.hi[t] = mask[(size_t)idx[t]] >> pc.c;
+        pc.w[t] = wt[(size_t)idx[t]];
+    }
+    // items of at most L terms; L doubles until the partial sums of the masks with several items fit the kernel's kExactParts
+    for (int L = 16;; L *= 2) {
+        pc.item_off.assign(1, 0);
+        pc.item_dst.clear();
+        pc.ms_off.assign(1, 0);
+        pc.ms_dst.clear();
+        int parts = 0;
+        for (size_t a = 0; a < T;) {
+            size_t b = a;
+            while (b < T && lo[b] == lo[a]) ++b;
+            const int slot = lo[a] + (lo[a] >> 4), nseg = (int)((b - a + (size_t)L - 1) / (size_t)L);
+            for (int s = 0; s < nseg; ++s) {
+                pc.item_off.push_back((int)std::min(b, a + (size_t)(s + 1) * (size_t)L));
+                pc.item_dst.push_back(nseg == 1 ? slot : ~(parts + s));
+            }
+            if (nseg > 1) {
+                parts += nseg;
+                pc.ms_off.push_back(parts);
+                pc.ms_dst.push_back(slot);
+            }
+            a = b;
+        }
+        if (parts <= kExactParts) break;
+        if (L >= 1024) return fail(GML_EUNSUPPORTED, "a connected component of the model has too many terms for exact enumeration");
+    }
+    return GML_OK;
+}
+
+// the enumerations of one planned component: its queries in windows of kExactWindow - 1 beside the empty query (Z)
+static int run_exact_component(ExactComponent &pc, int device) {
+    SamplerStaging s;
+    if (int rc = s.open(device)) return rc;
+    ExactPlan P{};
+    P.ni = (int)pc.item_dst.size();
+    P.nm = (int)pc.ms_dst.size();
+    if (pc.ms_dst.empty()) pc.ms_dst.push_back(0); // (no empty upload; the vectors outlive the stream's copies)
+    P.w = s.upload(pc.w);
+    P.hi = s.upload(pc.hi);
+    P.item_off = s.upload(pc.item_off);
+    P.item_dst = s.upload(pc.item_dst);
+    P.ms_off = s.upload(pc.ms_off);
+    P.ms_dst = s.upload(pc.ms_dst);
+    const long long nchunks = (long long)1 << (pc.sb - pc.c);
+    const int G = (int)std::min<long long>(nchunks, kExactGroups);
+    P.cpg = nchunks / G;
+    P.gm = s.alloc<double>((size_t)G);
+    P.gacc = s.alloc<double>((size_t)G * kExactWindow);
+    int *dqlo = s.alloc<int>(kExactWindow);
+    unsigned long long *dqhi = s.alloc<unsigned long long>(kExactWindow);
+    double *dres = s.alloc<double>(kExactWindow + 1);
+    if (s.rc) return s.rc;
+    P.q_lo = dqlo;
+    P.q_hi = dqhi;
+    const unsigned long long low = ((unsigned long long)1 << pc.c) - 1;
+    const size_t nq = pc.queries.size(), step = kExactWindow - 1;
+    pc.expect.assign(nq, 0.0);
+    std::vector<double> res((size_t)kExactWindow + 1);
+    for (size_t q0 = 0; q0 == 0 || q0 < nq; q0 += step) {
+        const size_t cnt = std::min(step, nq - q0);
+        std::vector<int> qlo(1, 0);
+        std::vector<unsigned long long> qhi(1, 0);
+        for (size_t q = q0; q < q0 + cnt; ++q) {
+            qlo.push_back((int)(pc.queries[q] & low));
+            qhi.push_back(pc.queries[q] >> pc.c);
+        }
+        P.nq = (int)cnt + 1;
+        s.copy(dqlo, qlo);
+        s.copy(dqhi, qhi);
+        if (s.rc) return s.rc;
+        launch_exact(P, G, dres, s.st);
+        s.ok(hipGetLastError(), "the enumeration's launch");
+        s.ok(hipMemcpyAsync(res.data(), dres, sizeof(double) * (size_t)(P.nq + 1), hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+        if (s.sync()) return s.rc;
+        // Z = 2^(c - 12) res[0] exp(M): the bits above c are in no term and doubled every sum (an exact scaling)
+        const double Zs = res[0], M = res[(size_t)P.nq];
+        pc.log_z = M + std::log(std::ldexp(Zs, pc.c - kExactChunkBits));
+        for (size_t q = 0; q < cnt; ++q) pc.expect[q0 + q] = res[q + 1] / Zs;
+    }
+    return GML_OK;
+}
+
+extern "C" int gml_model_exact(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, const int32_t *qkeys,
+                               int qkey_stride, int64_t nq, int device, double *log_z, double *mean, double *corr, double *qexp) {
+    if (!log_z) return fail(GML_EINVAL, "log_z is NULL");
+    if (int rc = check_term_pointers(keys, key_stride, weights, nterms)) return rc;
+    if (n <= 0 || nterms < 0) return fail(GML_EINVAL, "n must be positive and nterms non-negative");
+    if (nq < 0 || (nq > 0 && (!qkeys || !qexp || qkey_stride < 1))) return fail(GML_EINVAL, "NULL or malformed query list");
+    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
+    for (int64_t q = 0; q < nq; ++q)
+        for (int a = 0; a < qkey_stride; ++a) {
+            const int32_t v = qkeys[q * qkey_stride + a];
+            if (v < -1 || v >= n) return fail(GML_EINVAL, "query %lld names spin %d outside [0,%lld)", (long long)q, v, (long long)n);
+        }
+    const TermComponents tc = term_components(keys, key_stride, weights, nterms, n);
+    const size_t nb = tc.blocks.size();
+    for (auto &b : tc.blocks)
+        if (b.size() > (size_t)kExactMaxSpins)
+            return fail(GML_EUNSUPPORTED, "a connected component of the model has %zu spins: exact enumeration is limited to %d", b.size(),
+                        kExactMaxSpins);
+    std::vector<int> local((size_t)n, 0);
+    for (auto &b : tc.blocks)
+        for (size_t i = 0; i < b.size(); ++i) local[(size_t)b[i]] = (int)i;
+    // per component: its terms as masks over its own spins; the empty key is a constant of log Z
+    std::vector<std::vector<unsigned long long>> bmask(nb);
+    std::vector<std::vector<double>> bwt(nb);
+    std::vector<double> parts; // the summands of log Z
+    std::vector<int> sp;
+    for (int64_t t = 0; t < nterms; ++t) {
+        if (weights[t] == 0.0) continue;
+        reduce_key(keys + t * key_stride, key_stride, sp);
+        if (sp.empty()) {
+            parts.push_back(weights[t]);
+            continue;
+        }
+        unsigned long long mask = 0;
+        for (int v : sp) mask |= (unsigned long long)1 << local[(size_t)v];
+        const size_t b = (size_t)tc.id[(size_t)sp[0]];
+        bmask[b].push_back(mask);
+        bwt[b].push_back(weights[t]);
+    }
+    // a spin in no term needs no enumeration: ln 2, mean 0; the others are planned before the device is looked for
+    const bool moments = mean || corr;
+    std::vector<ExactComponent> comp(nb);
+    int64_t nfree = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        ExactComponent &pc = comp[b];
+        if (bmask[b].empty()) {
+            ++nfree;
+            continue;
+        }
+        pc.sb = (int)tc.blocks[b].size();
+        if (int rc = plan_exact_component(bmask[b], bwt[b], pc)) return rc;
+        if (moments)
+            for (int i = 0; i < pc.sb; ++i) pc.queries.push_back((unsigned long long)1 << i);
+        if (corr)
+            for (int i = 0; i < pc.sb; ++i)
+                for (int j = i + 1; j < pc.sb; ++j) pc.queries.push_back(((unsigned long long)1 << i) | ((unsigned long long)1 << j));
+    }
+    // a query is the product over the components of the expectations of its restrictions: (component, index of the restriction)
+    std::vector<int64_t> uq_off((size_t)nq + 1, 0);
+    std::vector<std::pair<int64_t, int64_t>> uq;
+    std::vector<uint8_t> uq_zero((size_t)nq, 0);
+    std::vector<std::pair<int64_t, unsigned long long>> restr;
+    for (int64_t q = 0; q < nq; ++q) {
+        reduce_key(qkeys + q * qkey_stride, qkey_stride, sp);
+        restr.clear();
+        for (int v : sp) {
+            const int64_t b = tc.id[(size_t)v];
+            if (bmask[(size_t)b].empty()) uq_zero[(size_t)q] = 1; // a free spin: expectation 0
+            auto it = std::find_if(restr.begin(), restr.end(), [&](auto &r) { return r.first == b; });
+            if (it == restr.end()) it = restr.insert(restr.end(), {b, 0ull});
+            it->second |= (unsigned long long)1 << local[(size_t)v];
+        }
+        std::sort(restr.begin(), restr.end());
+        if (!uq_zero[(size_t)q])
+            for (auto &r : restr) {
+                uq.emplace_back(r.first, (int64_t)comp[(size_t)r.first].queries.size());
+                comp[(size_t)r.first].queries.push_back(r.second);
+            }
+        uq_off[(size_t)q + 1] = (int64_t)uq.size();
+    }
+    if (int rc = gml_check_device(device)) return rc;
+    for (size_t b = 0; b < nb; ++b) {
+        if (bmask[b].empty()) continue;
+        if (int rc = run_exact_component(comp[b], device)) return rc;
+        parts.push_back(comp[b].log_z);
+    }
+    parts.push_back((double)nfree * std::log(2.0));
+    *log_z = pairwise_sum(parts.data(), parts.size());
+    if (moments) {
+        std::vector<double> m((size_t)n, 0.0);
+        for (size_t b = 0; b < nb; ++b)
+            if (!bmask[b].empty())
+                for (size_t i = 0; i < tc.blocks[b].size(); ++i) m[(size_t)tc.blocks[b][i]] = comp[b].expect[i];
+        if (mean) std::copy(m.begin(), m.end(), mean);
+        if (corr) {
+            for (int64_t i = 0; i < n; ++i)
+                for (int64_t j = 0; j < n; ++j) corr[i * n + j] = i == j ? 1.0 : m[(size_t)i] * m[(size_t)j];
+            for (size_t b = 0; b < nb; ++b) {
+                if (bmask[b].empty()) continue;
+                const std::vector<int> &mem = tc.blocks[b];
+                size_t at = mem.size(); // (the pairs follow the means, i < j in order)
+                for (size_t i = 0; i < mem.size(); ++i)
+                    for (size_t j = i + 1; j < mem.size(); ++j, ++at)
+                        corr[(int64_t)mem[i] * n + mem[j]] = corr[(int64_t)mem[j] * n + mem[i]] = comp[b].expect[at];
+            }
+        }
+    }
+    for (int64_t q = 0; q < nq; ++q) {
+        double e = uq_zero[(size_t)q] ? 0.0 : 1.0;
+        for (int64_t a = uq_off[(size_t)q]; a < uq_off[(size_t)q + 1] && !uq_zero[(size_t)q]; ++a)
+            e *= comp[(size_t)uq[(size_t)a].first].expect[(size_t)uq[(size_t)a].second];
+        qexp[q] = e;
+    }
+    return GML_OK;
 }

@@ -24,7 +24,8 @@ double g_hv_sparse_ratio = 0.3; // (config 5 at the default regulariser: 25.6 s 
 std::atomic<long long> g_hv_sparse_calls{0}; // (every part of a gml_multi_learn counts from its own host thread)
 int g_term_chains_tile = 0;                   // 0: the rule of term_chains_tile (gml_term_chains.hip)
 int g_cond_split = 1;                         // the conditional chains' constant part: 0 never, 1 by the host's rule, 2 always
-double g_tune[GML_NTUNE] = {};             // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
+int g_exact_chunk_bits = 0;                   // the exact enumeration's chunk bits: 0 = min(component size, kExactChunkBits)
+double g_tune[GML_NTUNE] = {};            // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
 // the kernel instances the int8-limb launchers have run (gml_i8.h: kI8InstBits)
 static std::atomic<uint64_t> g_i8_inst[(kI8InstBits + 63) / 64];
 void i8_note_instance(int bit) { g_i8_inst[bit >> 6].fetch_or(1ull << (bit & 63), std::memory_order_relaxed); }
@@ -100,6 +101,14 @@ extern "C" int gml_test_cond_split(int on) {
     if (on < 0 || on > 2) return -1;
     const int old = g_cond_split;
     g_cond_split = on;
+    return old;
+}
+// the low "chunk" bits of the exact enumeration (gml_exact.hip): c = 1 .. 12 instead of min(component size, 12), 0 restores that
+// default; small values take tiny models through the multi-chunk and multi-group paths.  Returns the old value, -1 for another value
+extern "C" int gml_test_exact_chunk_bits(int c) {
+    if (c < 0 || c > kExactChunkBits) return -1;
+    const int old = g_exact_chunk_bits;
+    g_exact_chunk_bits = c;
     return old;
 }
 extern "C" double gml_test_hv_sparse_ratio(double ratio) {

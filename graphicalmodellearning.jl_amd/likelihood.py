@@ -3,7 +3,9 @@
 (1/M) sum_k c_k log P(s_k) = sum_t w_t <prod_{i in t} s_i>_data - log Z.  The first part is exact (Problem.term_moments: integer
 sums on the device); log Z is estimated by annealed importance sampling on the device (gml_log_partition_ais: the term-list chains
 walked from beta = 0 to beta = 1 with a running weight).  AIS is unbiased for Z, hence biased low for log Z: the likelihood is an
-optimistic one, and the standard error does not see a well that no chain found (include/gml.h)."""
+optimistic one, and the standard error does not see a well that no chain found (include/gml.h).  Where every connected component of
+the model has at most 40 spins, Exact() gives log Z itself (gml_model_exact: enumeration on the device), and exact_moments the
+model's own means, correlations and term expectations: the model-side twin of moments(samples)."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -32,11 +34,21 @@ class AIS:
         self.steps = len(self.betas) - 1
 
 
+class Exact:
+    """Exact enumeration on the device (gml_model_exact): every connected component of the model's term hypergraph has at most
+    `max_spins` spins, itself at most 40 (the library's limit; a component of sb spins costs one pass over its 2^sb states)."""
+
+    def __init__(self, max_spins=40):
+        self.max_spins = int(max_spins)
+        if not 1 <= self.max_spins <= 40:
+            raise ValueError(f"max_spins must lie in [1, 40] (given {max_spins})")
+
+
 @dataclass
 class LogPartition:
     """log_z: the estimate; stderr: its delta-method standard error; ess: the effective sample size of the chains' weights (near 1:
     the schedule is too short); log_weights [chains].  energies [chains] and spins [chains, n] (the chains' final states and their
-    energies) with return_states, else None."""
+    energies) with return_states, else None.  From Exact(): log_z is exact, stderr 0.0, ess NaN, log_weights empty."""
     log_z: float
     stderr: float
     ess: float
@@ -62,13 +74,43 @@ def _model_terms(model):
     return args["terms"], args.get("n")
 
 
+def _largest_component(terms, n):
+    """the size of the largest connected component of the term hypergraph, by the library's rules (a spin named twice cancels, a
+    zero weight joins nothing)"""
+    keys, wts, _, n = _lib.term_arrays(terms, n)
+    parent = list(range(int(n)))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for key, w in zip(keys.tolist(), wts.tolist()):
+        sp = [v for v in set(key) if v >= 0 and key.count(v) % 2 == 1]
+        if w != 0.0:
+            for v in sp[1:]:
+                parent[find(v)] = find(sp[0])
+    return int(np.bincount([find(i) for i in range(int(n))]).max())
+
+
+def _check_exact(method, terms, n):
+    if method.max_spins < 40 and _largest_component(terms, n) > method.max_spins:
+        raise ValueError(f"a connected component of the model has more than max_spins = {method.max_spins} spins")
+
+
 def log_partition(model, method=None, *, seed=0, device=0, return_states=False):
     """log Z of `model` (a FactorGraph, a {1-based key tuple: weight} dict or a matrix with the fields on its diagonal) by annealed
-    importance sampling on the device; method: an AIS (default AIS()).  Returns a LogPartition."""
+    importance sampling on the device; method: an AIS (default AIS()), or an Exact for the exact value by enumeration (seed and
+    return_states play no part then).  Returns a LogPartition."""
     method = AIS() if method is None else method
-    if not isinstance(method, AIS):
+    if not isinstance(method, (AIS, Exact)):
         raise ValueError(f"log_partition takes an AIS method, given {type(method).__name__}")
     terms, n = _model_terms(model)
+    if isinstance(method, Exact):
+        _check_exact(method, terms, n)
+        log_z = _lib.model_exact(terms, n, pairs=False, device=device)[0]
+        return LogPartition(log_z, 0.0, float("nan"), np.zeros(0))
     result, logw, energies, spins = _lib.log_partition_ais(terms, n, method.chains, method.betas, method.sweeps_per_step, seed=seed,
                                                            device=device, return_states=return_states)
     return LogPartition(float(result[0]), float(result[1]), float(result[2]), logw, energies, spins)
@@ -91,3 +133,16 @@ def log_likelihood(data, model, method=None, *, log_z=None, seed=0, device=0):
     lz, se = (log_z.log_z, log_z.stderr) if isinstance(log_z, LogPartition) else (float(log_z), float("nan"))
     mean = data_term - lz
     return LogLikelihood(mean, M * mean, data_term, lz, se)
+
+
+def exact_moments(model, terms=None, pairs=True, device=0, method=None):
+    """The model's own moments by enumeration on the device (gml_model_exact; components of at most 40 spins): (m [n], C [n, n]) --
+    the magnetisations <s_i> and pair correlations <s_i s_j> under `model`, shaped as Problem.moments returns them (pairs=False: C is
+    None).  With terms= (what Problem.term_moments takes for keys): the expectation of every listed term, in the caller's order.  The
+    model-side twin of moments(samples).  method: an Exact whose max_spins refuses larger components."""
+    mterms, n = _model_terms(model)
+    _check_exact(Exact() if method is None else method, mterms, n)
+    if terms is not None:
+        return _lib.model_exact(mterms, n, queries=terms, pairs=False, device=device)[3]
+    _, m, corr, _ = _lib.model_exact(mterms, n, pairs=pairs, device=device)
+    return m, corr

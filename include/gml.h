@@ -367,6 +367,35 @@ int gml_log_partition_ais(const int32_t *keys, int key_stride, const double *wei
                           int8_t *spins /* [chains][n] row-major, +-1, or NULL */, double *result /* [3] or NULL */);
 
 /*
+ * gml_model_exact -- exact log Z and exact model-side expectations of ANY term list whose connected components have at most 40
+ * spins, by streaming enumeration on the device (no table of 2^n energies).  The yardstick for the estimate above, for the chain
+ * samplers and for learned models.  No handle is made; all pointers are host pointers.
+ * Model.  The term list as for gml_problem_create_sampled_terms: 0-based spins, -1 = unused slot, a spin named twice cancels, a term
+ * of weight zero joins nothing.  P(s) = exp(sum_t w_t prod_{i in t} s_i) / Z.  A term that reduces to the empty key adds its weight to
+ * log Z; a spin in no term (of non-zero weight) contributes ln 2 and has mean 0.
+ * Components.  The work is done per connected component of the term hypergraph; log Z is the sum over the components.
+ * Outputs.  *log_z.  mean [n] (or NULL): <s_i>.  corr [n][n] row-major (or NULL): <s_i s_j>, 1.0 on the diagonal, the product of
+ * the two means for spins of different components.  qexp [nq] (or NULL when nq = 0): <prod_{i in q} s_i> of every query key in
+ * qkeys [nq][qkey_stride] (the conventions of the term keys), the product over the components of the expectations of the key's
+ * restrictions; an empty or fully cancelled query gives 1.0.
+ * Arithmetic.  FP64 throughout.  Every sum has a fixed order that depends on the model alone -- the terms of one low mask in the
+ * caller's order, the chunks of an accumulation group in index order, the groups in index order; no accumulator takes more than 1024
+ * summands serially -- so two calls with the same arguments return the same bits, on any grid.  The weights enter through running
+ * maxima: couplings of +-150 neither overflow nor underflow.  A-priori error of log Z and of every expectation: about
+ * (12 + log2 T) 2^-53 sum_t |w_t| from the energies plus 1e-13 from the sums.
+ * GML_EINVAL, before any HIP call: log_z NULL; NULL keys or weights with nterms > 0; key_stride < 1; nterms < 0; n < 1; a spin outside
+ * [0, n) in a term or a query; a non-finite weight; nq < 0; nq > 0 with NULL qkeys or qexp or qkey_stride < 1.  GML_EUNSUPPORTED,
+ * before any HIP call: a component of more than 40 spins, or of more than 2^20 terms of non-zero weight.  The device is looked for
+ * last.
+ * Cost.  One enumeration of 2^sb states per component of sb spins and per window of 1023 expectations (the means and, with corr, the
+ * pairs of the component, then the restrictions of the queries): measured times in DESIGN 3.18.  Device memory (the component's
+ * terms, 8 MB of group sums) is released before the call returns.
+ */
+int gml_model_exact(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, const int32_t *qkeys,
+                    int qkey_stride, int64_t nq, int device, double *log_z, double *mean /* [n] or NULL */,
+                    double *corr /* [n][n] or NULL */, double *qexp /* [nq] or NULL */);
+
+/*
  * gml_problem_create_mcmc_terms_conditional, gml_conditional_means -- conditional inference: Glauber chains of ANY term list that
  * start from the rows of a resident handle and hold the observed spins fixed.  "Given these spins, what are the others?"
  * Inputs: a term list (keys, key_stride, weights, nterms, n) as for gml_problem_create_mcmc_terms_chains; a resident handle `evidence`
