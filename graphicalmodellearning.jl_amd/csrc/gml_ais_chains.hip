@@ -11,7 +11,6 @@
 // counter only and comes through the scalar path.  Waves share nothing; no barrier.  Every output is written once, at the end.
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_chain.h"
 #include "gml_term_field.h"
 
 namespace gml {
@@ -53,33 +52,21 @@ __global__ __launch_bounds__(256) void k_ais_chains(const TermChainSpin *__restr
                 const TermChainSpin &s = spin[i];
                 const double h = s.a + s.sig * term_field(s, rec, my, T);
                 const unsigned neg = chain_heat_bath(z0, (unsigned long long)i, beta * h);
-                unsigned *wp = my + (i >> 5) * T;
-                const unsigned word = *wp, old = (word >> (i & 31)) & 1u;
-                *wp = (word & ~(1u << (i & 31))) | (neg << (i & 31));
-                E -= (double)(2 * ((int)old - (int)neg)) * h; // s_new - s_old = 2 (old - neg)
+                E = chain_energy_step(E, chain_set_spin(my, T, i, neg), neg, h);
             }
         }
     }
     if (c >= chains) return;
     logw_out[c] = logw;
     if (E_out) E_out[c] = E;
-    if (states) {
-        int8_t *o = states + c * n;
-        for (int b = 0; b < nw; ++b) {
-            const unsigned word = my[b * T];
-            for (int i = 0; i < 32 && 32 * b + i < n; ++i) o[32 * b + i] = (word >> i) & 1u ? (int8_t)-1 : (int8_t)1;
-        }
-    }
+    if (states) chain_unpack(n, nw, my, T, states + c * n, 1); // row-major
 }
 
 void launch_ais_chains(const TermChainSpin *dspin, const TermChainSpin *dspin0, const unsigned *drec, int64_t n, int64_t chains,
                        const double *dbetas, int64_t nbetas, int sps, unsigned long long seed, double *dlogw, double *dE,
                        int8_t *dstates, hipStream_t st) {
-    const int T = term_chains_tile(n, chains);
-    const int shmem = (int)((n + 31) / 32) * T * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ais_chains), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    hipLaunchKernelGGL(k_ais_chains, dim3((unsigned)((chains + T - 1) / T)), dim3(T), shmem, st, dspin, dspin0, drec, (int)n, chains,
-                       dbetas, (int)(nbetas - 1), sps, seed, dlogw, dE, dstates);
+    launch_on_chain_tile(k_ais_chains, term_chains_tile(n, chains), (n + 31) / 32, chains, st, dspin, dspin0, drec, (int)n, chains, dbetas,
+                         (int)(nbetas - 1), sps, seed, dlogw, dE, dstates);
 }
 
 } // namespace gml

@@ -1,6 +1,7 @@
 // The Glauber chain of the samplers (include/gml.h: gml_problem_create_mcmc_terms, _mcmc_chains, _mcmc_terms_chains): its start state,
-// its random stream and its heat-bath update, once.  k_glauber, k_mcmc_chains and k_term_chains differ in how they compute the local
-// field h_i and in how they hold the state; everything else that defines the chain is here, so "the same chain" is one text.
+// its random stream, its heat-bath update and its recorded sweeps, once.  k_glauber, k_mcmc_chains and the term-list kernels differ in
+// how they compute the local field h_i and in how they hold the state; everything else that defines the chain is here, so "the same
+// chain" is one text.  What only the term-list kernels share is gml_term_field.h.
 // Internal, device side.  Chain c of n spins, spin s, sweep sw (0-based, burn-in included); a state bit set <=> the spin is -1.
 #pragma once
 #include "gml_rng.h"
@@ -28,18 +29,32 @@ __device__ __forceinline__ unsigned long long chain_z0(unsigned long long seed, 
     return seed + kU01Step * ((unsigned long long)(c * n) + 1ull) + kU01Stream * (unsigned long long)(sw + 1);
 }
 
-// heat bath of spin s: +1 iff u < 1 / (1 + exp(-2 h)), u the hash of the spin's counter word z0 + kU01Step s and h its local field.
-// Returns the state bit.
-__device__ __forceinline__ unsigned chain_heat_bath(unsigned long long z0, unsigned long long s, double field) {
-    const double pup = 1.0 / (1.0 + exp(-2.0 * field));
-    return u01_mix(z0 + kU01Step * s) < pup ? 0u : 1u;
-}
-
-// the same heat bath, handing back the probability it used (the conditional chains average 2 pup - 1, gml_cond_chains.hip)
+// heat bath of spin s: +1 iff u < pup = 1 / (1 + exp(-2 h)), u the hash of the spin's counter word z0 + kU01Step s and h its local field.
+// Returns the state bit and hands back pup (the conditional chains average 2 pup - 1).
 __device__ __forceinline__ unsigned chain_heat_bath_pup(unsigned long long z0, unsigned long long s, double field, double *pup_out) {
     const double pup = 1.0 / (1.0 + exp(-2.0 * field));
     *pup_out = pup;
     return u01_mix(z0 + kU01Step * s) < pup ? 0u : 1u;
+}
+
+// the same heat bath with pup dropped
+__device__ __forceinline__ unsigned chain_heat_bath(unsigned long long z0, unsigned long long s, double field) {
+    double pup;
+    return chain_heat_bath_pup(z0, s, field, &pup);
+}
+
+// is sweep `done` (the number of completed sweeps) a recorded one
+__device__ __forceinline__ bool chain_recorded(int done, int burn_in, int thin) {
+    if (done < burn_in) return false;
+    return (done - burn_in) % thin == 0;
+}
+
+// the n spins of a lane whose words are col[b * stride], as +-1 bytes o[s * ld]
+__device__ __forceinline__ void chain_unpack(int n, int nw, const unsigned *col, int stride, int8_t *o, int64_t ld) {
+    for (int b = 0; b < nw; ++b) {
+        const unsigned word = col[b * stride];
+        for (int i = 0; i < 32 && 32 * b + i < n; ++i) o[(int64_t)(32 * b + i) * ld] = (word >> i) & 1u ? (int8_t)-1 : (int8_t)1;
+    }
 }
 
 // A recorded sweep of the bit-state chains: after `done` completed sweeps, chain c (a lane whose words are col[b * stride]) writes its
@@ -47,11 +62,7 @@ __device__ __forceinline__ unsigned chain_heat_bath_pup(unsigned long long z0, u
 __device__ __forceinline__ void chain_record(int done, int burn_in, int thin, int64_t c, int64_t chains, int n, int nw, const unsigned *col,
                                              int stride, int8_t *__restrict__ out, int64_t ld) {
     if (done < burn_in || (done - burn_in) % thin != 0 || c >= chains) return;
-    int8_t *o = out + (int64_t)((done - burn_in) / thin) * chains + c;
-    for (int b = 0; b < nw; ++b) {
-        const unsigned word = col[b * stride];
-        for (int i = 0; i < 32 && 32 * b + i < n; ++i) o[(int64_t)(32 * b + i) * ld] = (word >> i) & 1u ? (int8_t)-1 : (int8_t)1;
-    }
+    chain_unpack(n, nw, col, stride, out + (int64_t)((done - burn_in) / thin) * chains + c, ld);
 }
 
 } // namespace gml

@@ -20,7 +20,6 @@
 // load per update in place of an LDS read per visible other spin.
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_chain.h"
 #include "gml_term_field.h"
 
 namespace gml {
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(256) void k_cond_chains(const TermChainSpin *__rest
     const double inv = 1.0 / (double)spc;
     for (int sw = 0; sw < sweeps; ++sw) {
         const unsigned long long z0 = chain_z0(seed, c, n, sw);
-        const bool recorded = sw + 1 >= burn_in && (sw + 1 - burn_in) % thin == 0, last = sw == sweeps - 1;
+        const bool recorded = chain_recorded(sw + 1, burn_in, thin), last = sw == sweeps - 1;
         for (int a = 0; a < H; ++a) {
             const TermChainSpin &r = hspin[a];
             const int i = hid[a];
@@ -70,15 +69,9 @@ __global__ __launch_bounds__(256) void k_cond_chains(const TermChainSpin *__rest
             if constexpr (SPLIT) S += mine ? cst[(int64_t)a * chains + c] : 0;
             const double h = r.a + r.sig * (double)S;
             double pup = 0.0;
-            const unsigned neg = MEANS ? chain_heat_bath_pup(z0, (unsigned long long)i, h, &pup) : chain_heat_bath(z0, (unsigned long long)i, h);
-            unsigned *wp = my + (i >> 5) * T;
-            *wp = (*wp & ~(1u << (i & 31))) | (neg << (i & 31));
+            chain_set_spin(my, T, i, chain_heat_bath_pup(z0, (unsigned long long)i, h, &pup));
             if constexpr (MEANS)
-                if (recorded && mine) {
-                    double *m = means + (int64_t)a * chains + c;
-                    const double v = *m + (2.0 * pup - 1.0);
-                    *m = last ? v * inv : v;
-                }
+                if (recorded && mine) chain_mean_add(means + (int64_t)a * chains + c, pup, last, inv);
         }
         if (out) chain_record(sw + 1, burn_in, thin, c, chains, n, nw, my, T, out, ld);
     }
@@ -88,12 +81,9 @@ void launch_cond_chains(const TermChainSpin *dhspin, const TermChainSpin *dcspin
                         const unsigned *drec, const unsigned *dSb, int64_t wpr, int64_t K, int64_t n, int64_t H, int64_t chains,
                         int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout, int64_t ld, double *dmeans, long long *dcst,
                         hipStream_t st) {
-    const int T = term_chains_tile(n, chains);
-    const int shmem = (int)((n + 31) / 32) * T * 4;
     auto launch = [&](auto kernel) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((chains + T - 1) / T)), dim3(T), shmem, st, dhspin, dcspin, dhid, dhidden, drec, dSb, wpr, K,
-                           (int)n, (int)H, chains, burn_in, thin, spc, seed, dout, ld, dmeans, dcst);
+        launch_on_chain_tile(kernel, term_chains_tile(n, chains), (n + 31) / 32, chains, st, dhspin, dcspin, dhid, dhidden, drec, dSb, wpr, K,
+                             (int)n, (int)H, chains, burn_in, thin, spc, seed, dout, ld, dmeans, dcst);
     };
     const bool split = dcspin != nullptr, want_means = dmeans != nullptr;
     if (split && want_means) launch(&k_cond_chains<true, true>);

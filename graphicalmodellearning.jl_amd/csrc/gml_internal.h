@@ -98,7 +98,7 @@ int gml_create_parts(const void *samples, int dtype, int64_t K, int64_t n, int64
                      const std::vector<std::pair<int64_t, int64_t>> &ranges, const std::vector<int> &devices,
                      std::vector<gml_problem *> &parts);
 
-// shared between the host files (gml_host.cpp: core; gml_ingest.cpp; gml_sampled.cpp; gml_operator.cpp)
+// shared between the host files (gml_host.cpp: core; gml_ingest.cpp; gml_sampled.cpp; gml_chains_host.cpp; gml_operator.cpp)
 int64_t gml_binom(int64_t n, int64_t k);
 bool gml_next_comb(std::vector<int> &idx, int64_t n);
 void gml_node_cols(const gml_problem *p, int64_t u, std::vector<int32_t> &cols);

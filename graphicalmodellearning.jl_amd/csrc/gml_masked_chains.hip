@@ -19,7 +19,6 @@
 // every lane has its own.
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_chain.h"
 #include "gml_term_field.h"
 
 namespace gml {
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(256) void k_masked_chains(const TermChainSpin *__re
     const double inv = 1.0 / (double)spc;
     for (int sw = 0; sw < sweeps; ++sw) {
         const unsigned long long z0 = chain_z0(seed, c, n, sw);
-        const bool recorded = sw + 1 >= burn_in && (sw + 1 - burn_in) % thin == 0, last = sw == sweeps - 1;
+        const bool recorded = chain_recorded(sw + 1, burn_in, thin), last = sw == sweeps - 1;
         for (int b = 0; b < nw; ++b) {
             const unsigned mword = mym[b * T];
             unsigned *wp = my + b * T;
@@ -76,15 +75,11 @@ __global__ __launch_bounds__(256) void k_masked_chains(const TermChainSpin *__re
                 const long long S = term_field_int(r, rec, my, T);
                 const double h = r.a + r.sig * (double)S;
                 double pup = 0.0;
-                const unsigned neg = MEANS ? chain_heat_bath_pup(z0, (unsigned long long)i, h, &pup) : chain_heat_bath(z0, (unsigned long long)i, h);
+                const unsigned neg = chain_heat_bath_pup(z0, (unsigned long long)i, h, &pup);
                 if ((mword >> bit) & 1u) {
-                    *wp = (*wp & ~(1u << bit)) | (neg << bit);
+                    chain_set_bit(wp, bit, neg); // (word pointer and bit index come from the walk)
                     if constexpr (MEANS)
-                        if (recorded) {
-                            double *m = means + (int64_t)i * chains + c;
-                            const double v = *m + (2.0 * pup - 1.0);
-                            *m = last ? v * inv : v;
-                        }
+                        if (recorded) chain_mean_add(means + (int64_t)i * chains + c, pup, last, inv);
                 }
             }
         }
@@ -98,12 +93,9 @@ int masked_chains_tile(int64_t n, int64_t chains) { return term_chains_tile(64 *
 void launch_masked_chains(const TermChainSpin *dspin, const unsigned *drec, const unsigned *dSb, int64_t wpr, const unsigned *dMb,
                           int64_t mwpr, int64_t K, int64_t n, int64_t chains, int burn_in, int thin, int spc, unsigned long long seed,
                           int8_t *dout, int64_t ld, double *dmeans, hipStream_t st) {
-    const int T = masked_chains_tile(n, chains);
-    const int shmem = 2 * (int)((n + 31) / 32) * T * 4;
     auto launch = [&](auto kernel) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((chains + T - 1) / T)), dim3(T), shmem, st, dspin, drec, dSb, wpr, dMb, mwpr, K, (int)n,
-                           chains, burn_in, thin, spc, seed, dout, ld, dmeans);
+        launch_on_chain_tile(kernel, masked_chains_tile(n, chains), 2 * ((n + 31) / 32), chains, st, dspin, drec, dSb, wpr, dMb, mwpr, K, (int)n,
+                             chains, burn_in, thin, spc, seed, dout, ld, dmeans);
     };
     if (dmeans) launch(&k_masked_chains<true>);
     else launch(&k_masked_chains<false>);

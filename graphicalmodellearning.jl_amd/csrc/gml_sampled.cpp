@@ -1,6 +1,7 @@
 // libgml_hip, host side: handles whose samples are drawn on the device -- the step before the path (src/sampling.jl:34-106):
-// exact block sampling, Glauber chains, histogramming of the draws.
-#include "gml_internal.h"
+// exact block sampling, Glauber chains of a term list (k_glauber) and of a dense pairwise model (the int8 chains), histogramming of
+// the draws; the moments of a handle and exact enumeration of a model.  The term-list chain family is gml_chains_host.cpp.
+#include "gml_sampled.h"
 #include "gml_solver.h"
 #include "gml_pack.h"
 
@@ -21,24 +22,21 @@ using namespace gml;
 static int64_t round_up(int64_t a, int64_t b) { return gml_round_up(a, b); }
 
 // ------------------------------------------------------------------------------------------
-// Argument checks shared by the creators below.  All of them come before the device lookup (gml_check_device), so a bad argument
-// is GML_EINVAL / GML_EUNSUPPORTED on every machine, with or without a GPU.
+// Argument checks of the creators (those that gml_chains_host.cpp shares are declared, and described, in gml_sampled.h).
 // ------------------------------------------------------------------------------------------
-static int check_out(gml_problem **out) {
+int gml::check_out(gml_problem **out) {
     if (!out) return fail(GML_EINVAL, "out is NULL");
     *out = nullptr;
     return GML_OK;
 }
 
-// Terms of one model: spins of term t = keys[t*stride .. +stride) (0-based, -1 = unused slot).  strict (the term chains): NULL
-// pointers and a negative count are refused for an empty list too.
-static int check_term_pointers(const int32_t *keys, int stride, const double *weights, int64_t nterms, bool strict = false) {
+int gml::check_term_pointers(const int32_t *keys, int stride, const double *weights, int64_t nterms, bool strict) {
     const bool null = !keys || !weights;
     if (stride < 1 || (null && (strict || nterms > 0)) || (strict && nterms < 0)) return fail(GML_EINVAL, "NULL or malformed term list");
     return GML_OK;
 }
 
-static int check_term_values(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n) {
+int gml::check_term_values(const int32_t *keys, int stride, const double *weights, int64_t nterms, int64_t n) {
     for (int64_t t = 0; t < nterms; ++t) {
         if (!std::isfinite(weights[t])) return fail(GML_EINVAL, "weight of term %lld is not finite", (long long)t);
         for (int a = 0; a < stride; ++a) {
@@ -49,9 +47,7 @@ static int check_term_values(const int32_t *keys, int stride, const double *weig
     return GML_OK;
 }
 
-// The distinct spins of one key after cancellation (a spin named twice cancels: s^2 = 1), in the order that fixes the record stream
-// of the term chains and the FP64 summation order of k_glauber.  Returns a spin the key names (cancelled or not), -1 for the empty key.
-static int reduce_key(const int32_t *key, int stride, std::vector<int> &sp) {
+int gml::reduce_key(const int32_t *key, int stride, std::vector<int> &sp) {
     sp.clear();
     int named = -1;
     for (int a = 0; a < stride; ++a) {
@@ -65,9 +61,8 @@ static int reduce_key(const int32_t *key, int stride, std::vector<int> &sp) {
     return named;
 }
 
-// the shape of a run of thinned chains; the handle arguments sit where both chain creators have always checked them
-static int check_chain_args(int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in, int thin, int order, int64_t node0,
-                            int64_t node1) {
+int gml::check_chain_args(int64_t n, int64_t chains, int64_t samples_per_chain, int burn_in, int thin, int order, int64_t node0,
+                          int64_t node1) {
     if (n <= 0) return fail(GML_EINVAL, "n must be positive");
     if (chains < 1 || samples_per_chain < 1 || burn_in < 1 || thin < 1)
         return fail(GML_EINVAL, "chains, samples_per_chain, burn_in and thin must be at least 1");
@@ -83,7 +78,7 @@ static int check_hist_spins(int64_t n) {
     if (n > 64) return fail(GML_EUNSUPPORTED, "histogramming on the device needs n <= 64 spins (n = %lld)", (long long)n);
     return GML_OK;
 }
-static int check_hist_limits(int64_t n, int64_t M) {
+int gml::check_hist_limits(int64_t n, int64_t M) {
     if (int rc = check_hist_spins(n)) return rc;
     if (M >= ((int64_t)1 << 31)) return fail(GML_EUNSUPPORTED, "histogramming on the device needs fewer than 2^31 samples");
     return GML_OK;
@@ -99,81 +94,6 @@ static int check_symmetric_finite(const double *model, int64_t n) {
         }
     return GML_OK;
 }
-
-// ------------------------------------------------------------------------------------------
-// What a creator holds on the device while its sampler runs: the stream, the handle under construction, the sampler's output bytes
-// and every temporary buffer.  begin, upload / alloc, the launches, finish; the destructor frees whatever finish has not handed on,
-// on every path.  The first failed call is kept in rc (codes and texts as HIPCHK) and makes the later ones no-ops.
-// ------------------------------------------------------------------------------------------
-struct SamplerStaging {
-    hipStream_t st = nullptr;
-    gml_problem *p = nullptr;
-    int8_t *out = nullptr; // the draws as +-1 bytes
-    std::vector<void *> tmp;
-    int rc = GML_OK;
-
-    SamplerStaging() = default;
-    SamplerStaging(const SamplerStaging &) = delete;
-    SamplerStaging &operator=(const SamplerStaging &) = delete;
-    ~SamplerStaging() {
-        release();
-        if (out) (void)dev_free(out);
-        delete p;
-    }
-    bool ok(hipError_t e, const char *call) {
-        if (rc == GML_OK && e != hipSuccess)
-            rc = fail(e == hipErrorOutOfMemory ? GML_ENOMEM : GML_EHIP, "%s failed: %s", call, hipGetErrorString(e));
-        return rc == GML_OK;
-    }
-    // no handle (gml_log_partition_ais): the device and a stream for upload / alloc / sync; the destructor releases as always
-    int open(int device) {
-        if (ok(hipSetDevice(device), "hipSetDevice")) ok(hipStreamCreate(&st), "hipStreamCreate");
-        return rc;
-    }
-    // the handle's K rows of n spins; out_bytes of output, cleared if the sampler does not write all of them
-    int begin(int device, int64_t K, int64_t n, int order, int64_t node0, int64_t node1, size_t out_bytes, bool clear) {
-        if (!ok(hipSetDevice(device), "hipSetDevice")) return rc;
-        p = gml_new_problem(K, n, (double)K, order, node0, node1, device);
-        if (ok(hipStreamCreate(&st), "hipStreamCreate") && ok(dev_malloc(&out, out_bytes), "dev_malloc") && clear)
-            ok(hipMemsetAsync(out, 0, out_bytes, st), "hipMemsetAsync");
-        return rc;
-    }
-    template <class T> T *alloc(size_t count) {
-        T *d = nullptr;
-        if (rc != GML_OK || !ok(dev_malloc(&d, sizeof(T) * count), "dev_malloc")) return nullptr;
-        tmp.push_back(d);
-        return d;
-    }
-    template <class T> void copy(T *dst, const std::vector<T> &v) {
-        if (rc == GML_OK && !v.empty()) ok(hipMemcpyAsync(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-    }
-    template <class T> T *upload(const std::vector<T> &v) {
-        T *d = alloc<T>(v.size());
-        copy(d, v);
-        return rc == GML_OK ? d : nullptr;
-    }
-    // after the launches: their errors, and the stream drained (the host vectors behind the uploads may go)
-    int sync() {
-        if (ok(hipGetLastError(), "the sampler's launch")) ok(hipStreamSynchronize(st), "hipStreamSynchronize");
-        return rc;
-    }
-    void release() {
-        for (void *q : tmp) (void)dev_free(q);
-        tmp.clear();
-        if (st) (void)hipStreamDestroy(st);
-        st = nullptr;
-    }
-    // the handle from the output bytes (sample-major [K][n] or, spin_major, [n][ld]); gml_create_from_device_bytes owns both from here
-    int finish(bool spin_major, int64_t ld, bool dedupe, gml_problem **result) {
-        if (sync()) return rc;
-        release();
-        gml_problem *q = p;
-        int8_t *bytes = out;
-        p = nullptr;
-        out = nullptr;
-        return gml_create_from_device_bytes(q, bytes, spin_major, ld, nullptr, result, dedupe);
-    }
-};
 
 // Connected components of the term hypergraph (the exact sampler, gml_model_exact): blocks[b] = the spins of component b in
 // ascending order, the components in the order of their smallest spin; id[i] = the component of spin i.
@@ -267,10 +187,7 @@ static int create_sampled_terms(const int32_t *keys, int stride, const double *w
     return s.finish(false, 0, dedupe, out);
 }
 
-// Incidence lists of a term list (create_mcmc_terms, gml_problem_create_mcmc_terms_chains): for every spin the terms it belongs
-// to, in term order (weight + the other spins; a spin named twice cancels, zero-weight terms are skipped).
-using Incidences = std::vector<std::vector<std::pair<double, std::vector<int>>>>;
-static Incidences build_incidences(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n) {
+Incidences gml::build_incidences(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n) {
     Incidences inc((size_t)n);
     std::vector<int> sp;
     for (int64_t t = 0; t < nterms; ++t) {
@@ -381,369 +298,6 @@ extern "C" int gml_problem_create_mcmc_chains(const double *model, int64_t n, in
     if (s.rc) return s.rc;
     launch_mcmc_chains(dDg, dq, dd, ds, dsum, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, s.out, ld, s.st);
     return s.finish(true, ld, histogram != 0, out); // the recorded states, spin-major
-}
-
-// The model of gml_problem_create_mcmc_terms_chains.  The couplings of every spin are quantised: sigma_i = 2^(E - 38) with
-// max_e |w_e| < 2^E over its incidences with other spins, q_e = rint(w_e / sigma_i), and the incidences grouped by arity into the
-// record stream of TermChainSpin (gml_dev.h): per spin a_i, sigma_i, Q_i and the records (q_e 2^24 + j_1 as two words, then j_2 .. j_k).
-// The records are appended to rec.  keep (spin, its other spins), when given: a_i and sigma_i as always, but Q_i and the records cover
-// only the incidences with other spins that it accepts (the start energy of gml_log_partition_ais, the record sets of the conditional
-// chains).
-using KeepIncidence = std::function<bool(int64_t, const std::vector<int> &)>;
-static void build_spin_records(const Incidences &inc, std::vector<TermChainSpin> &spin, std::vector<unsigned> &rec,
-                               const KeepIncidence &keep = nullptr) {
-    const int64_t n = (int64_t)inc.size();
-    spin.assign((size_t)n, TermChainSpin{});
-    for (int64_t i = 0; i < n; ++i) {
-        TermChainSpin &r = spin[(size_t)i];
-        double a = 0.0, mx = 0.0;
-        for (auto &e : inc[(size_t)i]) {
-            if (e.second.empty()) a += e.first;
-            else mx = std::max(mx, std::fabs(e.first));
-        }
-        int ex = 0;
-        if (mx > 0) (void)std::frexp(mx, &ex);
-        r.a = a;
-        r.sig = std::ldexp(1.0, ex - 38);
-        long long Q = 0;
-        r.off[0] = (long long)rec.size();
-        for (int k = 1; k <= kTermChainsMaxOthers; ++k) {
-            for (auto &e : inc[(size_t)i]) {
-                if (e.second.size() != (size_t)k) continue;
-                if (keep && !keep(i, e.second)) continue;
-                const long long q = (long long)std::nearbyint(std::ldexp(e.first, 38 - ex));
-                Q += q;
-                const unsigned long long P = ((unsigned long long)q << 24) | (unsigned long long)e.second[0];
-                rec.push_back((unsigned)P);
-                rec.push_back((unsigned)(P >> 32));
-                for (int m = 1; m < k; ++m) rec.push_back((unsigned)e.second[(size_t)m]);
-            }
-            r.off[k] = (long long)rec.size();
-        }
-        r.Q = Q;
-    }
-    if (rec.empty()) rec.push_back(0u);
-}
-
-// the term-chain kernel's limits: distinct spins per term, incidences with other spins per spin
-static int check_term_chain_limits(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n) {
-    std::vector<int64_t> cnt((size_t)n, 0);
-    std::vector<int> sp;
-    for (int64_t t = 0; t < nterms; ++t) {
-        if (weights[t] == 0.0) continue;
-        reduce_key(keys + t * key_stride, key_stride, sp);
-        if (sp.size() > (size_t)kTermChainsMaxOthers + 1)
-            return fail(GML_EUNSUPPORTED, "term %lld names %zu distinct spins: the term-list chain kernel supports at most %d",
-                        (long long)t, sp.size(), kTermChainsMaxOthers + 1);
-        if (sp.size() > 1)
-            for (int v : sp)
-                if (++cnt[(size_t)v] >= ((int64_t)1 << 24))
-                    return fail(GML_EUNSUPPORTED, "spin %d has 2^24 or more incidences with other spins: the term-list chain kernel "
-                                                  "supports fewer than 2^24", v);
-    }
-    return GML_OK;
-}
-
-// gml_problem_create_mcmc_terms_chains: thinned Glauber chains of any term list with exact integer fields (gml_term_chains.hip).
-extern "C" int gml_problem_create_mcmc_terms_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                                    int64_t chains, int64_t samples_per_chain, int burn_in, int thin, uint64_t seed,
-                                                    int histogram, int order, int64_t node0, int64_t node1, int device, gml_problem **out) {
-    if (int rc = check_out(out)) return rc;
-    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
-    if (int rc = check_chain_args(n, chains, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
-    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
-    const int64_t M = chains * samples_per_chain;
-    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
-        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
-                    (long long)n);
-    if (histogram)
-        if (int rc = check_hist_limits(n, M)) return rc;
-    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
-    std::vector<TermChainSpin> spin;
-    std::vector<unsigned> rec;
-    build_spin_records(build_incidences(keys, key_stride, weights, nterms, n), spin, rec);
-    if (int rc = gml_check_device(device)) return rc;
-    const int64_t ld = round_up(M, 256);
-    SamplerStaging s;
-    if (int rc = s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true)) return rc;
-    const TermChainSpin *dspin = s.upload(spin);
-    const unsigned *drec = s.upload(rec);
-    if (s.rc) return s.rc;
-    launch_term_chains(dspin, drec, n, chains, burn_in, thin, (int)samples_per_chain, (unsigned long long)seed, s.out, ld, s.st);
-    return s.finish(true, ld, histogram != 0, out); // the recorded states, spin-major
-}
-
-// the ladder of gml_problem_create_mcmc_terms_tempered: a power of two of rungs up to 64, finite betas that do not increase, the first positive
-static int check_ladder(const double *betas, int replicas, int swap_every, int64_t ladders) {
-    if (!betas) return fail(GML_EINVAL, "betas is NULL");
-    if (replicas < 1 || replicas > 64 || (replicas & (replicas - 1)) != 0)
-        return fail(GML_EINVAL, "replicas must be one of 1, 2, 4, 8, 16, 32, 64 (given %d)", replicas);
-    for (int r = 0; r < replicas; ++r) {
-        if (!std::isfinite(betas[r]) || betas[r] < 0.0) return fail(GML_EINVAL, "betas[%d] is negative or not finite", r);
-        if (r > 0 && betas[r] > betas[r - 1]) return fail(GML_EINVAL, "betas must not increase (betas[%d] > betas[%d])", r, r - 1);
-    }
-    if (!(betas[0] > 0.0)) return fail(GML_EINVAL, "betas[0] must be positive");
-    if (swap_every < 1) return fail(GML_EINVAL, "swap_every must be at least 1");
-    if (ladders > ((int64_t)1 << 40) / replicas) return fail(GML_EINVAL, "ladders * replicas is too large");
-    return GML_OK;
-}
-
-// gml_problem_create_mcmc_terms_tempered: replica-exchange chains of any term list, rung 0 recorded (gml_tempered_chains.hip).
-extern "C" int gml_problem_create_mcmc_terms_tempered(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                                      int64_t ladders, int64_t samples_per_chain, int burn_in, int thin,
-                                                      const double *betas, int replicas, int swap_every, uint64_t seed, int histogram,
-                                                      int order, int64_t node0, int64_t node1, int device, int64_t *swap_counts,
-                                                      gml_problem **out) {
-    if (int rc = check_out(out)) return rc;
-    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
-    if (int rc = check_chain_args(n, ladders, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
-    if (int rc = check_ladder(betas, replicas, swap_every, ladders)) return rc;
-    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
-    const int64_t M = ladders * samples_per_chain;
-    if (n > kMcmcChainsMaxN || term_chains_tile(n, ladders * replicas) == 0)
-        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
-                    (long long)n);
-    if (histogram)
-        if (int rc = check_hist_limits(n, M)) return rc;
-    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
-    std::vector<TermChainSpin> spin;
-    std::vector<unsigned> rec;
-    build_spin_records(build_incidences(keys, key_stride, weights, nterms, n), spin, rec);
-    if (int rc = gml_check_device(device)) return rc;
-    const int64_t ld = round_up(M, 256);
-    const size_t ncounts = 2 * (size_t)(replicas - 1);
-    std::vector<unsigned long long> counts(std::max<size_t>(ncounts, 1), 0ull);
-    const std::vector<double> ladder(betas, betas + replicas);
-    SamplerStaging s;
-    if (int rc = s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true)) return rc;
-    const TermChainSpin *dspin = s.upload(spin);
-    const unsigned *drec = s.upload(rec);
-    const double *dbetas = s.upload(ladder);
-    unsigned long long *dcounts = s.upload(counts); // zeros
-    if (s.rc) return s.rc;
-    launch_tempered_chains(dspin, drec, n, ladders, replicas, dbetas, swap_every, burn_in, thin, (int)samples_per_chain,
-                           (unsigned long long)seed, s.out, ld, dcounts, s.st);
-    s.ok(hipMemcpyAsync(counts.data(), dcounts, sizeof(unsigned long long) * counts.size(), hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
-    if (int rc = s.finish(true, ld, histogram != 0, out)) return rc; // the recorded states of rung 0, spin-major
-    if (swap_counts)
-        for (size_t k = 0; k < ncounts; ++k) swap_counts[k] = (int64_t)counts[k];
-    return GML_OK;
-}
-
-// the schedule of gml_log_partition_ais: at least two finite betas >= 0, the first 0; a sweep count that fits the chains' counter
-static int check_schedule(const double *betas, int64_t nbetas, int sweeps_per_step) {
-    if (!betas) return fail(GML_EINVAL, "betas is NULL");
-    if (nbetas < 2) return fail(GML_EINVAL, "nbetas must be at least 2 (given %lld)", (long long)nbetas);
-    if (sweeps_per_step < 1) return fail(GML_EINVAL, "sweeps_per_step must be at least 1");
-    if (nbetas - 1 > (int64_t)INT32_MAX / sweeps_per_step) return fail(GML_EINVAL, "(nbetas - 1) * sweeps_per_step exceeds 2^31 - 1 sweeps");
-    for (int64_t t = 0; t < nbetas; ++t)
-        if (!std::isfinite(betas[t]) || betas[t] < 0.0) return fail(GML_EINVAL, "betas[%lld] is negative or not finite", (long long)t);
-    if (betas[0] != 0.0) return fail(GML_EINVAL, "betas[0] must be 0 (the chains start from an exact draw at beta = 0)");
-    return GML_OK;
-}
-
-// gml_log_partition_ais: annealed importance sampling of any term list (gml_ais_chains.hip); the estimate itself on the host.
-extern "C" int gml_log_partition_ais(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t chains,
-                                     const double *betas, int64_t nbetas, int sweeps_per_step, uint64_t seed, int device,
-                                     double *log_weights, double *energies, int8_t *spins, double *result) {
-    if (!log_weights) return fail(GML_EINVAL, "log_weights is NULL");
-    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
-    if (n <= 0) return fail(GML_EINVAL, "n must be positive");
-    if (chains < 1 || chains > (int64_t)1 << 31) return fail(GML_EINVAL, "chains must lie in [1, 2^31] (given %lld)", (long long)chains);
-    if (int rc = check_schedule(betas, nbetas, sweeps_per_step)) return rc;
-    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
-    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
-        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
-                    (long long)n);
-    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
-    // one stream of records, two sets of spin records into it: the fields, and every term once for the start energy
-    std::vector<TermChainSpin> spin, spin0;
-    std::vector<unsigned> rec;
-    {
-        const Incidences inc = build_incidences(keys, key_stride, weights, nterms, n);
-        build_spin_records(inc, spin, rec);
-        // every term once, at its smallest spin: the incidences whose other spins are all above i
-        build_spin_records(inc, spin0, rec, [](int64_t i, const std::vector<int> &others) {
-            return *std::min_element(others.begin(), others.end()) >= i;
-        });
-    }
-    if (int rc = gml_check_device(device)) return rc;
-    const std::vector<double> schedule(betas, betas + nbetas);
-    SamplerStaging s;
-    if (int rc = s.open(device)) return rc;
-    const TermChainSpin *dspin = s.upload(spin), *dspin0 = s.upload(spin0);
-    const unsigned *drec = s.upload(rec);
-    const double *dbetas = s.upload(schedule);
-    double *dlogw = s.alloc<double>((size_t)chains), *dE = energies ? s.alloc<double>((size_t)chains) : nullptr;
-    int8_t *dstates = spins ? s.alloc<int8_t>((size_t)chains * (size_t)n) : nullptr;
-    if (s.rc) return s.rc;
-    launch_ais_chains(dspin, dspin0, drec, n, chains, dbetas, nbetas, sweeps_per_step, (unsigned long long)seed, dlogw, dE, dstates, s.st);
-    s.ok(hipGetLastError(), "the sampler's launch");
-    s.ok(hipMemcpyAsync(log_weights, dlogw, sizeof(double) * (size_t)chains, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
-    if (energies) s.ok(hipMemcpyAsync(energies, dE, sizeof(double) * (size_t)chains, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
-    if (spins) s.ok(hipMemcpyAsync(spins, dstates, (size_t)chains * (size_t)n, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
-    if (s.sync()) return s.rc;
-    if (result) {
-        // log of the mean weight around the largest one, its delta-method standard error, the effective sample size; chain order
-        double m = log_weights[0];
-        for (int64_t c = 1; c < chains; ++c) m = std::max(m, log_weights[c]);
-        double s1 = 0.0, s2 = 0.0;
-        for (int64_t c = 0; c < chains; ++c) {
-            const double x = std::exp(log_weights[c] - m);
-            s1 += x;
-            s2 += x * x;
-        }
-        const double mean = s1 / (double)chains;
-        result[0] = (double)n * std::log(2.0) + m + std::log(mean);
-        result[1] = chains > 1 ? std::sqrt(std::max(s2 / (double)chains - mean * mean, 0.0) / (double)(chains - 1)) / mean : 0.0;
-        result[2] = s1 * s1 / s2;
-    }
-    return GML_OK;
-}
-
-// The device part of the _masked entry points (conditional_chains has made every check): the spin records of k_term_chains over all
-// incidences, the two handles' sign bits, one launch.  means [n][chains] (host) or NULL; out as conditional_chains.
-static int masked_chains(const Incidences &inc, int64_t n, gml_problem *evidence, gml_problem *mask, int64_t chains, int64_t samples_per_chain,
-                         int burn_in, int thin, uint64_t seed, int order, int64_t node0, int64_t node1, gml_problem **out, double *means) {
-    std::vector<TermChainSpin> spin;
-    std::vector<unsigned> rec;
-    build_spin_records(inc, spin, rec);
-    const int device = evidence->device;
-    if (int rc = gml_check_device(device)) return rc;
-    const int64_t M = chains * samples_per_chain, ld = round_up(M, 256);
-    SamplerStaging s;
-    if (out ? s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true) : s.open(device)) return s.rc;
-    s.ok(hipStreamSynchronize(evidence->st), "hipStreamSynchronize"); // (whatever the caller last ran on the two handles)
-    s.ok(hipStreamSynchronize(mask->st), "hipStreamSynchronize");
-    const TermChainSpin *dspin = s.upload(spin);
-    const unsigned *drec = s.upload(rec);
-    const size_t nmeans = (size_t)n * (size_t)chains;
-    double *dmeans = means ? s.alloc<double>(nmeans) : nullptr; // (the kernel writes every entry)
-    if (s.rc) return s.rc;
-    launch_masked_chains(dspin, drec, evidence->d.Sb, evidence->d.Kp / 32, mask->d.Sb, mask->d.Kp / 32, evidence->K, n, chains, burn_in, thin,
-                         (int)samples_per_chain, (unsigned long long)seed, s.out, ld, dmeans, s.st);
-    s.ok(hipGetLastError(), "the sampler's launch");
-    if (means) s.ok(hipMemcpyAsync(means, dmeans, sizeof(double) * nmeans, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
-    if (!out) return s.sync();
-    return s.finish(true, ld, false, out); // the recorded states, spin-major; row (t, r, k) belongs to evidence row k
-}
-
-// gml_problem_create_mcmc_terms_conditional and gml_conditional_means behind one body (gml_cond_chains.hip): out != NULL makes the handle
-// of the recorded states, means != NULL ([H][K replicas], host) receives the Rao-Blackwellised conditional means.  per_row: the
-// _masked entry points (gml_masked_chains.hip) -- the hidden set comes row by row from the sign bits of the handle `rowmask`, not from
-// hidden [n]; means is [n][K replicas].
-static int conditional_chains(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
-                              const uint8_t *hidden, gml_problem *rowmask, bool per_row, int replicas, int64_t samples_per_chain, int burn_in,
-                              int thin, uint64_t seed, int order, int64_t node0, int64_t node1, gml_problem **out, double *means) {
-    if (!evidence) return fail(GML_EINVAL, "evidence is NULL");
-    if (per_row ? !rowmask : !hidden) return fail(GML_EINVAL, per_row ? "mask is NULL" : "hidden is NULL");
-    if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
-    if (n != evidence->n) return fail(GML_EINVAL, "n = %lld differs from the evidence handle's %lld spins", (long long)n, (long long)evidence->n);
-    if (per_row && (rowmask->n != evidence->n || rowmask->K != evidence->K || rowmask->device != evidence->device))
-        return fail(GML_EINVAL, "the mask handle (n = %lld, %lld rows, device %d) differs from the evidence handle (n = %lld, %lld rows, device %d)",
-                    (long long)rowmask->n, (long long)rowmask->K, rowmask->device, (long long)evidence->n, (long long)evidence->K, evidence->device);
-    if (replicas < 1) return fail(GML_EINVAL, "replicas must be at least 1 (given %d)", replicas);
-    const int64_t K = evidence->K;
-    if (K > ((int64_t)1 << 40) / replicas) return fail(GML_EINVAL, "the evidence handle's rows times replicas is too large");
-    const int64_t chains = K * replicas;
-    if (int rc = check_chain_args(n, chains, samples_per_chain, burn_in, thin, order, node0, node1)) return rc;
-    std::vector<int> hid;
-    for (int64_t i = 0; !per_row && i < n; ++i)
-        if (hidden[i]) hid.push_back((int)i);
-    if (!per_row && hid.empty()) return fail(GML_EINVAL, "no spin is hidden");
-    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
-    if (n > kMcmcChainsMaxN || term_chains_tile(n, chains) == 0)
-        return fail(GML_EUNSUPPORTED, "the term-list chain kernel supports n <= %lld spins (n = %lld)", (long long)kMcmcChainsMaxN,
-                    (long long)n);
-    if (per_row && masked_chains_tile(n, chains) == 0) // (state and mask words of 64 chains: twice the LDS of the other chain kernels)
-        return fail(GML_EUNSUPPORTED, "the per-row masked chain kernel supports n <= %lld spins (n = %lld)",
-                    (long long)(kMcmcChainsLds / (64 * 4 * 2) * 32), (long long)n);
-    if (int rc = check_term_chain_limits(keys, key_stride, weights, nterms, n)) return rc;
-    if (per_row) return masked_chains(build_incidences(keys, key_stride, weights, nterms, n), n, evidence, rowmask, chains, samples_per_chain,
-                                      burn_in, thin, seed, order, node0, node1, out, means);
-    // one stream of records for the hidden spins: all their incidences, or (the constant part of the field) those whose other spins are
-    // all visible and those with a hidden other spin as two sets.  The constant costs an update one 8-byte global load and saves it
-    // the LDS reads of the const records: the split is taken when these average kCondSplitReads per hidden spin (measured: a
-    // lattice with 3.5 loses 12 %, a sparse order-3 model with 21 gains 23 %, a dense model with 900 runs five times as fast;
-    // g_cond_split = 2 takes it whenever there is a const record, 0 never).  The bits are the same either way.
-    constexpr int64_t kCondSplitReads = 8;
-    const int64_t H = (int64_t)hid.size();
-    std::vector<TermChainSpin> live, cnst;
-    std::vector<unsigned> rec;
-    {
-        const Incidences inc = build_incidences(keys, key_stride, weights, nterms, n);
-        auto some_hidden = [&](const std::vector<int> &others) {
-            return std::any_of(others.begin(), others.end(), [&](int j) { return hidden[j] != 0; });
-        };
-        std::vector<TermChainSpin> all;
-        if (g_cond_split) {
-            build_spin_records(inc, all, rec, [&](int64_t i, const std::vector<int> &others) { return hidden[i] && !some_hidden(others); });
-            for (int i : hid) cnst.push_back(all[(size_t)i]);
-            int64_t reads = 0; // other spins named by the const records
-            for (const TermChainSpin &r : cnst)
-                for (int k = 1; k <= kTermChainsMaxOthers; ++k) reads += (r.off[k] - r.off[k - 1]) / (k + 1) * k;
-            if (reads == 0 || (g_cond_split != 2 && reads < kCondSplitReads * H)) cnst.clear(), rec.clear();
-        }
-        const bool split = !cnst.empty();
-        build_spin_records(inc, all, rec, [&](int64_t i, const std::vector<int> &others) { return hidden[i] && (!split || some_hidden(others)); });
-        for (int i : hid) live.push_back(all[(size_t)i]);
-    }
-    const std::vector<uint8_t> mask(hidden, hidden + n);
-    const int device = evidence->device;
-    if (int rc = gml_check_device(device)) return rc;
-    const int64_t M = chains * samples_per_chain, ld = round_up(M, 256);
-    SamplerStaging s;
-    if (out ? s.begin(device, M, n, order, node0, node1, (size_t)n * ld, true) : s.open(device)) return s.rc;
-    s.ok(hipStreamSynchronize(evidence->st), "hipStreamSynchronize"); // (whatever the caller last ran on the evidence handle)
-    const TermChainSpin *dlive = s.upload(live), *dcnst = cnst.empty() ? nullptr : s.upload(cnst);
-    const int *dhid = s.upload(hid);
-    const uint8_t *dmask = s.upload(mask);
-    const unsigned *drec = s.upload(rec);
-    long long *dcst = cnst.empty() ? nullptr : s.alloc<long long>((size_t)H * (size_t)chains);
-    const size_t nmeans = (size_t)H * (size_t)chains;
-    double *dmeans = means ? s.alloc<double>(nmeans) : nullptr;
-    if (dmeans) s.ok(hipMemsetAsync(dmeans, 0, sizeof(double) * nmeans, s.st), "hipMemsetAsync");
-    if (s.rc) return s.rc;
-    launch_cond_chains(dlive, dcnst, dhid, dmask, drec, evidence->d.Sb, evidence->d.Kp / 32, K, n, H, chains, burn_in, thin,
-                       (int)samples_per_chain, (unsigned long long)seed, s.out, ld, dmeans, dcst, s.st);
-    s.ok(hipGetLastError(), "the sampler's launch");
-    if (means) s.ok(hipMemcpyAsync(means, dmeans, sizeof(double) * nmeans, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
-    if (!out) return s.sync();
-    return s.finish(true, ld, false, out); // the recorded states, spin-major: row (t, r, k) belongs to evidence row k, so no histogram
-}
-
-extern "C" int gml_problem_create_mcmc_terms_conditional(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                                         gml_problem *evidence, const uint8_t *hidden, int replicas,
-                                                         int64_t samples_per_chain, int burn_in, int thin, uint64_t seed, int order,
-                                                         int64_t node0, int64_t node1, gml_problem **out) {
-    if (int rc = check_out(out)) return rc;
-    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, hidden, nullptr, false, replicas, samples_per_chain, burn_in, thin,
-                              seed, order, node0, node1, out, nullptr);
-}
-
-extern "C" int gml_conditional_means(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                     gml_problem *evidence, const uint8_t *hidden, int replicas, int64_t samples_per_chain, int burn_in,
-                                     int thin, uint64_t seed, double *means) {
-    if (!means) return fail(GML_EINVAL, "means is NULL");
-    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, hidden, nullptr, false, replicas, samples_per_chain, burn_in, thin,
-                              seed, 2, 0, n, nullptr, means);
-}
-
-extern "C" int gml_problem_create_mcmc_terms_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                                    gml_problem *evidence, gml_problem *mask, int replicas, int64_t samples_per_chain,
-                                                    int burn_in, int thin, uint64_t seed, int order, int64_t node0, int64_t node1,
-                                                    gml_problem **out) {
-    if (int rc = check_out(out)) return rc;
-    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, nullptr, mask, true, replicas, samples_per_chain, burn_in, thin,
-                              seed, order, node0, node1, out, nullptr);
-}
-
-extern "C" int gml_conditional_means_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                            gml_problem *evidence, gml_problem *mask, int replicas, int64_t samples_per_chain, int burn_in,
-                                            int thin, uint64_t seed, double *means) {
-    if (!means) return fail(GML_EINVAL, "means is NULL");
-    return conditional_chains(keys, key_stride, weights, nterms, n, evidence, nullptr, mask, true, replicas, samples_per_chain, burn_in, thin,
-                              seed, 2, 0, n, nullptr, means);
 }
 
 extern "C" int gml_problem_create_mcmc_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms,

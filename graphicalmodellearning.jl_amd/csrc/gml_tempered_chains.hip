@@ -11,7 +11,6 @@
 // state and its energy travel.  Rung 0 is recorded, after the swap.
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_chain.h"
 #include "gml_term_field.h"
 
 namespace gml {
@@ -44,10 +43,7 @@ __global__ __launch_bounds__(256) void k_tempered_chains(const TermChainSpin *__
             const TermChainSpin &s = spin[i];
             const double h = s.a + s.sig * term_field(s, rec, my, T);
             const unsigned neg = chain_heat_bath(z0, (unsigned long long)i, beta * h);
-            unsigned *wp = my + (i >> 5) * T;
-            const unsigned word = *wp, old = (word >> (i & 31)) & 1u;
-            *wp = (word & ~(1u << (i & 31))) | (neg << (i & 31));
-            E -= (double)(2 * ((int)old - (int)neg)) * h; // s = 1 - 2 bit: s_new - s_old = 2 (old - neg)
+            E = chain_energy_step(E, chain_set_spin(my, T, i, neg), neg, h);
         }
         const int done = sw + 1;
         if (R > 1 && done % swap_every == 0) {
@@ -86,11 +82,8 @@ void launch_tempered_chains(const TermChainSpin *dspin, const unsigned *drec, in
                             const double *dbetas, int swap_every, int burn_in, int thin, int spc, unsigned long long seed, int8_t *dout,
                             int64_t ld, unsigned long long *dswap_counts, hipStream_t st) {
     const int64_t lanes = ladders * replicas;
-    const int T = term_chains_tile(n, lanes);
-    const int shmem = (int)((n + 31) / 32) * T * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tempered_chains), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    hipLaunchKernelGGL(k_tempered_chains, dim3((unsigned)((lanes + T - 1) / T)), dim3(T), shmem, st, dspin, drec, (int)n, ladders,
-                       replicas, dbetas, swap_every, burn_in, thin, spc, seed, dout, ld, dswap_counts);
+    launch_on_chain_tile(k_tempered_chains, term_chains_tile(n, lanes), (n + 31) / 32, lanes, st, dspin, drec, (int)n, ladders, replicas,
+                         dbetas, swap_every, burn_in, thin, spc, seed, dout, ld, dswap_counts);
 }
 
 } // namespace gml

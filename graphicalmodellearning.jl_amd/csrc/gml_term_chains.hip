@@ -14,7 +14,6 @@
 // +-1 bytes, spin-major [n][ld], row t * chains + c.
 #include "../../include/gml.h"
 #include "gml_dev.h"
-#include "gml_chain.h"
 #include "gml_term_field.h"
 
 namespace gml {
@@ -34,8 +33,7 @@ __global__ __launch_bounds__(256) void k_term_chains(const TermChainSpin *__rest
             const TermChainSpin &r = spin[i];
             const double f = term_field(r, rec, my, T);
             const unsigned neg = chain_heat_bath(z0, (unsigned long long)i, r.a + r.sig * f);
-            unsigned *wp = my + (i >> 5) * T;
-            *wp = (*wp & ~(1u << (i & 31))) | (neg << (i & 31));
+            chain_set_spin(my, T, i, neg);
         }
         chain_record(sw + 1, burn_in, thin, c, chains, n, nw, my, T, out, ld);
     }
@@ -56,11 +54,8 @@ int term_chains_tile(int64_t n, int64_t chains) {
 
 void launch_term_chains(const TermChainSpin *dspin, const unsigned *drec, int64_t n, int64_t chains, int burn_in, int thin, int spc,
                         unsigned long long seed, int8_t *dout, int64_t ld, hipStream_t st) {
-    const int T = term_chains_tile(n, chains);
-    const int shmem = (int)((n + 31) / 32) * T * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_term_chains), hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    hipLaunchKernelGGL(k_term_chains, dim3((unsigned)((chains + T - 1) / T)), dim3(T), shmem, st, dspin, drec, (int)n, chains, burn_in,
-                       thin, spc, seed, dout, ld);
+    launch_on_chain_tile(k_term_chains, term_chains_tile(n, chains), (n + 31) / 32, chains, st, dspin, drec, (int)n, chains, burn_in, thin,
+                         spc, seed, dout, ld);
 }
 
 } // namespace gml

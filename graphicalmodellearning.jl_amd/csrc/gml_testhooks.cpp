@@ -95,7 +95,7 @@ extern "C" int gml_test_term_chains_tile(int T) {
     return old;
 }
 // the constant part of the conditional chains' fields (gml_cond_chains.hip): 1 (default) the incidences of a hidden spin whose other
-// spins are all observed are summed once per chain where the host's rule expects that to pay (gml_sampled.cpp), 2 wherever there is
+// spins are all observed are summed once per chain where the host's rule expects that to pay (gml_chains_host.cpp), 2 wherever there is
 // such an incidence, 0 never -- every sweep walks them; the same bits in all three.  Returns the old value, -1 for another value
 extern "C" int gml_test_cond_split(int on) {
     if (on < 0 || on > 2) return -1;

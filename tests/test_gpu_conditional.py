@@ -262,6 +262,54 @@ def test_errors(means):
         assert e.value.code == EINVAL
 
 
+# Two faults at once, on handles with rows: the checks that follow the chain arguments (no hidden spin, term values, n limit, incidence
+# limits), which a size-only stub cannot reach (tests/test_host_chain_refusal_order.py has the ones before).  Each case names two
+# neighbours of the sequence; the answers were recorded from the library before the host half of the family moved to its own file.
+NINE = {tuple(range(1, 10)): 0.1}
+BIG_N = 20000  # above the kernels' 16384 spins
+TWO_FAULTS = {
+    "thin 0 + no hidden spin": dict(terms={(1, 2): 0.3}, n=EV_N, hidden=(), thin=0),
+    "no hidden spin + non-finite weight": dict(terms={(1, 2): np.nan}, n=EV_N, hidden=()),
+    "no hidden spin + nine distinct spins": dict(terms=NINE, n=EV_N, hidden=()),
+    "non-finite weight + n above the limit": dict(terms={(1, 2): np.nan}, n=BIG_N, hidden=(1, 5)),
+    "key out of range + n above the limit": dict(terms={(1, BIG_N + 5): 0.3}, n=BIG_N, hidden=(1, 5)),
+    "n above the limit + nine distinct spins": dict(terms=NINE, n=BIG_N, hidden=(1, 5)),
+}
+EXPECTED_TWO_FAULTS = {
+    'key out of range + n above the limit':
+        (1, 'libgml_hip error 1: term 0 names spin 20004 outside [0,20000)'),
+    'n above the limit + nine distinct spins':
+        (5, 'libgml_hip error 5: the term-list chain kernel supports n <= 16384 spins (n = 20000)'),
+    'no hidden spin + nine distinct spins':
+        (1, 'libgml_hip error 1: no spin is hidden'),
+    'no hidden spin + non-finite weight':
+        (1, 'libgml_hip error 1: no spin is hidden'),
+    'non-finite weight + n above the limit':
+        (1, 'libgml_hip error 1: weight of term 0 is not finite'),
+    'thin 0 + no hidden spin':
+        (1, 'libgml_hip error 1: chains, samples_per_chain, burn_in and thin must be at least 1'),
+}
+
+
+def refusal(call, terms, n, second, means, **kw):
+    """(code, text) of the refusal of call(terms, n, evidence, second(n), ...) on an evidence handle of 3 rows of n spins"""
+    args = dict(replicas=1, samples_per_chain=1, burn_in=2, thin=1)
+    args.update(kw)
+    with gml.Problem(spins=np.ones((3, n), dtype=np.int8), node_range=(0, 1)) as p:
+        with pytest.raises(gml.GMLError) as e:
+            call(terms, n, p, second, seed=1, means=means, **args)
+    return e.value.code, str(e.value)
+
+
+@pytest.mark.parametrize("means", [False, True], ids=["creator", "means"])
+@pytest.mark.parametrize("case", sorted(TWO_FAULTS))
+def test_order_of_refusals_past_the_chain_arguments(case, means):
+    kw = dict(TWO_FAULTS[case])
+    got = refusal(_lib.conditional_chains, kw.pop("terms"), kw.pop("n"), list(kw.pop("hidden")), means, **kw)
+    print(case, "->", got)
+    assert got == EXPECTED_TWO_FAULTS[case]
+
+
 def test_spin_limit_named():
     n = 16385
     with gml.Problem(spins=np.ones((2, n), dtype=np.int8), node_range=(0, 1)) as p:

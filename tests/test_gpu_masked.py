@@ -231,6 +231,55 @@ def test_errors(means):
     bad_call(EUNSUPPORTED, "at most 8", terms={tuple(range(1, 10)): 0.1}, means=means)
 
 
+# Two faults at once, on handles with rows: the checks that follow the chain arguments (term values, n limit, the masked tile,
+# incidence limits), which a size-only stub cannot reach (tests/test_host_chain_refusal_order.py has the ones before).  Each case names
+# two neighbours of the sequence; the answers were recorded from the library before the host half of the family moved to its own file.
+NINE = {tuple(range(1, 10)): 0.1}
+BIG_N = 20000  # above the chain kernels' 16384 spins, and so above the masked kernel's 8192 too
+TWO_FAULTS = {
+    "thin 0 + non-finite weight": dict(terms={(1, 2): np.nan}, n=EV_N, thin=0),
+    "non-finite weight + n above the masked tile": dict(terms={(1, 2): np.nan}, n=8193),
+    "key out of range + n above the limit": dict(terms={(1, BIG_N + 5): 0.3}, n=BIG_N),
+    "n above the limit and the masked tile": dict(terms={(1, 2): 0.3}, n=BIG_N),
+    "n above the limit + nine distinct spins": dict(terms=NINE, n=BIG_N),
+    "n above the masked tile + nine distinct spins": dict(terms=NINE, n=8193),
+}
+EXPECTED_TWO_FAULTS = {
+    'key out of range + n above the limit':
+        (1, 'libgml_hip error 1: term 0 names spin 20004 outside [0,20000)'),
+    'n above the limit + nine distinct spins':
+        (5, 'libgml_hip error 5: the term-list chain kernel supports n <= 16384 spins (n = 20000)'),
+    'n above the limit and the masked tile':
+        (5, 'libgml_hip error 5: the term-list chain kernel supports n <= 16384 spins (n = 20000)'),
+    'n above the masked tile + nine distinct spins':
+        (5, 'libgml_hip error 5: the per-row masked chain kernel supports n <= 8192 spins (n = 8193)'),
+    'non-finite weight + n above the masked tile':
+        (1, 'libgml_hip error 1: weight of term 0 is not finite'),
+    'thin 0 + non-finite weight':
+        (1, 'libgml_hip error 1: chains, samples_per_chain, burn_in and thin must be at least 1'),
+}
+
+
+def refusal(terms, n, means, **kw):
+    """(code, text) of the refusal on an evidence and a mask handle of 3 rows of n spins"""
+    args = dict(replicas=1, samples_per_chain=1, burn_in=2, thin=1)
+    args.update(kw)
+    ones = np.ones((3, n), dtype=np.int8)
+    with gml.Problem(spins=ones, node_range=(0, 1)) as p, gml.Problem(spins=-ones, node_range=(0, 1)) as m:
+        with pytest.raises(gml.GMLError) as e:
+            _lib.conditional_chains_masked(terms, n, p, m, seed=1, means=means, **args)
+    return e.value.code, str(e.value)
+
+
+@pytest.mark.parametrize("means", [False, True], ids=["creator", "means"])
+@pytest.mark.parametrize("case", sorted(TWO_FAULTS))
+def test_order_of_refusals_past_the_chain_arguments(case, means):
+    kw = dict(TWO_FAULTS[case])
+    got = refusal(kw.pop("terms"), kw.pop("n"), means, **kw)
+    print(case, "->", got)
+    assert got == EXPECTED_TWO_FAULTS[case]
+
+
 def test_spin_limit_named():
     n = 8193  # one spin past the state and mask words of 64 chains that fit the kernel's LDS budget
     ones = np.ones((2, n), dtype=np.int8)
