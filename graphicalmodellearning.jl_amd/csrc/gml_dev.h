@@ -158,11 +158,14 @@ int i8_hessian(void *ws, const DevProblem &d, const int *dRowcol, const int *dVs
 // holding node u's sign) or -1 for padding rows.  Rp multiple of 32.
 // V [Rp][Kp]: V[r][k] = d f_r / d E_rk * s_rk = -w_k exp(-E) s (RISE: `partial_obj` of :204 times s)
 // fsum [Rp]: sum_k w_k phi(E_rk)  (must be zeroed by the caller)
+// ws: f64_reduce_ws_bytes(P, rows) bytes for launches of up to `rows` rows -- where the workgroups leave their parts of f and G, which a
+// second kernel adds in a fixed order: the same bits on every call
 // groups: ids of the 32-row groups to evaluate (padded with -1 to a multiple of 4).
 void launch_fwd_f64(const DevProblem &P, const double *Theta, const int *rowcol, const int *groups,
-                    int ngroups4, int form, double *V, double *fsum, hipStream_t st);
+                    int ngroups4, int form, double *V, double *fsum, double *ws, hipStream_t st);
+size_t f64_reduce_ws_bytes(const DevProblem &P, int64_t rows);
 // G [Rp][Qp] += sum_k V[r][k] * Xt[c][k] = the gradient (:205-207); must be zeroed by the caller
-void launch_bwd_f64(const DevProblem &P, const double *V, const int *groups, int ngroups, double *G,
+void launch_bwd_f64(const DevProblem &P, const double *V, const int *groups, int ngroups, double *G, double *ws,
                     hipStream_t st);
 // H [Rp][cap][cap] += sum_k h_rk Xt[F_ri][k] Xt[F_rj][k], lower-triangular 32x32 tiles only.
 // F [Rp][cap] column ids (padding = Qp-1), mt[r] = number of 32-tiles used by row r.

@@ -357,6 +357,7 @@ static int fill_sign_bits(const std::vector<gml_problem *> &parts, const std::fu
     if (rc) return rc;
     int64_t rows = std::max<int64_t>(1, (int64_t)(sp.cap / rowb));
     if (rows >= 32) rows = rows / 32 * 32; // whole 32-column groups for the row-major packer
+    if (g_tune[GML_TUNE_STAGE_SPINS] > 0) rows = std::min(rows, (int64_t)g_tune[GML_TUNE_STAGE_SPINS]); // (tests: many small chunks)
     const size_t G = parts.size();
     std::vector<hipEvent_t> ev(2 * G, nullptr);
     auto cleanup = [&](int code) {
@@ -375,7 +376,8 @@ static int fill_sign_bits(const std::vector<gml_problem *> &parts, const std::fu
     }
     int b = 0;
     int64_t chunk = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += rows, b ^= 1, ++chunk) {
+    g_fill_chunks = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += rows, b ^= 1, ++chunk, ++g_fill_chunks) {
         const int64_t i1 = std::min(n, i0 + rows);
         double t0 = now_s();
         if (chunk >= 2)
@@ -551,12 +553,9 @@ extern "C" int gml_problem_create_packed(const uint32_t *sign_bits, int64_t word
     int rc = gml_check_create_args(K, n, order, node0, node1, device);
     if (rc) return rc;
     if (words_per_spin < (K + 31) / 32) return fail(GML_EINVAL, "words_per_spin %lld too small for K=%lld", (long long)words_per_spin, (long long)K);
-    double M = 0;
-    for (int64_t k = 0; k < K; ++k) {
-        const double c = counts ? counts[k] : 1.0;
-        if (!(c >= 0) || !std::isfinite(c)) return fail(GML_EINVAL, "count of configuration %lld is negative or not finite", (long long)k);
-        M += c;
-    }
+    for (int64_t k = 0; counts && k < K; ++k)
+        if (!(counts[k] >= 0) || !std::isfinite(counts[k])) return fail(GML_EINVAL, "count of configuration %lld is negative or not finite", (long long)k);
+    const double M = sum_counts(counts, K, parallel_for); // the one order of M: what gml_pack_histogram returned for these counts
     if (!(M > 0)) return fail(GML_EINVAL, "sum of counts is zero");
     const int64_t wpr = gml_round_up(K, 1024) / 32, wreal = (K + 31) / 32;
     const uint32_t tailmask = (K & 31) ? ((1u << (K & 31)) - 1u) : 0xFFFFFFFFu;
@@ -645,14 +644,13 @@ extern "C" int gml_problem_create_device_convert(const void *samples, int dtype,
     CCHK(hipGetLastError());
     CCHK(hipStreamSynchronize(st));
 #undef CCHK
-    if (hbad >= 0) return cleanup(fail(GML_EINVAL, "configuration %lld holds a spin that is not +-1", hbad));
-    double Msum = 0;
-    for (int64_t k = 0; k < K; ++k) {
+    // the precedence of gml_problem_create: a bad count, a zero sum of counts, then a bad spin (all three are on the host by now)
+    for (int64_t k = 0; k < K; ++k)
         if (!(counts[k] >= 0) || !std::isfinite(counts[k]))
             return cleanup(fail(GML_EINVAL, "count of configuration %lld is negative or not finite", (long long)k));
-        Msum += counts[k];
-    }
+    const double Msum = sum_counts(counts.data(), K, parallel_for); // the one order of M, as pack_counts sums it
     if (!(Msum > 0)) return cleanup(fail(GML_EINVAL, "sum of counts is zero"));
+    if (hbad >= 0) return cleanup(fail(GML_EINVAL, "configuration %lld holds a spin that is not +-1", hbad));
     cleanup(GML_OK); // dS passes to the handle
     gml_problem *p = gml_new_problem(K, n, Msum, order, node0, node1, device);
     rc = gml_create_from_device_bytes(p, dS, col_major != 0, K, counts.data(), out);

@@ -44,6 +44,9 @@ struct gml_problem {
     int64_t ws_rows = 0;
     double *dTheta = nullptr, *dV = nullptr, *dG = nullptr, *dF = nullptr;
     int64_t dVrows = 0; // rows of the FP64 path's V (gml_ensure_f64)
+    double *dRed = nullptr; // the FP64 pass's parts of f and G before their fixed-order reduction (gml_dev.h: f64_reduce_ws_bytes)
+    size_t dRedBytes = 0;
+    int64_t dRedRows = 0; // the dVrows dRed was last sized for
     int *hCtl = nullptr; // pinned twin of the control block: srow | rowcol | groups
     int *dSrow = nullptr, *dRowcol = nullptr, *dGroups = nullptr;
     double *hTh = nullptr, *hG = nullptr, *hF = nullptr; // pinned staging (ws_rows x Qp, ws_rows)

@@ -45,19 +45,21 @@ constexpr int NT = 8; // 16-wide MFMA tiles of the +-1 side per wave (wave tile 
 #ifndef F64_FWD_WAVES
 #define F64_FWD_WAVES 4
 #endif
+// Kp is a multiple of 1024: with 128 F64_FWD_WAVES samples per workgroup dividing it, the grid covers Kp exactly, every wave of a
+// workgroup has samples, and all of them reach the barrier before the workgroup's part of f is stored
+static_assert(F64_FWD_WAVES == 1 || F64_FWD_WAVES == 2 || F64_FWD_WAVES == 4 || F64_FWD_WAVES == 8, "128 * F64_FWD_WAVES must divide 1024");
 __global__ __launch_bounds__(64 * F64_FWD_WAVES, 8 / F64_FWD_WAVES) void k_fwd_f64(const double *__restrict__ Theta, const unsigned *__restrict__ Xb,
                                                     const unsigned *__restrict__ Sb, const int *__restrict__ rowcol,
                                                     const int *__restrict__ groups, const double *__restrict__ w, int64_t Qp,
                                                     int64_t cconst, int64_t Kp, int nk, int form, double *__restrict__ V,
-                                                    double *__restrict__ fsum) {
+                                                    double *__restrict__ fpartial) {
+    __shared__ double fred[F64_FWD_WAVES][32]; // the waves' parts of f of the group's 32 rows
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int li = lane & 15, q = lane >> 4;
     const int grp = groups[blockIdx.y]; // 32-row group of this workgroup (-1: padding of the list)
     if (grp < 0) return;
     const int r0 = grp * 32;
     const int64_t k0 = (int64_t)blockIdx.x * (128 * F64_FWD_WAVES) + wave * 128; // this wave's 128 samples: one 128-sample piece of Xb
-    if (k0 >= Kp) return;
-
     v4d acc[2][NT];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
@@ -147,28 +149,58 @@ __global__ __launch_bounds__(64 * F64_FWD_WAVES, 8 / F64_FWD_WAVES) void k_fwd_f
             fpart += __shfl_xor(fpart, 2);
             fpart += __shfl_xor(fpart, 4);
             fpart += __shfl_xor(fpart, 8);
-            if (li == 0 && rc >= 0) unsafeAtomicAdd(&fsum[r], fpart);
+            if (li == 0) fred[wave][16 * mi + q + 4 * j] = fpart; // (0 for a padding row)
         }
+    }
+    if (form >= 4) return; // (a Hessian-vector forward has no objective)
+    // the workgroup's part of f, its waves added in their own order, goes to its own place: k_fsum_reduce adds the workgroups' parts in
+    // a fixed order too, so f is the same bits on every call (FP64 atomics on fsum added them in the order the waves happened to finish)
+    __syncthreads();
+    if (threadIdx.x < 32) {
+        double s = fred[0][threadIdx.x];
+#pragma unroll
+        for (int v = 1; v < F64_FWD_WAVES; ++v) s += fred[v][threadIdx.x];
+        fpartial[((int64_t)blockIdx.y * 32 + threadIdx.x) * gridDim.x + blockIdx.x] = s;
     }
 }
 
+// fsum[r] += the nx workgroup parts of row r, one wave per row: lane l adds the parts l, l + 64, ... in ascending order, the lanes meet in
+// a fixed butterfly
+__global__ __launch_bounds__(256) void k_fsum_reduce(const double *__restrict__ fpartial, const int *__restrict__ rowcol,
+                                                     const int *__restrict__ groups, int nx, double *__restrict__ fsum) {
+    const int grp = groups[blockIdx.y];
+    if (grp < 0) return;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int r = grp * 32 + t;
+    if (rowcol[r] < 0) return;
+    const double *src = fpartial + ((int64_t)blockIdx.y * 32 + t) * nx;
+    double s = 0.0;
+    for (int x = lane; x < nx; x += 64) s += src[x];
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (lane == 0) fsum[r] += s;
+}
+
 void launch_fwd_f64(const DevProblem &P, const double *Theta, const int *rowcol, const int *groups, int ngroups4, int form, double *V,
-                    double *fsum, hipStream_t st) {
+                    double *fsum, double *ws, hipStream_t st) {
     dim3 grid((unsigned)((P.Kp + 128 * F64_FWD_WAVES - 1) / (128 * F64_FWD_WAVES)), (unsigned)ngroups4);
     hipLaunchKernelGGL(k_fwd_f64, grid, dim3(64 * F64_FWD_WAVES), 0, st, Theta, P.Xb, P.Sb, rowcol, groups, P.w, P.Qp, P.cconst, P.Kp, (int)(P.Qfp / 64), form,
-                       V, fsum);
+                       V, ws);
+    if (form < 4) hipLaunchKernelGGL(k_fsum_reduce, dim3(8, (unsigned)ngroups4), dim3(256), 0, st, ws, rowcol, groups, (int)grid.x, fsum);
 }
 
 // ------------------------------------------------------------------------------------------
 // backward.  grid = (ceil(Qfp / 1024), row groups, split-K chunks); workgroup = 8 waves x 128 columns of one 32-row group over
-// one chunk of the samples; partial sums are combined with f64 atomics.  Lane (li, q) feeds step s of a 32-sample block with
+// one chunk of the samples; every chunk stores its partial sums in a place of its own (Gpart [chunk][listed row][Qp]) and
+// k_bwd_f64_reduce adds them in ascending chunk order: G is the same bits on every call (FP64 atomics added the chunks in the order
+// they happened to finish).  A single chunk adds to G directly.  Lane (li, q) feeds step s of a 32-sample block with
 // V[row li][k + 8 q + s] and, from the lane's dword (column li, block) of the Xtb image, the bit of sample k + 8 q + s:
 // bit q + 4 (s >> 2) + 8 (s & 3) (gml_bits.h: xtb_from_natural).  The constant statistic (x = 1 on every real sample; V is 0 on
 // the padding ones) is the plain row sum of V: wave 0 of the first column block adds it up on the side.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 1) void k_bwd_f64(const double *__restrict__ V, const unsigned *__restrict__ Xtb,
                                                     const int *__restrict__ groups, int64_t Qp, int64_t Qf, int64_t Qc /* columns of the image */,
-                                                    int64_t cconst, int64_t Kp, int64_t kchunk, double *__restrict__ G) {
+                                                    int64_t cconst, int64_t Kp, int64_t kchunk, double *__restrict__ G,
+                                                    double *__restrict__ Gpart) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int li = lane & 15, q = lane >> 4;
     const int r0 = groups[blockIdx.y] * 32;
@@ -233,7 +265,11 @@ __global__ __launch_bounds__(512, 1) void k_bwd_f64(const double *__restrict__ V
             const int64_t c = c0 + 16 * ni + li;
             if (c < Qf) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) unsafeAtomicAdd(&G[(int64_t)(r0 + 16 * mi + q + 4 * j) * Qp + c], acc[mi][ni][j]);
+                for (int j = 0; j < 4; ++j) {
+                    const int rr = 16 * mi + q + 4 * j;
+                    if (gridDim.z == 1) G[(int64_t)(r0 + rr) * Qp + c] += acc[mi][ni][j]; // (this lane alone owns the entry)
+                    else Gpart[(((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * 32 + rr) * Qp + c] = acc[mi][ni][j];
+                }
             }
         }
     if (sums) {
@@ -242,13 +278,30 @@ __global__ __launch_bounds__(512, 1) void k_bwd_f64(const double *__restrict__ V
             double v = rs[mi];
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (q == 0) unsafeAtomicAdd(&G[(int64_t)(r0 + 16 * mi + li) * Qp + cconst], v);
+            if (q == 0) {
+                const int rr = 16 * mi + li;
+                if (gridDim.z == 1) G[(int64_t)(r0 + rr) * Qp + cconst] += v;
+                else Gpart[(((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * 32 + rr) * Qp + cconst] = v;
+            }
         }
     }
 }
 
-void launch_bwd_f64(const DevProblem &P, const double *V, const int *groups, int ngroups, double *G, hipStream_t st) {
-    const unsigned gx = (unsigned)((P.Qf + 1023) / 1024 > 0 ? (P.Qf + 1023) / 1024 : 1), gy = (unsigned)ngroups;
+// G[r][c] += the nsplit chunk parts of the entry in ascending chunk order; grid = (listed rows, ceil(Qp / 256))
+__global__ __launch_bounds__(256) void k_bwd_f64_reduce(const double *__restrict__ Gpart, const int *__restrict__ groups, int64_t Qp, int64_t Qf,
+                                                        int64_t cconst, int nsplit, double *__restrict__ G) {
+    const int64_t c = (int64_t)blockIdx.y * 256 + threadIdx.x;
+    if (c >= Qp || (c >= Qf && c != cconst)) return;
+    const int64_t rr = blockIdx.x, nrows = gridDim.x;
+    double *dst = G + ((int64_t)groups[rr >> 5] * 32 + (rr & 31)) * Qp + c;
+    double s = *dst;
+    for (int z = 0; z < nsplit; ++z) s += Gpart[((int64_t)z * nrows + rr) * Qp + c];
+    *dst = s;
+}
+
+// split of the samples over the workgroups of a backward launch with `ngroups` row groups
+static void bwd_f64_split(const DevProblem &P, int ngroups, unsigned *gx_out, int64_t *nsplit_out, int64_t *kchunk_out) {
+    const unsigned gx = (unsigned)((P.Qf + 1023) / 1024 > 0 ? (P.Qf + 1023) / 1024 : 1), gy = (unsigned)(ngroups > 0 ? ngroups : 1);
     // one 8-wave workgroup per CU at a time: about two rounds of workgroups over the 256 CUs, in whole 1024-sample chunks
     int64_t nsplit = (512 + (int64_t)gx * gy - 1) / ((int64_t)gx * gy);
     const int64_t maxsplit = P.Kp / 2048 > 0 ? P.Kp / 2048 : 1;
@@ -257,9 +310,35 @@ void launch_bwd_f64(const DevProblem &P, const double *V, const int *groups, int
     int64_t kchunk = (P.Kp + nsplit - 1) / nsplit;
     kchunk = (kchunk + 63) / 64 * 64;
     nsplit = (P.Kp + kchunk - 1) / kchunk;
-    dim3 grid(gx, gy, (unsigned)nsplit);
+    *gx_out = gx;
+    *nsplit_out = nsplit;
+    *kchunk_out = kchunk;
+}
+
+// bytes of the workspace `ws` of launch_fwd_f64 / launch_bwd_f64 for launches of up to `rows` rows (a multiple of 32): the larger of the
+// forward's parts of f ([row][Kp / 512], the group list padded to 4) and the backward's chunk parts of G for any number of listed groups
+size_t f64_reduce_ws_bytes(const DevProblem &P, int64_t rows) {
+    const int64_t ng_max = rows / 32 > 0 ? rows / 32 : 1;
+    size_t bytes = sizeof(double) * (size_t)((ng_max + 3) / 4 * 4 * 32) * (size_t)(P.Kp / (128 * F64_FWD_WAVES));
+    for (int64_t ng = 1; ng <= ng_max; ++ng) {
+        unsigned gx;
+        int64_t nsplit, kchunk;
+        bwd_f64_split(P, (int)ng, &gx, &nsplit, &kchunk);
+        if (nsplit > 1) bytes = std::max(bytes, sizeof(double) * (size_t)nsplit * (size_t)ng * 32 * (size_t)P.Qp);
+    }
+    return bytes;
+}
+
+void launch_bwd_f64(const DevProblem &P, const double *V, const int *groups, int ngroups, double *G, double *ws, hipStream_t st) {
+    unsigned gx;
+    int64_t nsplit, kchunk;
+    bwd_f64_split(P, ngroups, &gx, &nsplit, &kchunk);
+    dim3 grid(gx, (unsigned)ngroups, (unsigned)nsplit);
     const int64_t Qc = (P.Qfp + 255) / 256 * 256;
-    hipLaunchKernelGGL(k_bwd_f64, grid, dim3(512), 0, st, V, P.Xtb, groups, P.Qp, P.Qf, Qc, P.cconst, P.Kp, kchunk, G);
+    hipLaunchKernelGGL(k_bwd_f64, grid, dim3(512), 0, st, V, P.Xtb, groups, P.Qp, P.Qf, Qc, P.cconst, P.Kp, kchunk, G, ws);
+    if (nsplit > 1)
+        hipLaunchKernelGGL(k_bwd_f64_reduce, dim3((unsigned)ngroups * 32, (unsigned)((P.Qp + 255) / 256)), dim3(256), 0, st, ws, groups, P.Qp, P.Qf,
+                           P.cconst, (int)nsplit, G);
 }
 
 } // namespace gml

@@ -81,6 +81,21 @@ int gml_ensure_f64(gml_problem *p, int64_t vrows) {
         HIPCHK(hipMemsetAsync(p->dV, 0, sizeof(double) * vrows * d.Kp, p->st));
         p->dVrows = vrows;
     }
+    if (p->dRedRows != p->dVrows) { // the parts of f and G before their fixed-order reduction: sized with V, once per size of V
+        const size_t red = f64_reduce_ws_bytes(d, p->dVrows);
+        if (p->dRedBytes < red) {
+            if (p->dRed) (void)dev_free(p->dRed);
+            p->dRed = nullptr;
+            p->dRedBytes = 0;
+            p->dRedRows = 0;
+            HIPCHK(dev_mem_info(&freeb, &totalb));
+            if ((double)red > 0.9 * (double)freeb)
+                return fail(GML_ENOMEM, "FP64 reduction workspace of %.2f GB does not fit: use precision i8x", (double)red / 1e9);
+            HIPCHK(dev_malloc(&p->dRed, red));
+            p->dRedBytes = red;
+        }
+        p->dRedRows = p->dVrows;
+    }
     return GML_OK;
 }
 
@@ -161,9 +176,9 @@ static int launch_pass(gml_problem *p, int64_t Rp, int ngroups, int npad, int fo
     if (!hv) HIPCHK(hipMemsetAsync(p->dF, 0, sizeof(double) * Rp, st));
     if (want_grad) HIPCHK(hipMemsetAsync(p->dG, 0, sizeof(double) * Rp * p->d.Qp, st));
     if (ev) HIPCHK(hipEventRecord(ev[0], st));
-    launch_fwd_f64(p->d, p->dTheta, p->dRowcol, p->dGroups, npad, hv ? form + 4 : form, p->dV, p->dF, st); // (hv: V <- h (x . p), in place)
+    launch_fwd_f64(p->d, p->dTheta, p->dRowcol, p->dGroups, npad, hv ? form + 4 : form, p->dV, p->dF, p->dRed, st); // (hv: V <- h (x . p), in place)
     if (ev) HIPCHK(hipEventRecord(ev[1], st));
-    if (want_grad) launch_bwd_f64(p->d, p->dV, p->dGroups, ngroups, p->dG, st);
+    if (want_grad) launch_bwd_f64(p->d, p->dV, p->dGroups, ngroups, p->dG, p->dRed, st);
     if (ev) HIPCHK(hipEventRecord(ev[2], st));
     HIPCHK(hipGetLastError());
     return GML_OK;

@@ -210,12 +210,10 @@ template <typename T> int64_t pack_spins_t(const HistView &h, int64_t i0, int64_
 
 template <typename T> int64_t pack_counts_t(const HistView &h, double *counts, double *Msum, const ParallelFor &pf) {
     const T *cb = static_cast<const T *>(h.counts);
-    const int64_t blk = 65536, nb = (h.K + blk - 1) / blk;
-    std::vector<double> part((size_t)nb, 0.0);
+    const int64_t blk = kSumBlock, nb = (h.K + blk - 1) / blk;
     std::atomic<int64_t> bad(-1);
     pf(nb, [&](int64_t b) {
         const int64_t k1 = std::min(h.K, (b + 1) * blk);
-        double s = 0;
         for (int64_t k = b * blk; k < k1; ++k) {
             const double c = cb ? Elem<T>::num(cb[k * h.counts_stride]) : 1.0;
             counts[k] = c;
@@ -224,17 +222,29 @@ template <typename T> int64_t pack_counts_t(const HistView &h, double *counts, d
                 while ((cur < 0 || k < cur) && !bad.compare_exchange_weak(cur, k)) {
                 }
             }
-            s += c;
         }
-        part[(size_t)b] = s;
     });
-    double M = 0;
-    for (double s : part) M += s; // fixed order: M does not depend on the thread count
-    *Msum = M;
+    *Msum = sum_counts(counts, h.K, pf);
     return bad.load();
 }
 
 } // namespace
+
+// M, the sum of the counts, in its ONE defined order (include/gml.h): blocks of kSumBlock counts summed left to right, then the partial
+// sums added left to right.  The blocks run on the pool; the order, and with it every bit of M, does not depend on the thread count.
+double sum_counts(const double *counts, int64_t K, const ParallelFor &pf) {
+    const int64_t nb = (K + kSumBlock - 1) / kSumBlock;
+    std::vector<double> part((size_t)std::max<int64_t>(nb, 0), 0.0);
+    pf(nb, [&](int64_t b) {
+        const int64_t k1 = std::min(K, (b + 1) * kSumBlock);
+        double s = 0;
+        for (int64_t k = b * kSumBlock; k < k1; ++k) s += counts ? counts[k] : 1.0;
+        part[(size_t)b] = s;
+    });
+    double M = 0;
+    for (double s : part) M += s;
+    return M;
+}
 
 int64_t pack_spins(const HistView &h, int64_t i0, int64_t i1, int64_t wpr, uint32_t *out, const ParallelFor &pf) {
     switch (h.dtype) {

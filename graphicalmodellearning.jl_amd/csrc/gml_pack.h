@@ -24,7 +24,11 @@ HistView hist_view(const void *samples, int dtype, int64_t K, int64_t n, int64_t
 
 typedef std::function<void(int64_t, const std::function<void(int64_t)> &)> ParallelFor;
 
-// counts -> double [K] (finite, >= 0), *Msum = their sum.  Returns the first offending configuration, or -1.
+// The sum of K counts (NULL: all ones) in the one order that defines a handle's M on every creation route: blocks of kSumBlock counts
+// summed left to right, then the partial sums added left to right (include/gml.h, next to gml_pack_histogram).
+constexpr int64_t kSumBlock = 65536;
+double sum_counts(const double *counts, int64_t K, const ParallelFor &pf);
+// counts -> double [K] (finite, >= 0), *Msum = their sum (sum_counts).  Returns the first offending configuration, or -1.
 int64_t pack_counts(const HistView &h, double *counts, double *Msum, const ParallelFor &pf);
 // Sign words of the spins [i0, i1): out[(i - i0) * wpr + w], bit j of word w <-> configuration 32 w + j, set <=> -1;
 // all wpr words of every row are written (zero beyond K).  Returns the smallest configuration index that holds an

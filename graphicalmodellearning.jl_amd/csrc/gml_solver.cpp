@@ -760,10 +760,10 @@ int Solver::pass_f64(const PassArgs &q, const std::vector<int> &rows, PassRaw &r
     int *dctl = reinterpret_cast<int *>(dPass);
     HIPCHK(stg.h2d(dctl, ctl.data(), sizeof(int) * (Rp + ng4)));
     HIPCHK(hipMemsetAsync(dFs, 0, sizeof(double) * Rp, st));
-    launch_fwd_f64(d, q.src, dctl, dctl + Rp, ng4, formulation, p->dV, dFs, st);
+    launch_fwd_f64(d, q.src, dctl, dctl + Rp, ng4, formulation, p->dV, dFs, p->dRed, st);
     if (q.want_grad) {
         HIPCHK(hipMemsetAsync(Gs, 0, sizeof(double) * nd, st));
-        launch_bwd_f64(d, p->dV, dctl + Rp, ng, Gs, st);
+        launch_bwd_f64(d, p->dV, dctl + Rp, ng, Gs, p->dRed, st);
         RCCHK(upload_rows(rows, dRowsP));
         launch_copy_rows(dRowsP, (int)n, Qp, Gs, q.dst, nullptr, nullptr, st);
         if (formulation == GML_LOGRISE) launch_scale_rows_inv(dRowsP, (int)n, dFs, Qp, q.dst, st);

@@ -21,8 +21,9 @@ extern double g_hv_sparse_ratio;
 extern std::atomic<long long> g_hv_sparse_calls; // products taken entry by entry so far (all solves of the process)
 // experiment knobs (gml_test_tune; 0 = the built-in rule): what scripts/gpu_tune_*.py sweep, not an interface.  Tests and the benchmark
 // address the knobs by number, so an index never moves: 3 belonged to an experiment that was removed and stays reserved (unused)
-enum { GML_TUNE_KH_BASE = 0, GML_TUNE_FACE_ROUNDS = 1 /* value - 1 = rounds */, GML_TUNE_HESS_WGS = 2, GML_TUNE_NO_ZERO_SHORTCUT = 4 /* 1: the first pass runs its GEMM like any other */, GML_TUNE_NO_ZEROCOPY = 5 /* 1: results and row lists through device arrays and copies, as on handles too large for the pinned arena */, GML_TUNE_NO_COMPACT = 6 /* 1: the forward GEMMs of objective passes sweep all columns, always (A/B of the column compaction) */, GML_TUNE_BENCH_COMPACT = 7 /* 1: the timing hooks gml_bench_pass* compact too (they sweep all columns by default: the bench headline prices the dense contraction) */, GML_TUNE_SOLVER_COMPACT = 8 /* 1: gml_learn's own passes try the compaction whatever the column count.  By default they do from 4 096 statistics columns on (multi-body problems, thousands of spins: config 5 at c = 1.2 3.5 -> 2.2 s): measured (profiles/r6_compact_ab.txt) -- with the 1 024 columns of the headline problem a node's optimum keeps ~100 noise-level coefficients, a tile's 32 rows cover every column after the third pass: no gain, 1 - 5 % overhead */, GML_TUNE_NO_PAIRS = 9 /* 1: the forward sweep of precision i8w runs dense on plain digit planes in every tile, as it does where a column pair leaves the range of seven digits (gml_i8_pairs.h): the same result bits, so a test can hold the two paths against each other */, GML_TUNE_HESS_BLK_WGS = 10 /* workgroups the k-split of the blocked Hessian kernel aims at (0: 4096), as GML_TUNE_HESS_WGS for the one-workgroup kernel: tests reach long chunks at small shapes */, GML_NTUNE = 16 };
+enum { GML_TUNE_KH_BASE = 0, GML_TUNE_FACE_ROUNDS = 1 /* value - 1 = rounds */, GML_TUNE_HESS_WGS = 2, GML_TUNE_NO_ZERO_SHORTCUT = 4 /* 1: the first pass runs its GEMM like any other */, GML_TUNE_NO_ZEROCOPY = 5 /* 1: results and row lists through device arrays and copies, as on handles too large for the pinned arena */, GML_TUNE_NO_COMPACT = 6 /* 1: the forward GEMMs of objective passes sweep all columns, always (A/B of the column compaction) */, GML_TUNE_BENCH_COMPACT = 7 /* 1: the timing hooks gml_bench_pass* compact too (they sweep all columns by default: the bench headline prices the dense contraction) */, GML_TUNE_SOLVER_COMPACT = 8 /* 1: gml_learn's own passes try the compaction whatever the column count.  By default they do from 4 096 statistics columns on (multi-body problems, thousands of spins: config 5 at c = 1.2 3.5 -> 2.2 s): measured (profiles/r6_compact_ab.txt) -- with the 1 024 columns of the headline problem a node's optimum keeps ~100 noise-level coefficients, a tile's 32 rows cover every column after the third pass: no gain, 1 - 5 % overhead */, GML_TUNE_NO_PAIRS = 9 /* 1: the forward sweep of precision i8w runs dense on plain digit planes in every tile, as it does where a column pair leaves the range of seven digits (gml_i8_pairs.h): the same result bits, so a test can hold the two paths against each other */, GML_TUNE_HESS_BLK_WGS = 10 /* workgroups the k-split of the blocked Hessian kernel aims at (0: 4096), as GML_TUNE_HESS_WGS for the one-workgroup kernel: tests reach long chunks at small shapes */, GML_TUNE_STAGE_SPINS = 11 /* > 0: fill_sign_bits (gml_ingest.cpp) stages at most this many spins per chunk of its pinned pipeline instead of what the stage holds, and nothing else changes: tests reach many chunks, and chunks of fewer than 32 spins, at small shapes */, GML_NTUNE = 16 };
 extern double g_tune[GML_NTUNE];
+extern std::atomic<long long> g_fill_chunks; // (test hook) stages the last fill_sign_bits of the process went through (gml_ingest.cpp)
 
 // (test hook, gml_testhooks.cpp: gml_test_traj_*) the record of a solve's outer iterations: what the host logic of gml_solver.cpp decided,
 // step by step, for tests/test_gpu_solver_trajectory.py.  Off by default; while it is armed a solve appends one TrajIter per outer iteration

@@ -25,6 +25,7 @@ std::atomic<long long> g_hv_sparse_calls{0}; // (every part of a gml_multi_learn
 int g_term_chains_tile = 0;                   // 0: the rule of term_chains_tile (gml_term_chains.hip)
 int g_cond_split = 1;                         // the conditional chains' constant part: 0 never, 1 by the host's rule, 2 always
 int g_exact_chunk_bits = 0;                   // the exact enumeration's chunk bits: 0 = min(component size, kExactChunkBits)
+std::atomic<long long> g_fill_chunks{0};      // chunks the last fill_sign_bits staged (gml_test_fill_chunks)
 double g_tune[GML_NTUNE] = {};            // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
 // the kernel instances the int8-limb launchers have run (gml_i8.h: kI8InstBits)
 static std::atomic<uint64_t> g_i8_inst[(kI8InstBits + 63) / 64];
@@ -134,6 +135,30 @@ extern "C" int gml_test_stream_idle(gml_problem *p) {
     if (hipStreamQuery(p->st) == hipSuccess) return 1;
     (void)hipGetLastError(); // (hipErrorNotReady is no failure of the caller's next HIP call)
     return 0;
+}
+// Test hook (not part of include/gml.h): the number of stages the last fill_sign_bits of the process uploaded its sign bits in (the
+// host-packer and packed creation routes; a refused fill counts the chunks before the bad one)
+extern "C" long long gml_test_fill_chunks(void) { return g_fill_chunks.load(); }
+// Test hook (not part of include/gml.h): the weights of a handle as every creation route leaves them -- w [Kp] from HBM (copied on the
+// handle's stream), summary [4] = M, wmax, wuni, counts_int (1.0 / 0.0) and wblk [Kp / 512] from the host side.  A NULL output is
+// skipped.  Read only: copies; launches nothing.  tests/test_gpu_ingest_state.py.
+extern "C" int gml_test_weight_state(gml_problem *p, double *w, double *summary, double *wblk) {
+    if (!p) return fail(GML_EINVAL, "NULL argument");
+    if (w) {
+        if (!p->d.w) return fail(GML_EINVAL, "the handle holds no weights");
+        HIPCHK(hipSetDevice(p->device));
+        HIPCHK(hipMemcpyAsync(w, p->d.w, sizeof(double) * (size_t)p->d.Kp, hipMemcpyDeviceToHost, p->st));
+        HIPCHK(hipStreamSynchronize(p->st));
+    }
+    if (summary) {
+        const double v[4] = {p->M, p->d.wmax, p->d.wuni, p->counts_int ? 1.0 : 0.0};
+        std::memcpy(summary, v, sizeof v);
+    }
+    if (wblk) {
+        if ((int64_t)p->wblk.size() != p->d.Kp / 512) return fail(GML_EINVAL, "wblk holds %zu blocks, not Kp / 512", p->wblk.size());
+        std::memcpy(wblk, p->wblk.data(), sizeof(double) * p->wblk.size());
+    }
+    return GML_OK;
 }
 // A handle that holds sizes only -- no device, no samples -- for the tests of argument checks that run before any device work
 // (tests/test_host_sandwich.py).  Release it with gml_problem_destroy.

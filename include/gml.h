@@ -185,6 +185,12 @@ int gml_problem_create_device_convert(const void *samples, int dtype, int64_t K,
  *   gml_problem_create_packed   handle from the packed form
  *   gml_problem_get_sign_bits   the packed form of a handle's samples ([n][gml_packed_words(K)] dwords, host pointer),
  *                               e.g. of a handle sampled on the device
+ * M has ONE definition on every route that takes counts (gml_problem_create, _create_device_convert, _create_spins, _create_packed,
+ * gml_pack_histogram, gml_multi_create): the counts are summed left to right in blocks of 65 536 configurations, and the partial
+ * sums are then added left to right.  Integer counts sum exactly in any order; for fractional counts this order is what makes
+ * gml_problem_create_packed of gml_pack_histogram's output the handle of gml_problem_create, weight for weight (w_k = counts_k / M).
+ * Refusals follow one precedence on all of these routes: the argument checks, the first count that is negative or not finite, a
+ * zero sum of counts, then the first configuration (smallest index over all spins) that holds an entry other than +-1.
  */
 int64_t gml_packed_words(int64_t K);
 int gml_pack_histogram(const void *samples, int dtype, int64_t K, int64_t n, int64_t ld, int col_major,

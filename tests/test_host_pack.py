@@ -8,13 +8,7 @@ import gml_amd as gml
 from gml_amd import _lib
 
 
-def numpy_pack(spins):
-    """spins K x n in {-1,+1} -> [n][round_up(K,1024)/32] uint32"""
-    K, n = spins.shape
-    Kp = (K + 1023) // 1024 * 1024
-    neg = np.zeros((n, Kp), dtype=np.uint8)
-    neg[:, :K] = (spins.T < 0)
-    return np.packbits(neg.reshape(n, Kp // 32, 32), axis=2, bitorder="little").view(np.uint32).reshape(n, Kp // 32)
+from _ingest_reference import numpy_pack  # noqa: E402,F401  (the statement of the packed form; other test files import it from here)
 
 
 def make_hist(K, n, dtype, order, seed=0):
