@@ -13,7 +13,8 @@ from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, 
 from .inference import (ConditionalMeans, Imputation, PredictiveCheck, conditional_means, conditional_sample, impute,  # noqa: F401
                         impute_sample, predictive_check)
 from .learn import learn  # noqa: F401
-from .likelihood import AIS, Exact, LogLikelihood, LogPartition, exact_moments, log_likelihood, log_partition  # noqa: F401
+from .likelihood import (AIS, Exact, LogLikelihood, LogPartition, exact_moments, log_likelihood, log_partition,  # noqa: F401
+                         observed_log_likelihood)
 from .missing import EMStep, ImputationEM, MissingDataResult, learn_missing  # noqa: F401
 from .path import PathResult, learn_path  # noqa: F401
 from .sampling import GMSampler, Gibbs, Glauber, GlauberChains, GlauberTermChains, TemperedTermChains, sample  # noqa: F401
@@ -24,4 +25,4 @@ __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multi
            "structure_from_rows", "structure_from_keys", "learn_path", "PathResult", "AIS", "log_partition", "log_likelihood", "LogPartition",
            "LogLikelihood", "conditional_sample", "conditional_means", "predictive_check", "ConditionalMeans", "PredictiveCheck",
            "impute", "impute_sample", "Imputation", "learn_missing", "ImputationEM", "EMStep", "MissingDataResult", "Exact",
-           "exact_moments"]
+           "exact_moments", "observed_log_likelihood"]

@@ -98,6 +98,8 @@ def lib():
     L.gml_conditional_means.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
     L.gml_problem_create_mcmc_terms_masked.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, i32, i64, i64, C.POINTER(p)]
     L.gml_conditional_means_masked.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
+    L.gml_conditional_exact.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
+    L.gml_conditional_exact_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_problem_create_sampled_hist.argtypes =[p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -809,6 +811,37 @@ def conditional_chains_masked(terms, n, evidence, mask, replicas=1, samples_per_
     n0, n1 = _node_range(node_range, n)
     check(lib().gml_problem_create_mcmc_terms_masked(*common, int(order), n0, n1, C.byref(h)))
     return Problem._from_handle(h, order)
+
+
+def conditional_exact(terms, n, evidence, hidden, *, means=True, log_w=True, log_p=True):
+    """gml_conditional_exact on a term list as term_arrays takes it: evidence an open Problem, hidden the 0-BASED hidden spins, the same
+    in every row (at most 24).  Returns (means float64 [H, K], the hidden spins ascending; log_w [K]; log_p [K]), None for what was
+    not asked for: exact conditional means, log sum_{s_H} exp E and the conditional log-probability of the values the evidence holds on
+    the hidden spins, by enumeration on the evidence's device."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    mask = np.zeros(max(int(n), 0), dtype=np.uint8)
+    hidden = np.asarray(hidden, dtype=np.int64).ravel()
+    if len(hidden) and (hidden.min() < 0 or hidden.max() >= n):
+        raise GMLError(GML_EINVAL, f"a hidden spin lies outside [0, {int(n)})")
+    mask[hidden] = 1
+    m = np.zeros((int(mask.sum()), evidence.K)) if means else None
+    lw = np.zeros(evidence.K) if log_w else None
+    lp = np.zeros(evidence.K) if log_p else None
+    check(lib().gml_conditional_exact(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, _ptr(mask), _ptr(m), _ptr(lw), _ptr(lp)))
+    return m, lw, lp
+
+
+def conditional_exact_masked(terms, n, evidence, mask, *, means=True, log_w=True, log_p=True):
+    """gml_conditional_exact_masked: evidence and mask two open Problems of the same n, K and device; a -1 in row k of the mask hides that
+    spin in row k of the evidence (at most 24 per row).  Returns (means float64 [n, K], observed entries holding the evidence value;
+    log_w [K]; log_p [K]), None for what was not asked for."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    m = np.zeros((max(int(n), 0), evidence.K)) if means else None
+    lw = np.zeros(evidence.K) if log_w else None
+    lp = np.zeros(evidence.K) if log_p else None
+    check(lib().gml_conditional_exact_masked(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, mask._h, _ptr(m), _ptr(lw),
+                                             _ptr(lp)))
+    return m, lw, lp
 
 
 def moments(samples_or_problem, terms=None, raw=False, device=0):

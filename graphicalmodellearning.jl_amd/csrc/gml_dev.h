@@ -294,6 +294,40 @@ struct ExactPlan {
 };
 void launch_exact(const ExactPlan &P, int G, double *dres, hipStream_t st);
 
+// Exact conditional inference, one workgroup per row (gml_cond_exact.hip).  A plan is one hidden set: h hidden spins hid [h] (ascending;
+// local bit j <-> hid[j]), c chunk bits.  The model's terms sorted by their hidden part (stable): w [T], vis [T][S] the visible spins of
+// every term (kCondNoSpin = unused slot).  Row phase: items [item_off[it], item_off[it + 1]) of at most 1024 terms; item_dst >= 0 is the
+// coefficient the item alone makes, item_dst < 0 the partial sum ~item_dst; the hidden parts of several items add the partial sums
+// [ms_off[s], ms_off[s + 1]) into coefficient ms_dst[s].  Chunk phase: the nc coefficients lie in the order of their low (chunk)
+// masks, chi [nc] their high parts; low mask s of ns takes the coefficients [run_off[s], run_off[s + 1]) into the padded slot
+// run_dst[s].  A job is (plan, row); the results of row k go to log_w[k], log_p[k] and means[j ldm + k], j < h (any of them NULL).
+constexpr int kCondMaxHidden = 24;                       // hidden spins of a row
+constexpr int kCondMaxHigh = 12;                         // of them above the chunk: 4096 chunks per row
+constexpr int kCondCoefs = 1024;                         // distinct hidden parts of a row's terms (the LDS array of the coefficients)
+constexpr int kCondParts = 1024;                         // partial sums of one row's coefficients (they lie in the transform's vector)
+constexpr int kCondMaxTermSpins = 8;                     // distinct spins of a term
+constexpr int64_t kCondMaxN = 16384;                     // spins: the row's sign bits lie in 512 words of LDS
+constexpr unsigned short kCondNoSpin = 16384;            // an unused slot of vis: bit kCondMaxN of the row's bits is always 0
+// where the calling thread's last call of either entry point spent its time (gml_testhooks.cpp: gml_test_cond_exact_times): seconds on
+// the host before the downloads without the slabs (checks, the mask's bits, planning), seconds in the slabs (upload, launch, drain),
+// seconds in all.  Per thread: concurrent calls from several host threads do not share it.
+extern thread_local double g_cond_exact_times[3];
+struct CondExactPlan {
+    const double *w;
+    const unsigned short *vis;
+    const int *item_off, *item_dst, *ms_off, *ms_dst;
+    const unsigned short *chi;
+    const int *run_off, *run_dst;
+    int hid[kCondMaxHidden];
+    int S, ni, nm, nc, ns, h, c;
+};
+struct CondExactJob {
+    long long row;
+    int plan, pad_;
+};
+void launch_cond_exact(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
+                       double *dmeans, int64_t ldm, double *dlog_w, double *dlog_p, hipStream_t st);
+
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].
 // faces: the orthant-face re-solves inside the kernel (working-set columns F [R][cap], iterates X [R][Qp] and their column kinds,

@@ -15,40 +15,10 @@
 // result is a function of the model alone.
 #include "../../include/gml.h"
 #include "gml_dev.h"
+#include "gml_exact_wht.h"
 #include "gml_wg.h"
 
 namespace gml {
-
-// the transform's vector in LDS: element i at i + (i >> 4), one pad double per 16.  With i = a + 16 b + 256 d (4 bits each) that is
-// a + 17 b + 272 d, and the three radix-16 passes read, per ds_read_b64 and half wave:
-//   pass A (a in registers, lanes = b, d): stride 34 dwords, 32 distinct even banks -- conflict-free;
-//   pass B (b in registers, lanes = a, d): 16 consecutive doubles and 16 more 544 = 32 (mod 64) dwords on -- conflict-free;
-//   pass C (d in registers, lanes = a, b): 16 consecutive doubles and 16 more 34 dwords on -- the last lane meets the first on one
-//   bank pair (3 LDS cycles instead of 2).
-__device__ __forceinline__ int exact_pad(int i) { return i + (i >> 4); }
-
-// 16-point Walsh-Hadamard transform in registers: x[k | s] takes the difference (a set bit is a spin of -1)
-__device__ __forceinline__ void wht16(double (&x)[16]) {
-#pragma unroll
-    for (int s = 1; s < 16; s <<= 1) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (k & s) continue;
-            const double a = x[k], b = x[k | s];
-            x[k] = a + b;
-            x[k | s] = a - b;
-        }
-    }
-}
-
-__device__ __forceinline__ void exact_load(const double *v, int base, int stride, double (&x)[16]) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = v[base + stride * k];
-}
-__device__ __forceinline__ void exact_store(double *v, int base, int stride, const double (&x)[16]) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[base + stride * k] = x[k];
-}
 
 __global__ __launch_bounds__(256) void k_exact_enumerate(const ExactPlan P) {
     __shared__ double v[kExactVec], part[kExactParts], red[4];

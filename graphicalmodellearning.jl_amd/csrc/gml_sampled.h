@@ -1,5 +1,6 @@
 // What the creators of sampled handles share on the host: gml_sampled.cpp (exact block sampler, k_glauber, the int8 chains, moments,
-// gml_model_exact) and gml_chains_host.cpp (the term-list chain family).  Internal; not part of the C ABI.
+// gml_model_exact), gml_chains_host.cpp (the term-list chain family) and gml_cond_exact.cpp (exact conditional inference).  Internal;
+// not part of the C ABI.
 #pragma once
 #include "gml_internal.h"
 

@@ -24,6 +24,7 @@ double g_hv_sparse_ratio = 0.3; // (config 5 at the default regulariser: 25.6 s 
 std::atomic<long long> g_hv_sparse_calls{0}; // (every part of a gml_multi_learn counts from its own host thread)
 int g_term_chains_tile = 0;                   // 0: the rule of term_chains_tile (gml_term_chains.hip)
 int g_cond_split = 1;                         // the conditional chains' constant part: 0 never, 1 by the host's rule, 2 always
+thread_local double g_cond_exact_times[3] = {0, 0, 0}; // the time split of this thread's last gml_conditional_exact[_masked] call
 int g_exact_chunk_bits = 0;                   // the exact enumeration's chunk bits: 0 = min(component size, kExactChunkBits)
 std::atomic<long long> g_fill_chunks{0};      // chunks the last fill_sign_bits staged (gml_test_fill_chunks)
 double g_tune[GML_NTUNE] = {};            // experiment knobs of the solver, 0 = the built-in rule (gml_solver.h)
@@ -106,6 +107,14 @@ extern "C" int gml_test_cond_split(int on) {
 }
 // the low "chunk" bits of the exact enumeration (gml_exact.hip): c = 1 .. 12 instead of min(component size, 12), 0 restores that
 // default; small values take tiny models through the multi-chunk and multi-group paths.  Returns the old value, -1 for another value
+// out [3] = the host, slab and total seconds of the calling thread's last call of gml_conditional_exact / gml_conditional_exact_masked
+// (gml_cond_exact.cpp; scripts/cond_exact_times.py reports the host's share from it)
+extern "C" int gml_test_cond_exact_times(double *out) {
+    if (!out) return -1;
+    for (int i = 0; i < 3; ++i) out[i] = g_cond_exact_times[i];
+    return 0;
+}
+
 extern "C" int gml_test_exact_chunk_bits(int c) {
     if (c < 0 || c > kExactChunkBits) return -1;
     const int old = g_exact_chunk_bits;

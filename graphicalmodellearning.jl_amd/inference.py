@@ -10,12 +10,18 @@ pseudo-likelihood nor an AIS likelihood gives.
 
 impute / impute_sample are the same two for data with holes, where every row lacks its own set of spins (0 in the histogram matrix):
 the hidden set is read per row from a second resident handle (gml_conditional_means_masked, gml_problem_create_mcmc_terms_masked).
-missing.learn_missing builds stochastic-imputation EM on them."""
+missing.learn_missing builds stochastic-imputation EM on them.
+
+With method=Exact() conditional_means, impute and predictive_check use no chain: every row's hidden spins are enumerated on the device
+(gml_conditional_exact, gml_conditional_exact_masked; at most 24 hidden spins per row, any n), with the model's weights as they are
+(the chains quantise them).  The exact path also gives what no chain can: log_p, the joint conditional log-probability of the values a
+row holds on its hidden spins, and log_w, from which likelihood.observed_log_likelihood scores data with holes."""
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from .likelihood import Exact
 from .sampling import GlauberTermChains, _problem_args, _term_list_args
 
 
@@ -23,23 +29,29 @@ from .sampling import GlauberTermChains, _problem_args, _term_list_args
 class ConditionalMeans:
     """means [K, H]: E[s_i | the visible spins of row k] for the hidden spins i (ascending), averaged over the replicas; stderr [K, H]:
     the standard deviation over replicas / sqrt(replicas), NaN for one replica; per_replica [replicas, K, H]; hidden: the H hidden spins,
-    1-based, ascending; counts [K]: the counts of the evidence rows."""
+    1-based, ascending; counts [K]: the counts of the evidence rows.  From method=Exact(): the exact means, stderr 0.0, per_replica
+    [1, K, H], and log_w [K] = log sum over the hidden spins of exp(E) (log P(visible spins of row k) = log_w[k] - log Z), log_p [K] =
+    log P(the values row k holds on the hidden spins | its visible spins); both None from the chains."""
     means: np.ndarray
     stderr: np.ndarray
     per_replica: np.ndarray
     hidden: list
     counts: np.ndarray
+    log_w: np.ndarray = None
+    log_p: np.ndarray = None
 
 
 @dataclass
 class PredictiveCheck:
     """Per hidden spin (1-based, ascending): accuracy, the count-weighted share of rows whose hidden value is sign(mean) (a mean of
     exactly 0 predicts +1), and log_loss, the count-weighted mean of -log p with p = (1 + s mean) / 2 the probability given to the
-    value s the data hold.  means: the ConditionalMeans behind them."""
+    value s the data hold.  means: the ConditionalMeans behind them.  joint_log_loss (method=Exact() only, else None): the
+    count-weighted mean of -log P(all held-out values of the row | its visible spins), the joint that the per-spin losses do not give."""
     hidden: list
     accuracy: np.ndarray
     log_loss: np.ndarray
     means: ConditionalMeans
+    joint_log_loss: float = None
 
 
 def _hidden_spins(hidden, n):
@@ -81,6 +93,17 @@ class _Evidence:
             self.p.close()
 
 
+def _exact_method(method, sampler, replicas, seed):
+    """method=None: the chains.  An Exact: no chain runs, so a sampler, replicas and a seed are refused rather than ignored."""
+    if method is None:
+        return None
+    if not isinstance(method, Exact):
+        raise ValueError(f"conditional inference takes method=None (chains) or an Exact, given {type(method).__name__}")
+    if sampler is not None or int(replicas) != 1 or int(seed) != 0:
+        raise ValueError("method=Exact() enumerates: it takes no sampler, replicas=1 and seed=0")
+    return method
+
+
 def _run(model, evidence, hidden, sampler, replicas, seed, means):
     sampler = _sampler(sampler)
     if int(replicas) < 1:
@@ -103,9 +126,23 @@ def conditional_sample(model, evidence, hidden, sampler=None, *, replicas=1, see
     return _run(model, evidence, hidden, sampler, replicas, seed, False)[0]
 
 
-def conditional_means(model, evidence, hidden, sampler=None, *, replicas=1, seed=0):
+def conditional_means(model, evidence, hidden, sampler=None, *, replicas=1, seed=0, method=None):
     """Rao-Blackwellised conditional means of the hidden spins given the visible spins of every evidence row; arguments as
-    conditional_sample.  No handle is made.  Returns a ConditionalMeans (columns: the hidden spins in ascending order)."""
+    conditional_sample.  No handle is made.  Returns a ConditionalMeans (columns: the hidden spins in ascending order).
+    method=Exact(): the exact means by enumeration of the hidden spins (at most method.max_hidden <= 24 of them), with log_w and log_p;
+    no sampler, replicas or seed then."""
+    if _exact_method(method, sampler, replicas, seed) is not None:
+        ev = _Evidence(evidence)
+        spins = _hidden_spins(hidden, ev.n)
+        if len(spins) > method.max_hidden:  # (refused before a handle is opened)
+            raise ValueError(f"{len(spins)} spins are hidden: more than max_hidden = {method.max_hidden}")
+        args = _term_list_args(model, _problem_args(model))
+        terms = args["terms"] if len(args["terms"]) else {(1,): 0.0}  # (a model without a term, as the chains take it)
+        with ev as p:
+            m, log_w, log_p = _lib.conditional_exact(terms, ev.n, p, np.asarray(spins) - 1)
+            counts = p.counts()
+        means = np.ascontiguousarray(m.T)
+        return ConditionalMeans(means, np.zeros_like(means), means[None].copy(), spins, counts, log_w, log_p)
     raw, spins, counts, K = _run(model, evidence, hidden, sampler, replicas, seed, True)
     R = int(replicas)
     per = np.ascontiguousarray(raw.reshape(len(spins), R, K).transpose(1, 2, 0))  # [H][r K + k] -> [r][k][a]
@@ -126,10 +163,9 @@ class Imputation:
     missing: np.ndarray
 
 
-def _missing_rows(samples):
-    """(values int8 [K', n] with +1 in place of a hole, missing bool [K', n]) of a K x (1+n) histogram matrix whose spin entries are in
-    {-1, 0, +1}, 0 = missing.  A row of count c becomes c consecutive rows: every original sample has its own holes to fill.  Counts that
-    are not positive integers and any other spin entry are refused."""
+def _parse_holes(samples):
+    """(counts [K], spins [K, n], missing bool [K, n]) of a K x (1+n) histogram matrix whose spin entries are in {-1, 0, +1}, 0 =
+    missing.  Counts that are not positive integers and any other spin entry are refused."""
     s = np.asarray(samples)
     if s.ndim != 2 or s.shape[1] < 2:
         raise ValueError("samples must be a K x (1+n) histogram matrix")
@@ -138,9 +174,22 @@ def _missing_rows(samples):
         raise ValueError("the counts of data with missing entries must be positive integers (a row of count c is expanded into c rows)")
     if not np.all((spins == -1) | (spins == 0) | (spins == 1)):
         raise ValueError("the spin entries of data with missing entries must be -1, +1 or 0 (0 = missing)")
-    rows = np.repeat(np.arange(s.shape[0]), counts.astype(np.int64))
-    missing = (spins == 0)[rows]
+    return counts, spins, spins == 0
+
+
+def _missing_rows(samples):
+    """(values int8 [K', n] with +1 in place of a hole, missing bool [K', n]) of a histogram matrix as _parse_holes takes it.  A row of
+    count c becomes c consecutive rows: every original sample has its own holes to fill."""
+    counts, spins, missing = _parse_holes(samples)
+    rows = np.repeat(np.arange(len(counts)), counts.astype(np.int64))
+    missing = missing[rows]
     return np.where(missing, 1, spins[rows]).astype(np.int8), missing
+
+
+def _check_holes(missing, max_hidden):
+    most = int(missing.sum(axis=1).max()) if missing.size else 0
+    if most > max_hidden:
+        raise ValueError(f"a row lacks {most} spins: more than max_hidden = {max_hidden}")
 
 
 def _mask_order(missing):
@@ -184,6 +233,17 @@ class _Holes:
                                               order=args.get("order", 2) if order is None else order)
 
 
+def _exact_holes(model, values, missing, device=0, means=True, log_w=True, log_p=True):
+    """_lib.conditional_exact_masked of `model` on data with holes (values int8 [K, n], missing bool [K, n]): (means [K, n], log_w [K],
+    log_p [K]) in the caller's row order, None for what was not asked for"""
+    with _Holes(values, missing, device=device) as holes:
+        args = _term_list_args(model, _problem_args(model))
+        terms = args["terms"] if len(args["terms"]) else {(1,): 0.0}
+        m, lw, lp = _lib.conditional_exact_masked(terms, holes.n, holes.evidence, holes.mask, means=means, log_w=log_w, log_p=log_p)
+        inv = holes.inverse
+    return (None if m is None else np.ascontiguousarray(m.T[inv]), None if lw is None else lw[inv], None if lp is None else lp[inv])
+
+
 def _impute_args(samples, sampler, replicas):
     sampler = _sampler(sampler)
     if int(replicas) < 1:
@@ -208,9 +268,16 @@ def impute_sample(model, samples, sampler=None, *, replicas=1, seed=0):
     return _lib.Problem(spins=states, order=order)
 
 
-def impute(model, samples, sampler=None, *, replicas=1, seed=0):
+def impute(model, samples, sampler=None, *, replicas=1, seed=0, method=None):
     """Rao-Blackwellised conditional means of the missing entries of `samples` (as impute_sample) given the observed entries of the
-    same row (gml_conditional_means_masked).  No handle is returned.  Returns an Imputation, its rows in the caller's order."""
+    same row (gml_conditional_means_masked).  No handle is returned.  Returns an Imputation, its rows in the caller's order.
+    method=Exact(): the exact means by enumeration of every row's missing spins (gml_conditional_exact_masked; at most
+    method.max_hidden <= 24 per row), stderr 0.0; no sampler, replicas or seed then."""
+    if _exact_method(method, sampler, replicas, seed) is not None:
+        values, missing = _missing_rows(samples)
+        _check_holes(missing, method.max_hidden)  # (refused before a handle is opened)
+        means = _exact_holes(model, values, missing, log_w=False, log_p=False)[0]
+        return Imputation(means, np.zeros_like(means), missing)
     sampler, (values, missing) = _impute_args(samples, sampler, replicas)
     with _Holes(values, missing) as holes:
         raw = holes.chains(model, sampler, replicas, seed, True)
@@ -223,18 +290,22 @@ def impute(model, samples, sampler=None, *, replicas=1, seed=0):
     return Imputation(per.mean(axis=0), stderr, missing)
 
 
-def predictive_check(model, data, hidden, sampler=None, *, replicas=1, seed=0):
+def predictive_check(model, data, hidden, sampler=None, *, replicas=1, seed=0, method=None):
     """Hide the spins `hidden` in every row of `data` (an open Problem or a histogram matrix), predict them from the others under
     `model`, and compare with the values the data hold.  Returns a PredictiveCheck.  It says how well each hidden spin is predicted
     from the rest under the model; with several hidden spins each is predicted with the others hidden too (their joint uncertainty is
-    averaged over), and it says nothing about spins that were never hidden."""
+    averaged over), and it says nothing about spins that were never hidden.  method=Exact(): exact means instead of chains, and
+    joint_log_loss, the loss of the joint prediction of a row's hidden spins."""
     ev = _Evidence(data)
-    _hidden_spins(hidden, ev.n)  # (refused before the data are opened)
+    spins = _hidden_spins(hidden, ev.n)  # (refused before the data are opened)
+    if _exact_method(method, sampler, replicas, seed) is not None and len(spins) > method.max_hidden:
+        raise ValueError(f"{len(spins)} spins are hidden: more than max_hidden = {method.max_hidden}")
     with ev as p:
-        cm = conditional_means(model, p, hidden, sampler, replicas=replicas, seed=seed)
+        cm = conditional_means(model, p, hidden, sampler, replicas=replicas, seed=seed, method=method)
         truth = p.spins()[:, np.asarray(cm.hidden) - 1].astype(np.float64)
     w = cm.counts / cm.counts.sum()
     predicted = np.where(cm.means >= 0.0, 1.0, -1.0)
     accuracy = w @ (predicted == truth)
     prob = np.maximum((1.0 + truth * cm.means) / 2.0, np.finfo(np.float64).tiny)
-    return PredictiveCheck(cm.hidden, accuracy, w @ (-np.log(prob)), cm)
+    joint = None if cm.log_p is None else float(-(w @ cm.log_p))
+    return PredictiveCheck(cm.hidden, accuracy, w @ (-np.log(prob)), cm, joint)

@@ -264,6 +264,97 @@ function conditional_means(terms::Dict, samples::Array{T,2}, hidden::AbstractVec
     end
 end
 
+# the term list of a Dict(key tuple (1-based spins) => weight) as the C ABI takes it: (keymat (stride x T) Int32, 0-based, -1 = unused;
+# weights; stride)
+function term_arrays(terms::Dict)
+    stride = max(1, maximum(length, keys(terms); init=1))
+    keymat = fill(Int32(-1), stride, length(terms))       # Julia (stride x T) == C row-major (T x stride)
+    weights = Vector{Float64}(undef, length(terms))
+    for (t, (key, w)) in enumerate(terms)
+        for (a, v) in enumerate(key)
+            keymat[a, t] = Int32(v - 1)
+        end
+        weights[t] = w
+    end
+    return keymat, weights, stride
+end
+
+"""
+    conditional_exact(terms::Dict, samples, hidden; device=0) -> means (K x H), log_w (K), log_p (K)
+
+Exact conditional inference (gml_conditional_exact, include/gml.h): the spins `hidden` (1-based, at most 24) of every row of the
+histogram `samples` (K x (1+n)) are enumerated on the device, no chain.  `means[k, a]` = E[s | the visible spins of row k] of the a-th
+hidden spin (ascending); `log_w[k]` = log sum over the hidden spins of exp(E), so log P(visible spins of row k) = log_w[k] - log Z;
+`log_p[k]` = log P(the values row k holds on the hidden spins | its visible spins).  The counts of `samples` play no part.
+Marshalling only.
+"""
+function conditional_exact(terms::Dict, samples::Array{T,2}, hidden::AbstractVector{<:Integer}; device::Integer=0) where T <: Real
+    s = T <: AbstractFloat ? convert(Array{Float64,2}, samples) : convert(Array{Int64,2}, samples)
+    dtype = eltype(s) == Float64 ? GML_F64 : GML_I64
+    K, n = size(s, 1), size(s, 2) - 1
+    all(i -> 1 <= i <= n, hidden) && !isempty(hidden) && allunique(hidden) ||
+        throw(ArgumentError("conditional_exact: hidden must name distinct spins in 1:$n"))
+    mask = zeros(UInt8, n)
+    mask[hidden] .= 1
+    keymat, weights, stride = term_arrays(terms)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:gml_problem_create, libgml), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Cint, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+               s, dtype, K, n, K, 1 #= column-major =#, 2, 0, n, device, handle)
+    rc == GML_OK || error("gml_problem_create: $(lasterr())")
+    try
+        means = Array{Float64}(undef, K, length(hidden))  # C row-major [H][K] == Julia (K x H)
+        log_w = Vector{Float64}(undef, K)
+        log_p = Vector{Float64}(undef, K)
+        rc = ccall((:gml_conditional_exact, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, handle[], mask, means, log_w, log_p)
+        rc == GML_OK || error("gml_conditional_exact: $(lasterr())")
+        return means, log_w, log_p
+    finally
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
+    end
+end
+
+"""
+    conditional_exact_masked(terms::Dict, samples; device=0) -> means (K x n), log_w (K), log_p (K)
+
+The same for data with holes (gml_conditional_exact_masked): a spin entry of `samples` (K x (1+n)) is -1, +1 or 0 = missing, at most 24
+missing per row, and every row's own missing spins are enumerated.  `means[k, i]` is the exact conditional mean where row k lacks spin
+i and the observed value where it does not; `log_w[k]` - log Z is the marginal log-likelihood of what row k observes.  Two handles
+are made and destroyed: the evidence (a hole holds +1, which plays no part) and the mask (-1 = missing).  Marshalling only.
+"""
+function conditional_exact_masked(terms::Dict, samples::Array{T,2}; device::Integer=0) where T <: Real
+    K, n = size(samples, 1), size(samples, 2) - 1
+    spins = samples[:, 2:end]
+    all(v -> v == -1 || v == 0 || v == 1, spins) || throw(ArgumentError("conditional_exact_masked: spin entries must be -1, +1 or 0"))
+    evidence = Int8.(ifelse.(spins .== 0, 1, spins))
+    holes = Int8.(ifelse.(spins .== 0, -1, 1))
+    keymat, weights, stride = term_arrays(terms)
+    he = Ref{Ptr{Cvoid}}(C_NULL)
+    hm = Ref{Ptr{Cvoid}}(C_NULL)
+    create(bytes, h) = ccall((:gml_problem_create_spins, libgml), Cint,
+                             (Ptr{Cdouble}, Ptr{Int8}, Int64, Int64, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+                             C_NULL, bytes, K, n, 2, 0, n, device, h)
+    rc = create(permutedims(evidence), he)                # (C row-major [K][n] bytes == Julia (n x K); counts NULL: all ones)
+    rc == GML_OK || error("gml_problem_create_spins: $(lasterr())")
+    try
+        rc = create(permutedims(holes), hm)
+        rc == GML_OK || error("gml_problem_create_spins: $(lasterr())")
+        means = Array{Float64}(undef, K, n)               # C row-major [n][K] == Julia (K x n)
+        log_w = Vector{Float64}(undef, K)
+        log_p = Vector{Float64}(undef, K)
+        rc = ccall((:gml_conditional_exact_masked, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, he[], hm[], means, log_w, log_p)
+        rc == GML_OK || error("gml_conditional_exact_masked: $(lasterr())")
+        return means, log_w, log_p
+    finally
+        hm[] == C_NULL || ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), hm[])
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), he[])
+    end
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

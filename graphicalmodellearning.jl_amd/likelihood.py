@@ -35,13 +35,17 @@ class AIS:
 
 
 class Exact:
-    """Exact enumeration on the device (gml_model_exact): every connected component of the model's term hypergraph has at most
-    `max_spins` spins, itself at most 40 (the library's limit; a component of sb spins costs one pass over its 2^sb states)."""
+    """Exact enumeration on the device.  For log Z and the model's moments (gml_model_exact): every connected component of the model's
+    term hypergraph has at most `max_spins` spins, itself at most 40 (the library's limit; a component of sb spins costs one pass over
+    its 2^sb states).  For conditional inference (gml_conditional_exact: conditional_means, impute, predictive_check,
+    observed_log_likelihood): every row hides at most `max_hidden` spins, itself at most 24 (a row of h hidden spins costs 2^h states)."""
 
-    def __init__(self, max_spins=40):
-        self.max_spins = int(max_spins)
+    def __init__(self, max_spins=40, max_hidden=24):
+        self.max_spins, self.max_hidden = int(max_spins), int(max_hidden)
         if not 1 <= self.max_spins <= 40:
             raise ValueError(f"max_spins must lie in [1, 40] (given {max_spins})")
+        if not 1 <= self.max_hidden <= 24:
+            raise ValueError(f"max_hidden must lie in [1, 24] (given {max_hidden})")
 
 
 @dataclass
@@ -128,6 +132,28 @@ def log_likelihood(data, model, method=None, *, log_z=None, seed=0, device=0):
         with _lib.Problem(data, device=device) as p:
             sums, M = p.term_moments(terms, raw=True), p.M
     data_term = float(np.dot(w, sums.astype(np.float64))) / M
+    if log_z is None:
+        log_z = log_partition(model, method, seed=seed, device=device)
+    lz, se = (log_z.log_z, log_z.stderr) if isinstance(log_z, LogPartition) else (float(log_z), float("nan"))
+    mean = data_term - lz
+    return LogLikelihood(mean, M * mean, data_term, lz, se)
+
+
+def observed_log_likelihood(data, model, method=None, *, log_z=None, seed=0, device=0):
+    """The log-likelihood of data with holes: `data` is a K x (1+n) histogram matrix whose spin entries are -1, +1 or 0 = missing, as
+    impute takes it (counts: positive integers), every row hiding at most 24 spins.  A row contributes log P(x_O), the marginal
+    probability of what it observes: log sum over its missing spins of exp(E), by enumeration on the device
+    (gml_conditional_exact_masked: exact, whatever `method` is), minus log Z.  log_z and method (an AIS, or an Exact whose max_hidden
+    also bounds the holes of a row) as in log_likelihood.  Returns a LogLikelihood whose data_term is the count-weighted mean of
+    log sum exp(E); on data without holes it equals log_likelihood."""
+    from . import inference  # (inference imports this module)
+
+    max_hidden = method.max_hidden if isinstance(method, Exact) else 24
+    counts, spins, missing = inference._parse_holes(data)
+    inference._check_holes(missing, max_hidden)  # (refused before a handle is opened)
+    _, log_w, _ = inference._exact_holes(model, np.where(missing, 1, spins).astype(np.int8), missing, device=device, means=False, log_p=False)
+    M = float(counts.sum())
+    data_term = float(np.dot(counts.astype(np.float64), log_w)) / M
     if log_z is None:
         log_z = log_partition(model, method, seed=seed, device=device)
     lz, se = (log_z.log_z, log_z.stderr) if isinstance(log_z, LogPartition) else (float(log_z), float("nan"))

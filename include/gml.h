@@ -482,6 +482,53 @@ int gml_conditional_means_masked(const int32_t *keys, int key_stride, const doub
                                  uint64_t seed, double *means /* [n][K * replicas], host */);
 
 /*
+ * gml_conditional_exact, gml_conditional_exact_masked -- exact conditional inference: every row's hidden spins are enumerated on the
+ * device, no chain.  The yardstick for the conditional chains above, and the only way to the joint conditional probability of held-out
+ * values and to the marginal likelihood of a partly observed row.  Any n <= 16384, at most 24 hidden spins per row.
+ * Model.  The term list with the conventions of gml_model_exact: 0-based spins, -1 = unused slot, a spin named twice cancels, a term of
+ *   weight zero joins nothing.  The weights are FP64 and NOT quantised (the chains quantise every spin's couplings to 2^-38 of its
+ *   largest).
+ * Definitions.  Row k of the evidence handle has a hidden set H_k of h_k spins and observed values x_O.  For a reduced term t,
+ *   hid(t) = t & H_k and sigma_{t,k} = prod_{j in t \ H_k} x_{k,j}.  E_k(s_H) = sum_t w_t sigma_{t,k} prod_{i in hid(t)} s_i, over ALL
+ *   terms: those with an empty hidden part and the empty key are the row's constant.
+ * Outputs, per row (host; any may be NULL, not all three).
+ *   log_w [K]: log sum_{s_H} exp(E_k(s_H)).  log P(x_O) = log_w[k] - log Z.  A row without a hidden spin gives E(row).
+ *   means: E[s_i | x_O] of the hidden spins.
+ *   log_p [K]: E_k(the values the evidence row holds on H_k) - log_w[k] = log P(x_H = held values | x_O).  Meaningful where the held
+ *     values are the truth (a predictive check); it plays no part otherwise.
+ * gml_conditional_exact: one hidden set for every row, hidden [n] of uint8 (non-zero = hidden), at least one; means is [H][K],
+ *   hidden-major, the hidden spins ascending -- the layout of gml_conditional_means with replicas = 1.
+ * gml_conditional_exact_masked: the hidden set of row k is the set bits of row k of the handle `mask` (as for
+ *   gml_conditional_means_masked); means is [n][K], an observed entry holding its evidence value +-1.0.  A row without holes is
+ *   legal.  The counts of the handles play no part in either.
+ * Determinism.  The result of a row is a pure function of the model, that row and that row's hidden set: the same bits on every call,
+ *   wherever the row sits, whatever the other rows are, on any grid.  Every sum has a fixed order -- the terms of one hidden part in
+ *   the caller's order, the coefficients of one chunk mask in ascending order of their hidden parts, the chunks in index order -- and no
+ *   accumulator takes more than 1024 summands serially.  A mask handle whose rows all equal one vector gives, bit for bit, what
+ *   gml_conditional_exact gives with that vector.
+ * Arithmetic.  That of gml_model_exact: FP64, running maxima (couplings of +-150 neither overflow nor underflow), the a-priori error
+ *   of every output about (12 + log2 T) 2^-53 sum_t |w_t| plus 1e-13.
+ * GML_EINVAL, before any device work, in this order: all three outputs NULL; NULL evidence; NULL hidden / mask; NULL keys or weights,
+ *   key_stride < 1, nterms < 0; n different from the evidence handle's; a mask handle whose n, K or device differs from the evidence
+ *   handle's; no hidden spin (gml_conditional_exact only); a non-finite weight or a spin outside [0, n).
+ * GML_EUNSUPPORTED, the limit named in gml_last_error, in this order: n > 16384; more than 24 hidden spins (the masked form names the
+ *   first such row; it reads the hidden sets from the device, so this one check of it follows the download of the mask's bits and
+ *   precedes every enumeration); a term of more than 8 distinct spins (of non-zero weight; in the masked form this one precedes the
+ *   download); more than 1024 distinct hidden parts hid(t) under one hidden set; more than 1024 partial sums under one hidden
+ *   set (the hidden parts of more than 1024 terms are summed in items of 1024: any model of up to 2^19 terms fits, and up to 2^20 where
+ *   they gather in one hidden part, as the visible-only terms of a dense model do).  For gml_conditional_exact all of these precede any device work.
+ * Cost.  Per row one pass over the T terms (the row's coefficients) and 2^h states in chunks of 4096; per distinct hidden set one
+ *   pass over the terms and a sort of them on the host.  Measured times in DESIGN 3.19.  No handle is made; every device buffer is
+ *   released on every path.
+ */
+int gml_conditional_exact(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
+                          const uint8_t *hidden /* [n], host */, double *means /* [H][K] or NULL */, double *log_w /* [K] or NULL */,
+                          double *log_p /* [K] or NULL */);
+int gml_conditional_exact_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                 gml_problem *evidence, gml_problem *mask, double *means /* [n][K] or NULL */,
+                                 double *log_w /* [K] or NULL */, double *log_p /* [K] or NULL */);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
