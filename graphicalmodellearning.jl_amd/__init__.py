@@ -10,11 +10,11 @@ from ._lib import (EXCLUDED, FREE, PENALISED, GMLConvergenceError, GMLError, Mul
 from .factor_graph import FactorGraph, matrix_to_terms, permutations, check_model_data  # noqa: F401
 from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, GMLMethod,  # noqa: F401
                            logRISE, multiRISE)
-from .inference import (ConditionalMeans, Imputation, PredictiveCheck, conditional_means, conditional_sample, impute,  # noqa: F401
-                        impute_sample, predictive_check)
+from .inference import (ConditionalMeans, ConditionalMode, Imputation, ImputedMode, PredictiveCheck, conditional_means,  # noqa: F401
+                        conditional_mode, conditional_sample, impute, impute_mode, impute_sample, predictive_check)
 from .learn import learn  # noqa: F401
-from .likelihood import (AIS, Exact, LogLikelihood, LogPartition, exact_moments, log_likelihood, log_partition,  # noqa: F401
-                         observed_log_likelihood)
+from .likelihood import (AIS, Exact, LogLikelihood, LogPartition, MostProbable, exact_moments, log_likelihood,  # noqa: F401
+                         log_partition, most_probable_states, observed_log_likelihood)
 from .missing import EMStep, ImputationEM, MissingDataResult, learn_missing  # noqa: F401
 from .path import PathResult, learn_path  # noqa: F401
 from .sampling import GMSampler, Gibbs, Glauber, GlauberChains, GlauberTermChains, TemperedTermChains, sample  # noqa: F401
@@ -25,4 +25,5 @@ __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multi
            "structure_from_rows", "structure_from_keys", "learn_path", "PathResult", "AIS", "log_partition", "log_likelihood", "LogPartition",
            "LogLikelihood", "conditional_sample", "conditional_means", "predictive_check", "ConditionalMeans", "PredictiveCheck",
            "impute", "impute_sample", "Imputation", "learn_missing", "ImputationEM", "EMStep", "MissingDataResult", "Exact",
-           "exact_moments", "observed_log_likelihood"]
+           "exact_moments", "observed_log_likelihood", "most_probable_states", "MostProbable", "conditional_mode", "ConditionalMode",
+           "impute_mode", "ImputedMode"]

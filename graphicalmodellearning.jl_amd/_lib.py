@@ -100,6 +100,9 @@ def lib():
     L.gml_conditional_means_masked.argtypes = [p, i32, p, i64, i64, p, p, i32, i64, i32, i32, C.c_uint64, p]
     L.gml_conditional_exact.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_exact_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
+    L.gml_model_best_states.argtypes = [p, i32, p, i64, i64, i64, i32, C.POINTER(i64), p, p]
+    L.gml_conditional_mode.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
+    L.gml_conditional_mode_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_problem_create_sampled_hist.argtypes =[p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -392,6 +395,21 @@ def model_exact(terms, n, queries=None, pairs=True, device=0):
     check(lib().gml_model_exact(_ptr(keys), stride, _ptr(wts), len(wts), n, _ptr(qkeys) if nq else None, qkeys.shape[1] if nq else 1, nq,
                                 int(device), C.byref(log_z), _ptr(m), _ptr(corr), _ptr(q) if nq else None))
     return float(log_z.value), m, corr, (q[:nq] if q is not None else None)
+
+
+def model_best_states(terms, n, k, device=0):
+    """gml_model_best_states on a term list as term_arrays takes it: (states int8 [found, n] of +-1, energies float64 [found]) -- the
+    found = min(k, 2^n) most probable states, energy descending, equal energies in state order (spin i at bit i, a set bit is -1); by
+    enumeration on the device, k <= 256, components of at most 40 spins."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    n, k = int(n), int(k)
+    rows = min(max(k, 0), 256)  # (the library refuses a k outside [1, 256] before it writes)
+    states = np.zeros((rows, max(n, 0)), dtype=np.int8)
+    energies = np.zeros(rows)
+    found = C.c_int64()
+    check(lib().gml_model_best_states(_ptr(keys), stride, _ptr(wts), len(wts), n, k, int(device), C.byref(found), _ptr(states),
+                                      _ptr(energies)))
+    return states[:found.value], energies[:found.value]
 
 
 class Problem:
@@ -842,6 +860,37 @@ def conditional_exact_masked(terms, n, evidence, mask, *, means=True, log_w=True
     check(lib().gml_conditional_exact_masked(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, mask._h, _ptr(m), _ptr(lw),
                                              _ptr(lp)))
     return m, lw, lp
+
+
+def conditional_mode(terms, n, evidence, hidden, *, energy=True, log_p=True):
+    """gml_conditional_mode on a term list as term_arrays takes it: evidence an open Problem, hidden the 0-BASED hidden spins, the same
+    in every row (at most 24).  Returns (states int8 [H, K], the hidden spins ascending; energy [K]; log_p [K]), None for what was not
+    asked for: every row's most probable joint state of the hidden spins, its energy E_k and its conditional log-probability, by
+    enumeration on the evidence's device.  Without log_p the device computes no exponential."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    mask = np.zeros(max(int(n), 0), dtype=np.uint8)
+    hidden = np.asarray(hidden, dtype=np.int64).ravel()
+    if len(hidden) and (hidden.min() < 0 or hidden.max() >= n):
+        raise GMLError(GML_EINVAL, f"a hidden spin lies outside [0, {int(n)})")
+    mask[hidden] = 1
+    st = np.zeros((int(mask.sum()), evidence.K), dtype=np.int8)
+    en = np.zeros(evidence.K) if energy else None
+    lp = np.zeros(evidence.K) if log_p else None
+    check(lib().gml_conditional_mode(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, _ptr(mask), _ptr(st), _ptr(en), _ptr(lp)))
+    return st, en, lp
+
+
+def conditional_mode_masked(terms, n, evidence, mask, *, energy=True, log_p=True):
+    """gml_conditional_mode_masked: evidence and mask two open Problems of the same n, K and device; a -1 in row k of the mask hides that
+    spin in row k of the evidence (at most 24 per row).  Returns (states int8 [n, K], observed entries holding the evidence value;
+    energy [K]; log_p [K]), None for what was not asked for."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    st = np.zeros((max(int(n), 0), evidence.K), dtype=np.int8)
+    en = np.zeros(evidence.K) if energy else None
+    lp = np.zeros(evidence.K) if log_p else None
+    check(lib().gml_conditional_mode_masked(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, mask._h, _ptr(st), _ptr(en),
+                                            _ptr(lp)))
+    return st, en, lp
 
 
 def moments(samples_or_problem, terms=None, raw=False, device=0):

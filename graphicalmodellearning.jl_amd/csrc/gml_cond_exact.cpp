@@ -3,7 +3,8 @@
 // one plan per distinct hidden set (the terms sorted by hidden part, items, partial sums, the coefficients in the order of their
 // chunk masks), plans and jobs uploaded in slabs, one launch and one synchronisation per slab.  The per-row form reads the hidden
 // sets from the mask handle's sign bits, groups the rows by identical set and plans a set exactly as the uniform form plans its one:
-// a mask whose rows are all equal therefore gives the uniform form's bits.
+// a mask whose rows are all equal therefore gives the uniform form's bits.  gml_conditional_mode and gml_conditional_mode_masked (every
+// row's most probable hidden state) are the same two paths with other outputs (CondOutputs) and the kernel's mode forms.
 #include "gml_sampled.h"
 
 #include <map>
@@ -192,12 +193,25 @@ struct Slab {
     }
 };
 
+// what a call asks for (host pointers, any but the first of a family NULL): the sums of gml_conditional_exact[_masked] -- means, log_w,
+// log_p -- or, with mode set, the most probable hidden state of every row of gml_conditional_mode[_masked] -- states, energy, log_p
+struct CondOutputs {
+    bool mode = false;
+    double *means = nullptr, *log_w = nullptr;
+    int8_t *states = nullptr;
+    double *energy = nullptr;
+    double *log_p = nullptr;
+    bool per_spin() const { return mode ? states != nullptr : means != nullptr; }
+};
+
 // the device side of one call: the stream, the outputs [hmax][K], [K], [K] (those asked for) and the slabs
 struct CondExactRun {
     SamplerStaging s;
     const unsigned *dSb = nullptr;
     int64_t wpr = 0, n = 0, K = 0;
-    double *dmeans = nullptr, *dlw = nullptr, *dlp = nullptr;
+    double *dmeans = nullptr, *dlw = nullptr, *dlp = nullptr, *den = nullptr;
+    int8_t *dstates = nullptr;
+    bool mode = false;
 
     int open(gml_problem *evidence, gml_problem *mask) {
         if (s.open(evidence->device)) return s.rc;
@@ -209,10 +223,13 @@ struct CondExactRun {
         K = evidence->K;
         return s.rc;
     }
-    int outputs(size_t hmax, bool means, bool log_w, bool log_p) {
-        if (means) dmeans = s.alloc<double>(std::max<size_t>(hmax, 1) * (size_t)K);
-        if (log_w) dlw = s.alloc<double>((size_t)K);
-        if (log_p) dlp = s.alloc<double>((size_t)K);
+    int outputs(size_t hmax, const CondOutputs &o) {
+        mode = o.mode;
+        if (o.means) dmeans = s.alloc<double>(std::max<size_t>(hmax, 1) * (size_t)K);
+        if (o.states) dstates = s.alloc<int8_t>(std::max<size_t>(hmax, 1) * (size_t)K);
+        if (o.log_w) dlw = s.alloc<double>((size_t)K);
+        if (o.energy) den = s.alloc<double>((size_t)K);
+        if (o.log_p) dlp = s.alloc<double>((size_t)K);
         return s.rc;
     }
     // upload, launch, drain, free: one synchronisation per slab
@@ -241,7 +258,8 @@ struct CondExactRun {
         const CondExactPlan *dplans = s.upload(plans);
         const CondExactJob *djobs = s.upload(sl.jobs);
         if (s.rc) return s.rc;
-        launch_cond_exact(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, dmeans, K, dlw, dlp, s.st);
+        if (mode) launch_cond_mode(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, dstates, K, den, dlp, s.st);
+        else launch_cond_exact(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, dmeans, K, dlw, dlp, s.st);
         if (s.sync()) return s.rc;
         for (size_t i = mark; i < s.tmp.size(); ++i) (void)dev_free(s.tmp[i]);
         s.tmp.resize(mark);
@@ -249,16 +267,16 @@ struct CondExactRun {
         g_cond_exact_times[1] += gml_now_s() - t0;
         return s.rc;
     }
-    void download(double *dst, const double *src, size_t count) {
-        if (dst && count) s.ok(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    template <class T> void download(T *dst, const T *src, size_t count) {
+        if (dst && count) s.ok(hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
     }
 };
 
 // what both entry points check alike before the model's values, in the order of check_conditional_args (gml_chains_host.cpp)
 int check_cond_exact_args(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, const gml_problem *evidence,
-                          const void *second, const char *second_name, const gml_problem *rowmask, const double *means, const double *log_w,
-                          const double *log_p) {
-    if (!means && !log_w && !log_p) return fail(GML_EINVAL, "means, log_w and log_p are all NULL");
+                          const void *second, const char *second_name, const gml_problem *rowmask, const CondOutputs &o) {
+    if (o.mode && !o.states) return fail(GML_EINVAL, "states is NULL");
+    if (!o.mode && !o.means && !o.log_w && !o.log_p) return fail(GML_EINVAL, "means, log_w and log_p are all NULL");
     if (!evidence) return fail(GML_EINVAL, "evidence is NULL");
     if (!second) return fail(GML_EINVAL, "%s is NULL", second_name);
     if (int rc = check_term_pointers(keys, key_stride, weights, nterms, true)) return rc;
@@ -282,12 +300,11 @@ struct CondExactClock {
     ~CondExactClock() { g_cond_exact_times[2] = gml_now_s() - t0; }
 };
 
-} // namespace
-
-extern "C" int gml_conditional_exact(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                     gml_problem *evidence, const uint8_t *hidden, double *means, double *log_w, double *log_p) {
+// one hidden set for every row: gml_conditional_exact and gml_conditional_mode
+int cond_uniform(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
+                 const uint8_t *hidden, const CondOutputs &o) {
     CondExactClock clock;
-    if (int rc = check_cond_exact_args(keys, key_stride, weights, nterms, n, evidence, hidden, "hidden", nullptr, means, log_w, log_p)) return rc;
+    if (int rc = check_cond_exact_args(keys, key_stride, weights, nterms, n, evidence, hidden, "hidden", nullptr, o)) return rc;
     std::vector<int> hid;
     for (int64_t i = 0; i < n; ++i)
         if (hidden[i]) hid.push_back((int)i);
@@ -305,23 +322,27 @@ extern "C" int gml_conditional_exact(const int32_t *keys, int key_stride, const 
     if (int rc = gml_check_device(evidence->device)) return rc;
     if (evidence->K == 0) return GML_OK; // (no row: nothing to enumerate)
     CondExactRun run;
-    if (run.open(evidence, nullptr) || run.outputs(hid.size(), means != nullptr, log_w != nullptr, log_p != nullptr)) return run.s.rc;
+    if (run.open(evidence, nullptr) || run.outputs(hid.size(), o)) return run.s.rc;
     Slab sl;
     const int plan = sl.add(pc);
     sl.jobs.reserve((size_t)run.K);
     for (int64_t k = 0; k < run.K; ++k) sl.jobs.push_back(CondExactJob{(long long)k, plan, 0});
     if (run.flush(sl)) return run.s.rc;
     clock.before_download();
-    run.download(means, run.dmeans, hid.size() * (size_t)run.K);
-    run.download(log_w, run.dlw, (size_t)run.K);
-    run.download(log_p, run.dlp, (size_t)run.K);
+    run.download(o.means, run.dmeans, hid.size() * (size_t)run.K);
+    run.download(o.states, run.dstates, hid.size() * (size_t)run.K);
+    run.download(o.log_w, run.dlw, (size_t)run.K);
+    run.download(o.energy, run.den, (size_t)run.K);
+    run.download(o.log_p, run.dlp, (size_t)run.K);
     return run.s.sync();
 }
 
-extern "C" int gml_conditional_exact_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
-                                            gml_problem *evidence, gml_problem *mask, double *means, double *log_w, double *log_p) {
+// a hidden set per row, read from the mask handle: gml_conditional_exact_masked and gml_conditional_mode_masked
+int cond_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
+                gml_problem *mask, const CondOutputs &o) {
     CondExactClock clock;
-    if (int rc = check_cond_exact_args(keys, key_stride, weights, nterms, n, evidence, mask, "mask", mask, means, log_w, log_p)) return rc;
+    if (int rc = check_cond_exact_args(keys, key_stride, weights, nterms, n, evidence, mask, "mask", mask, o)) return rc;
+    const bool per_spin = o.per_spin();
     if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
     if (int rc = check_cond_exact_n(n)) return rc;
     ReducedTerms R;
@@ -332,11 +353,11 @@ extern "C" int gml_conditional_exact_masked(const int32_t *keys, int key_stride,
     if (run.open(evidence, mask)) return run.s.rc;
     const int64_t K = run.K;
     // the hidden sets: the mask's sign bits come down ([n][Kp / 32], bit k % 32 of word k / 32 <-> row k), and the evidence's with
-    // them when the means are wanted (an observed entry holds its evidence value)
+    // them when the means (the states) are wanted (an observed entry holds its evidence value)
     const size_t mwpr = (size_t)(mask->d.Kp / 32), ewpr = (size_t)run.wpr;
-    std::vector<unsigned> mb((size_t)n * mwpr), eb(means ? (size_t)n * ewpr : 0);
+    std::vector<unsigned> mb((size_t)n * mwpr), eb(per_spin ? (size_t)n * ewpr : 0);
     run.s.ok(hipMemcpyAsync(mb.data(), mask->d.Sb, sizeof(unsigned) * mb.size(), hipMemcpyDeviceToHost, run.s.st), "hipMemcpyAsync");
-    if (means) run.s.ok(hipMemcpyAsync(eb.data(), evidence->d.Sb, sizeof(unsigned) * eb.size(), hipMemcpyDeviceToHost, run.s.st), "hipMemcpyAsync");
+    if (per_spin) run.s.ok(hipMemcpyAsync(eb.data(), evidence->d.Sb, sizeof(unsigned) * eb.size(), hipMemcpyDeviceToHost, run.s.st), "hipMemcpyAsync");
     if (run.s.sync()) return run.s.rc;
     const size_t kwords = (size_t)((K + 31) / 32);
     auto for_holes = [&](const std::function<void(int64_t, int)> &fn) { // (row, spin) of every hole, the spins of a row ascending
@@ -374,7 +395,7 @@ extern "C" int gml_conditional_exact_masked(const int32_t *keys, int key_stride,
         }
         patterns[it->second].second.push_back(k);
     }
-    if (run.outputs(hmax, means != nullptr, log_w != nullptr, log_p != nullptr)) return run.s.rc;
+    if (run.outputs(hmax, o)) return run.s.rc;
     std::vector<int> loc((size_t)n, -1);
     Slab sl;
     for (auto &pat : patterns) {
@@ -387,17 +408,62 @@ extern "C" int gml_conditional_exact_masked(const int32_t *keys, int key_stride,
     }
     if (run.flush(sl)) return run.s.rc;
     clock.before_download();
-    std::vector<double> hm(means ? std::max<size_t>(hmax, 1) * (size_t)K : 0);
-    run.download(means ? hm.data() : nullptr, run.dmeans, hm.size());
-    run.download(log_w, run.dlw, (size_t)K);
-    run.download(log_p, run.dlp, (size_t)K);
+    std::vector<double> hm(o.means ? std::max<size_t>(hmax, 1) * (size_t)K : 0);
+    std::vector<int8_t> hs(o.states ? std::max<size_t>(hmax, 1) * (size_t)K : 0);
+    run.download(o.means ? hm.data() : nullptr, run.dmeans, hm.size());
+    run.download(o.states ? hs.data() : nullptr, run.dstates, hs.size());
+    run.download(o.log_w, run.dlw, (size_t)K);
+    run.download(o.energy, run.den, (size_t)K);
+    run.download(o.log_p, run.dlp, (size_t)K);
     if (run.s.sync()) return run.s.rc;
-    if (means) {
+    // [n][K]: the evidence values, then every row's holes from the hidden-major results
+    auto scatter = [&](auto *dst, const auto &src) {
         for (int64_t i = 0; i < n; ++i)
-            for (int64_t k = 0; k < K; ++k) means[i * K + k] = ((eb[(size_t)i * ewpr + (size_t)(k >> 5)] >> (k & 31)) & 1u) ? -1.0 : 1.0;
+            for (int64_t k = 0; k < K; ++k) dst[i * K + k] = ((eb[(size_t)i * ewpr + (size_t)(k >> 5)] >> (k & 31)) & 1u) ? -1 : 1;
         for (int64_t k = 0; k < K; ++k)
             for (size_t a = off[(size_t)k]; a < off[(size_t)k + 1]; ++a)
-                means[(int64_t)holes[a] * K + k] = hm[(a - off[(size_t)k]) * (size_t)K + (size_t)k];
-    }
+                dst[(int64_t)holes[a] * K + k] = src[(a - off[(size_t)k]) * (size_t)K + (size_t)k];
+    };
+    if (o.means) scatter(o.means, hm);
+    if (o.states) scatter(o.states, hs);
     return GML_OK;
+}
+
+} // namespace
+
+extern "C" int gml_conditional_exact(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                     gml_problem *evidence, const uint8_t *hidden, double *means, double *log_w, double *log_p) {
+    CondOutputs o;
+    o.means = means;
+    o.log_w = log_w;
+    o.log_p = log_p;
+    return cond_uniform(keys, key_stride, weights, nterms, n, evidence, hidden, o);
+}
+extern "C" int gml_conditional_exact_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                            gml_problem *evidence, gml_problem *mask, double *means, double *log_w, double *log_p) {
+    CondOutputs o;
+    o.means = means;
+    o.log_w = log_w;
+    o.log_p = log_p;
+    return cond_masked(keys, key_stride, weights, nterms, n, evidence, mask, o);
+}
+
+// the most probable hidden state of every row (include/gml.h; the mode forms of k_cond_exact)
+extern "C" int gml_conditional_mode(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                    gml_problem *evidence, const uint8_t *hidden, int8_t *states, double *energy, double *log_p) {
+    CondOutputs o;
+    o.mode = true;
+    o.states = states;
+    o.energy = energy;
+    o.log_p = log_p;
+    return cond_uniform(keys, key_stride, weights, nterms, n, evidence, hidden, o);
+}
+extern "C" int gml_conditional_mode_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                           gml_problem *evidence, gml_problem *mask, int8_t *states, double *energy, double *log_p) {
+    CondOutputs o;
+    o.mode = true;
+    o.states = states;
+    o.energy = energy;
+    o.log_p = log_p;
+    return cond_masked(keys, key_stride, weights, nterms, n, evidence, mask, o);
 }

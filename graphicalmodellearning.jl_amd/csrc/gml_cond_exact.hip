@@ -15,6 +15,8 @@
 // A row of c < kExactChunkBits chunk bits runs the same transforms: the bits above c belong to no coefficient, every sum over them is
 // an exact doubling, and the factor 2^(kExactChunkBits - c) is taken out of the sum again before its logarithm.
 // The result of a row is a function of the model, the row's bits and the plan alone: not of the job's place, the grid or the other rows.
+// The same kernel, compiled in two more forms, selects the row's most probable hidden state instead of (or beside) summing
+// (gml_conditional_mode, gml_conditional_mode_masked): see kMode below.
 #include "../../include/gml.h"
 #include "gml_dev.h"
 #include "gml_exact_wht.h"
@@ -42,15 +44,25 @@ __device__ __forceinline__ double item_sum(const double *__restrict__ w, const u
     return s;
 }
 
+// kMode (compile time): kCondSums = the sums above; kCondModeSums = those and the row's most probable hidden state (its energy stands in
+// log_p for the held one's); kCondModeOnly = that state and its energy alone -- steps 3 and 4 of the chunk are not compiled.  In the
+// mode forms every thread keeps its best (energy, local state) over its 16 registers and all chunks -- strict > while the states
+// ascend, so the lower state keeps a tie -- and the row ends with one arg-max over the workgroup; thread j writes hidden spin j.
+// The mode forms write through the same parameters: means [h][ldm] is then the +-1 bytes of the state (Spin = int8_t), log_w [K] its
+// energy, log_p [K] that energy - log sum exp.
+enum { kCondSums = 0, kCondModeSums = 1, kCondModeOnly = 2 };
+
+template <int kMode, class Spin>
 __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restrict__ plans, const CondExactJob *__restrict__ jobs,
                                                     long long njobs, const unsigned *__restrict__ Sb, long long wpr, int n,
-                                                    double *__restrict__ means, long long ldm, double *__restrict__ log_w,
+                                                    Spin *__restrict__ means, long long ldm, double *__restrict__ log_w,
                                                     double *__restrict__ log_p) {
     // v: the transform's vector; the row phase, which does not transform, keeps the row's sign bits (514 words) and its partial sums
     // (kCondParts doubles from element 264 on) in it
     __shared__ double v[kExactVec], coef[kCondCoefs], red[4], res[kCondMaxHidden + 1];
     __shared__ double held_e;
     __shared__ unsigned held_bits;
+    __shared__ unsigned long long red_s[4];
     unsigned *bits = reinterpret_cast<unsigned *>(v);
     double *part = v + 264;
     const int tid = threadIdx.x;
@@ -128,6 +140,8 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
         const int *run_off = P.run_off, *run_dst = P.run_dst;
         const int nchunks = 1 << (h - c);
         double acc0 = 0.0, acc1 = 0.0, m0 = -INFINITY, m1 = -INFINITY; // (the maxima are the same in every thread)
+        double be = -INFINITY; // (the mode forms: this thread's best)
+        unsigned long long bs = ~0ull;
         for (int hv = 0; hv < nchunks; ++hv) {
             __syncthreads(); // (the picks of the chunk before, or the row phase, have read v)
 #pragma unroll
@@ -157,6 +171,15 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
                 for (int e = 1; e < 16; ++e)
                     if ((unsigned)e == (held_lo >> 8)) he = x[e];
                 held_e = he;
+            }
+            if constexpr (kMode != kCondSums) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    if (tid + 256 * e < (1 << c) && x[e] > be) {
+                        be = x[e];
+                        bs = ((unsigned long long)hv << c) | (unsigned long long)(tid + 256 * e);
+                    }
+                if constexpr (kMode == kCondModeOnly) continue;
             }
             // 3. p = exp(E - m0) at the running maximum; a chunk that raises it rescales what has been accumulated
             double mx = x[0];
@@ -189,14 +212,26 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
                 m0 = -INFINITY;
             }
         }
-        if (tid <= h) res[tid] = acc1;
-        __syncthreads();
-        if (tid == 0) {
-            const double lw = m1 + log(ldexp(res[0], c - kExactChunkBits));
-            if (log_w) log_w[k] = lw;
-            if (log_p) log_p[k] = held_e - lw;
+        if constexpr (kMode != kCondSums) {
+            best_of_block(be, bs, red, red_s);
+            if (tid < h) means[(long long)tid * ldm + k] = (bs >> tid) & 1ull ? -1 : 1;
+            if (tid == 0 && log_w) log_w[k] = be;
         }
-        if (mine && means) means[(long long)j * ldm + k] = res[tid] / res[0];
+        if constexpr (kMode != kCondModeOnly) {
+            if (tid <= h) res[tid] = acc1;
+            __syncthreads();
+            if (tid == 0) {
+                const double lw = m1 + log(ldexp(res[0], c - kExactChunkBits));
+                if constexpr (kMode == kCondSums) {
+                    if (log_w) log_w[k] = lw;
+                    if (log_p) log_p[k] = held_e - lw;
+                } else {
+                    log_p[k] = be - lw;
+                }
+            }
+            if constexpr (kMode == kCondSums)
+                if (mine && means) means[(long long)j * ldm + k] = res[tid] / res[0];
+        }
     }
 }
 
@@ -204,8 +239,20 @@ void launch_cond_exact(const CondExactPlan *dplans, const CondExactJob *djobs, i
                        double *dmeans, int64_t ldm, double *dlog_w, double *dlog_p, hipStream_t st) {
     if (njobs <= 0) return;
     const unsigned grid = (unsigned)std::min<int64_t>(njobs, (int64_t)1 << 20);
-    hipLaunchKernelGGL(k_cond_exact, dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb, (long long)wpr, (int)n, dmeans,
-                       (long long)ldm, dlog_w, dlog_p);
+    hipLaunchKernelGGL((k_cond_exact<kCondSums, double>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
+                       (long long)wpr, (int)n, dmeans, (long long)ldm, dlog_w, dlog_p);
+}
+
+void launch_cond_mode(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
+                      int8_t *dstates, int64_t lds, double *denergy, double *dlog_p, hipStream_t st) {
+    if (njobs <= 0) return;
+    const unsigned grid = (unsigned)std::min<int64_t>(njobs, (int64_t)1 << 20);
+    if (dlog_p)
+        hipLaunchKernelGGL((k_cond_exact<kCondModeSums, int8_t>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
+                           (long long)wpr, (int)n, dstates, (long long)lds, denergy, dlog_p);
+    else
+        hipLaunchKernelGGL((k_cond_exact<kCondModeOnly, int8_t>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
+                           (long long)wpr, (int)n, dstates, (long long)lds, denergy, dlog_p);
 }
 
 } // namespace gml

@@ -293,6 +293,11 @@ struct ExactPlan {
     double *gm, *gacc;
 };
 void launch_exact(const ExactPlan &P, int G, double *dres, hipStream_t st);
+// The k <= kBestMax best states of the component (gml_best.hip): the plan's terms, items and partial sums as above (its queries and
+// sums play no part), c low bits.  Group g writes its best min(k, states of the group) pairs (energy, state: bit i set <-> spin i of
+// the component is -1) to dge / dgs [G][k], best first, the rest -inf / ~0.
+constexpr int kBestMax = 256;                            // states asked for: the group's list, 4 KB of LDS (= the workgroup's threads)
+void launch_exact_best(const ExactPlan &P, int G, int c, int k, double *dge, unsigned long long *dgs, hipStream_t st);
 
 // Exact conditional inference, one workgroup per row (gml_cond_exact.hip).  A plan is one hidden set: h hidden spins hid [h] (ascending;
 // local bit j <-> hid[j]), c chunk bits.  The model's terms sorted by their hidden part (stable): w [T], vis [T][S] the visible spins of
@@ -327,6 +332,11 @@ struct CondExactJob {
 };
 void launch_cond_exact(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
                        double *dmeans, int64_t ldm, double *dlog_w, double *dlog_p, hipStream_t st);
+// The same jobs for the most probable hidden state of every row (the mode forms of the kernel): dstates[j lds + k] = +-1, the value of
+// hid[j] in the state of largest E_k (equal energies: the lower local state), denergy[k] (or NULL) that energy, dlog_p[k] (or NULL)
+// that energy - log_w[k].  With dlog_p NULL the kernel computes no exp and no second transform.
+void launch_cond_mode(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
+                      int8_t *dstates, int64_t lds, double *denergy, double *dlog_p, hipStream_t st);
 
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].

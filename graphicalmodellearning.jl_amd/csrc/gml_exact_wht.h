@@ -1,5 +1,6 @@
-// Device-side pieces shared by the two enumeration kernels, k_exact_enumerate (gml_exact.hip) and k_cond_exact (gml_cond_exact.hip):
-// the padded LDS vector of one chunk and the radix-16 Walsh-Hadamard passes over it.  Include from .hip files only.
+// Device-side pieces shared by the enumeration kernels, k_exact_enumerate (gml_exact.hip), k_exact_best (gml_best.hip) and
+// k_cond_exact (gml_cond_exact.hip): the padded LDS vector of one chunk, the radix-16 Walsh-Hadamard passes over it, and the order
+// of the selecting forms.  Include from .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,37 @@ __device__ __forceinline__ void wht16(double (&x)[16]) {
             x[k | s] = a - b;
         }
     }
+}
+
+// The order of the best states (k_exact_best, the mode forms of k_cond_exact): energy descending, equal energies state ascending.
+// Whether (ea, sa) comes before (eb, sb).
+template <class Idx> __device__ __forceinline__ bool best_before(double ea, Idx sa, double eb, Idx sb) {
+    return ea > eb || (ea == eb && sa < sb);
+}
+// The first pair of a workgroup of 256 threads in that order; every thread gets it.  le, ls: 4 elements of LDS each, free again
+// after the next barrier.
+__device__ __forceinline__ void best_of_block(double &e, unsigned long long &s, double *le, unsigned long long *ls) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oe = __shfl_xor(e, o);
+        const unsigned long long os = __shfl_xor(s, o);
+        if (best_before(oe, os, e, s)) {
+            e = oe;
+            s = os;
+        }
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        le[threadIdx.x >> 6] = e;
+        ls[threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    e = le[0];
+    s = ls[0];
+    for (int wv = 1; wv < 4; ++wv)
+        if (best_before(le[wv], ls[wv], e, s)) {
+            e = le[wv];
+            s = ls[wv];
+        }
 }
 
 __device__ __forceinline__ void exact_load(const double *v, int base, int stride, double (&x)[16]) {

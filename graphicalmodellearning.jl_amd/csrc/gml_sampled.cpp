@@ -560,10 +560,8 @@ static int plan_exact_component(const std::vector<unsigned long long> &mask, con
     return GML_OK;
 }
 
-// the enumerations of one planned component: its queries in windows of kExactWindow - 1 beside the empty query (Z)
-static int run_exact_component(ExactComponent &pc, int device) {
-    SamplerStaging s;
-    if (int rc = s.open(device)) return rc;
+// the planned component's terms, items and partial sums on the device, and its chunks dealt to G groups of cpg
+static ExactPlan upload_exact_terms(SamplerStaging &s, ExactComponent &pc, int &G) {
     ExactPlan P{};
     P.ni = (int)pc.item_dst.size();
     P.nm = (int)pc.ms_dst.size();
@@ -575,8 +573,17 @@ static int run_exact_component(ExactComponent &pc, int device) {
     P.ms_off = s.upload(pc.ms_off);
     P.ms_dst = s.upload(pc.ms_dst);
     const long long nchunks = (long long)1 << (pc.sb - pc.c);
-    const int G = (int)std::min<long long>(nchunks, kExactGroups);
+    G = (int)std::min<long long>(nchunks, kExactGroups);
     P.cpg = nchunks / G;
+    return P;
+}
+
+// the enumerations of one planned component: its queries in windows of kExactWindow - 1 beside the empty query (Z)
+static int run_exact_component(ExactComponent &pc, int device) {
+    SamplerStaging s;
+    if (int rc = s.open(device)) return rc;
+    int G = 0;
+    ExactPlan P = upload_exact_terms(s, pc, G);
     P.gm = s.alloc<double>((size_t)G);
     P.gacc = s.alloc<double>((size_t)G * kExactWindow);
     int *dqlo = s.alloc<int>(kExactWindow);
@@ -613,6 +620,44 @@ static int run_exact_component(ExactComponent &pc, int device) {
     return GML_OK;
 }
 
+// The model by connected components: local[i] = the place of spin i in its component, mask / wt [b] = the component's terms over its own
+// spins in the caller's order, consts = the weights of the terms that reduce to the empty key.  Refuses a component above 40 spins.
+struct ComponentTerms {
+    TermComponents tc;
+    std::vector<int> local;
+    std::vector<std::vector<unsigned long long>> mask;
+    std::vector<std::vector<double>> wt;
+    std::vector<double> consts;
+};
+static int component_terms(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, ComponentTerms &ct) {
+    ct.tc = term_components(keys, key_stride, weights, nterms, n);
+    const size_t nb = ct.tc.blocks.size();
+    for (auto &b : ct.tc.blocks)
+        if (b.size() > (size_t)kExactMaxSpins)
+            return fail(GML_EUNSUPPORTED, "a connected component of the model has %zu spins: exact enumeration is limited to %d", b.size(),
+                        kExactMaxSpins);
+    ct.local.assign((size_t)n, 0);
+    for (auto &b : ct.tc.blocks)
+        for (size_t i = 0; i < b.size(); ++i) ct.local[(size_t)b[i]] = (int)i;
+    ct.mask.resize(nb);
+    ct.wt.resize(nb);
+    std::vector<int> sp;
+    for (int64_t t = 0; t < nterms; ++t) {
+        if (weights[t] == 0.0) continue;
+        reduce_key(keys + t * key_stride, key_stride, sp);
+        if (sp.empty()) {
+            ct.consts.push_back(weights[t]);
+            continue;
+        }
+        unsigned long long mask = 0;
+        for (int v : sp) mask |= (unsigned long long)1 << ct.local[(size_t)v];
+        const size_t b = (size_t)ct.tc.id[(size_t)sp[0]];
+        ct.mask[b].push_back(mask);
+        ct.wt[b].push_back(weights[t]);
+    }
+    return GML_OK;
+}
+
 extern "C" int gml_model_exact(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, const int32_t *qkeys,
                                int qkey_stride, int64_t nq, int device, double *log_z, double *mean, double *corr, double *qexp) {
     if (!log_z) return fail(GML_EINVAL, "log_z is NULL");
@@ -625,33 +670,16 @@ extern "C" int gml_model_exact(const int32_t *keys, int key_stride, const double
             const int32_t v = qkeys[q * qkey_stride + a];
             if (v < -1 || v >= n) return fail(GML_EINVAL, "query %lld names spin %d outside [0,%lld)", (long long)q, v, (long long)n);
         }
-    const TermComponents tc = term_components(keys, key_stride, weights, nterms, n);
-    const size_t nb = tc.blocks.size();
-    for (auto &b : tc.blocks)
-        if (b.size() > (size_t)kExactMaxSpins)
-            return fail(GML_EUNSUPPORTED, "a connected component of the model has %zu spins: exact enumeration is limited to %d", b.size(),
-                        kExactMaxSpins);
-    std::vector<int> local((size_t)n, 0);
-    for (auto &b : tc.blocks)
-        for (size_t i = 0; i < b.size(); ++i) local[(size_t)b[i]] = (int)i;
     // per component: its terms as masks over its own spins; the empty key is a constant of log Z
-    std::vector<std::vector<unsigned long long>> bmask(nb);
-    std::vector<std::vector<double>> bwt(nb);
-    std::vector<double> parts; // the summands of log Z
+    ComponentTerms ct;
+    if (int rc = component_terms(keys, key_stride, weights, nterms, n, ct)) return rc;
+    const TermComponents &tc = ct.tc;
+    const size_t nb = tc.blocks.size();
+    const std::vector<int> &local = ct.local;
+    const std::vector<std::vector<unsigned long long>> &bmask = ct.mask;
+    const std::vector<std::vector<double>> &bwt = ct.wt;
+    std::vector<double> parts = ct.consts; // the summands of log Z
     std::vector<int> sp;
-    for (int64_t t = 0; t < nterms; ++t) {
-        if (weights[t] == 0.0) continue;
-        reduce_key(keys + t * key_stride, key_stride, sp);
-        if (sp.empty()) {
-            parts.push_back(weights[t]);
-            continue;
-        }
-        unsigned long long mask = 0;
-        for (int v : sp) mask |= (unsigned long long)1 << local[(size_t)v];
-        const size_t b = (size_t)tc.id[(size_t)sp[0]];
-        bmask[b].push_back(mask);
-        bwt[b].push_back(weights[t]);
-    }
     // a spin in no term needs no enumeration: ln 2, mean 0; the others are planned before the device is looked for
     const bool moments = mean || corr;
     std::vector<ExactComponent> comp(nb);
@@ -725,6 +753,154 @@ extern "C" int gml_model_exact(const int32_t *keys, int key_stride, const double
         for (int64_t a = uq_off[(size_t)q]; a < uq_off[(size_t)q + 1] && !uq_zero[(size_t)q]; ++a)
             e *= comp[(size_t)uq[(size_t)a].first].expect[(size_t)uq[(size_t)a].second];
         qexp[q] = e;
+    }
+    return GML_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// gml_model_best_states: the k most probable states, component by component (gml_best.hip), merged on the host
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// best states over some of the spins, best first (energy descending, equal energies state ascending): entry r has energy e[r] and the
+// n sign bits bits[r W .. (r + 1) W), bit i of word i / 64 set <-> spin i is -1 (a spin outside the list's spins: 0)
+struct BestList {
+    size_t W = 1;
+    std::vector<double> e;
+    std::vector<uint64_t> bits;
+    size_t size() const { return e.size(); }
+    const uint64_t *at(size_t r) const { return bits.data() + r * W; }
+};
+
+// The k best sums of two lists over disjoint spins.  A heap walks the pairs (i, j) in the order of e_A[i] + e_B[j] (rounded sums are
+// monotone in either index, so the frontier rule holds), past k until the sum falls below the k-th: every pair that ties with the
+// cut is seen.  The pairs are then sorted by (sum descending, joint state ascending -- compared from the highest spin down) and cut.
+BestList merge_best(const BestList &A, const BestList &B, size_t k) {
+    struct Pair {
+        double e;
+        uint32_t i, j;
+    };
+    const size_t W = A.W, na = A.size(), nb = B.size();
+    auto state_less = [&](const Pair &p, const Pair &q) {
+        for (size_t w = W; w-- > 0;) {
+            const uint64_t x = A.at(p.i)[w] | B.at(p.j)[w], y = A.at(q.i)[w] | B.at(q.j)[w];
+            if (x != y) return x < y;
+        }
+        return false;
+    };
+    auto lower_sum = [](const Pair &p, const Pair &q) { return p.e < q.e; };
+    std::vector<Pair> heap, got;
+    std::vector<uint8_t> seen(na * nb, 0);
+    auto push = [&](size_t i, size_t j) {
+        if (i >= na || j >= nb || seen[i * nb + j]) return;
+        seen[i * nb + j] = 1;
+        heap.push_back(Pair{A.e[i] + B.e[j], (uint32_t)i, (uint32_t)j});
+        std::push_heap(heap.begin(), heap.end(), lower_sum);
+    };
+    push(0, 0);
+    while (!heap.empty() && (got.size() < k || heap.front().e == got.back().e)) {
+        std::pop_heap(heap.begin(), heap.end(), lower_sum);
+        const Pair p = heap.back();
+        heap.pop_back();
+        got.push_back(p);
+        push(p.i + 1, p.j);
+        push(p.i, p.j + 1);
+    }
+    std::sort(got.begin(), got.end(), [&](const Pair &p, const Pair &q) { return p.e != q.e ? p.e > q.e : state_less(p, q); });
+    if (got.size() > k) got.resize(k);
+    BestList out;
+    out.W = W;
+    out.bits.resize(got.size() * W);
+    for (size_t r = 0; r < got.size(); ++r) {
+        out.e.push_back(got[r].e);
+        for (size_t w = 0; w < W; ++w) out.bits[r * W + w] = A.at(got[r].i)[w] | B.at(got[r].j)[w];
+    }
+    return out;
+}
+
+// The min(k, 2^sb) best states of one planned component: the device selects by the energies of its butterflies (equal ones: the lower
+// state), the host cuts the groups' lists to one, recomputes every selected energy as the plain sum of the component's terms in the
+// caller's order (pairwise_sum) and sorts by (that energy descending, state ascending).
+int run_best_component(ExactComponent &pc, const std::vector<unsigned long long> &mask, const std::vector<double> &wt, int k, int device,
+                       std::vector<std::pair<double, unsigned long long>> &best) {
+    SamplerStaging s;
+    if (int rc = s.open(device)) return rc;
+    int G = 0;
+    const ExactPlan P = upload_exact_terms(s, pc, G);
+    const size_t cand = (size_t)G * (size_t)k;
+    double *dge = s.alloc<double>(cand);
+    unsigned long long *dgs = s.alloc<unsigned long long>(cand);
+    if (s.rc) return s.rc;
+    launch_exact_best(P, G, pc.c, k, dge, dgs, s.st);
+    s.ok(hipGetLastError(), "the selection's launch");
+    std::vector<double> ge(cand);
+    std::vector<unsigned long long> gs(cand);
+    s.ok(hipMemcpyAsync(ge.data(), dge, sizeof(double) * cand, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    s.ok(hipMemcpyAsync(gs.data(), dgs, sizeof(unsigned long long) * cand, hipMemcpyDeviceToHost, s.st), "hipMemcpyAsync");
+    if (s.sync()) return s.rc;
+    std::vector<size_t> idx;
+    for (size_t a = 0; a < cand; ++a)
+        if (gs[a] != ~0ull) idx.push_back(a);
+    const unsigned long long states = (unsigned long long)1 << pc.sb;
+    const size_t want = (size_t)std::min<unsigned long long>((unsigned long long)k, states);
+    if (idx.size() < want) return fail(GML_EHIP, "the selection returned %zu of %zu states", idx.size(), want);
+    std::partial_sort(idx.begin(), idx.begin() + (ptrdiff_t)want, idx.end(),
+                      [&](size_t a, size_t b) { return ge[a] != ge[b] ? ge[a] > ge[b] : gs[a] < gs[b]; });
+    idx.resize(want);
+    best.clear();
+    std::vector<double> summand(mask.size());
+    for (size_t a : idx) {
+        for (size_t t = 0; t < mask.size(); ++t) summand[t] = (__builtin_popcountll(mask[t] & gs[a]) & 1) ? -wt[t] : wt[t];
+        best.emplace_back(pairwise_sum(summand.data(), summand.size()), gs[a]);
+    }
+    std::sort(best.begin(), best.end(), [](auto &p, auto &q) { return p.first != q.first ? p.first > q.first : p.second < q.second; });
+    return GML_OK;
+}
+
+} // namespace
+
+extern "C" int gml_model_best_states(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t k,
+                                     int device, int64_t *found, int8_t *states, double *energies) {
+    if (int rc = check_term_pointers(keys, key_stride, weights, nterms)) return rc;
+    if (n <= 0 || nterms < 0) return fail(GML_EINVAL, "n must be positive and nterms non-negative");
+    if (int rc = check_term_values(keys, key_stride, weights, nterms, n)) return rc;
+    if (k < 1) return fail(GML_EINVAL, "k must be at least 1");
+    if (!found || !states || !energies) return fail(GML_EINVAL, "found, states or energies is NULL");
+    if (k > kBestMax) return fail(GML_EUNSUPPORTED, "k = %lld: at most %d best states are kept", (long long)k, kBestMax);
+    ComponentTerms ct;
+    if (int rc = component_terms(keys, key_stride, weights, nterms, n, ct)) return rc;
+    const size_t nb = ct.tc.blocks.size();
+    std::vector<ExactComponent> comp(nb);
+    for (size_t b = 0; b < nb; ++b) {
+        if (ct.mask[b].empty()) continue; // (a spin in no term: two states of energy 0, no device work)
+        comp[b].sb = (int)ct.tc.blocks[b].size();
+        if (int rc = plan_exact_component(ct.mask[b], ct.wt[b], comp[b])) return rc;
+    }
+    if (int rc = gml_check_device(device)) return rc;
+    const size_t W = (size_t)((n + 63) / 64);
+    BestList all; // the constant of every energy, over no spin
+    all.W = W;
+    all.e.push_back(pairwise_sum(ct.consts.data(), ct.consts.size()));
+    all.bits.assign(W, 0);
+    std::vector<std::pair<double, unsigned long long>> best;
+    for (size_t b = 0; b < nb; ++b) {
+        const std::vector<int> &mem = ct.tc.blocks[b];
+        if (ct.mask[b].empty()) best = {{0.0, 0ull}, {0.0, 1ull}};
+        else if (int rc = run_best_component(comp[b], ct.mask[b], ct.wt[b], (int)k, device, best)) return rc;
+        BestList part;
+        part.W = W;
+        part.bits.assign(best.size() * W, 0);
+        for (size_t r = 0; r < best.size(); ++r) {
+            part.e.push_back(best[r].first);
+            for (size_t i = 0; i < mem.size(); ++i)
+                if ((best[r].second >> i) & 1ull) part.bits[r * W + (size_t)mem[i] / 64] |= (uint64_t)1 << (mem[i] % 64);
+        }
+        all = merge_best(all, part, (size_t)k);
+    }
+    *found = (int64_t)all.size();
+    for (size_t r = 0; r < all.size(); ++r) {
+        energies[r] = all.e[r];
+        for (int64_t i = 0; i < n; ++i) states[(int64_t)r * n + i] = ((all.at(r)[(size_t)i / 64] >> (i % 64)) & 1u) ? -1 : 1;
     }
     return GML_OK;
 }

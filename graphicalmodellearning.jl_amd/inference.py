@@ -244,6 +244,62 @@ def _exact_holes(model, values, missing, device=0, means=True, log_w=True, log_p
     return (None if m is None else np.ascontiguousarray(m.T[inv]), None if lw is None else lw[inv], None if lp is None else lp[inv])
 
 
+@dataclass
+class ConditionalMode:
+    """states int8 [K, H]: every evidence row's most probable JOINT state of the hidden spins given its visible ones (equal energies:
+    the hidden spins read as a binary number, the first at bit 0, -1 a set bit -- the lower number, so a hidden spin in no term is +1);
+    energy [K]: E_k of that state, the row's constant included; log_p [K] = log P(x_H = states[k] | x_O); hidden: the H hidden spins,
+    1-based, ascending; counts [K]: the counts of the evidence rows."""
+    states: np.ndarray
+    energy: np.ndarray
+    log_p: np.ndarray
+    hidden: list
+    counts: np.ndarray
+
+
+def conditional_mode(model, evidence, hidden, *, method=None):
+    """The most probable joint completion of the hidden spins of every evidence row, by enumeration on the device
+    (gml_conditional_mode): model, evidence, hidden as conditional_means takes them; method: an Exact whose max_hidden (<= 24) bounds
+    the hidden spins.  Not the signs of the conditional means, which decide spin by spin.  Returns a ConditionalMode."""
+    method = Exact() if method is None else _exact_method(method, None, 1, 0)
+    ev = _Evidence(evidence)
+    spins = _hidden_spins(hidden, ev.n)
+    if len(spins) > method.max_hidden:  # (refused before a handle is opened)
+        raise ValueError(f"{len(spins)} spins are hidden: more than max_hidden = {method.max_hidden}")
+    args = _term_list_args(model, _problem_args(model))
+    terms = args["terms"] if len(args["terms"]) else {(1,): 0.0}  # (a model without a term, as the chains take it)
+    with ev as p:
+        st, energy, log_p = _lib.conditional_mode(terms, ev.n, p, np.asarray(spins) - 1)
+        counts = p.counts()
+    return ConditionalMode(np.ascontiguousarray(st.T), energy, log_p, spins, counts)
+
+
+@dataclass
+class ImputedMode:
+    """completed int8 [K', n]: every row with its missing entries filled by their most probable JOINT values given the observed ones
+    (an observed entry keeps its value); energy [K'] and log_p [K'] of that completion as in ConditionalMode (a row without holes:
+    its own energy and 0.0); missing [K', n] bool.  K' rows as in Imputation."""
+    completed: np.ndarray
+    energy: np.ndarray
+    log_p: np.ndarray
+    missing: np.ndarray
+
+
+def impute_mode(model, samples, *, method=None):
+    """The most probable joint completion of every row of data with holes (`samples` as impute takes it), by enumeration of the row's
+    missing spins on the device (gml_conditional_mode_masked; at most method.max_hidden <= 24 per row).  Returns an ImputedMode, its rows
+    in the caller's order."""
+    method = Exact() if method is None else _exact_method(method, None, 1, 0)
+    values, missing = _missing_rows(samples)
+    _check_holes(missing, method.max_hidden)  # (refused before a handle is opened)
+    with _Holes(values, missing) as holes:
+        args = _term_list_args(model, _problem_args(model))
+        terms = args["terms"] if len(args["terms"]) else {(1,): 0.0}
+        st, energy, log_p = _lib.conditional_mode_masked(terms, holes.n, holes.evidence, holes.mask)
+        inv = holes.inverse
+    return ImputedMode(np.ascontiguousarray(st.T[inv]), energy[inv], log_p[inv], missing)
+
+
 def _impute_args(samples, sampler, replicas):
     sampler = _sampler(sampler)
     if int(replicas) < 1:

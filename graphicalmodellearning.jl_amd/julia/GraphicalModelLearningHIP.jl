@@ -355,6 +355,99 @@ function conditional_exact_masked(terms::Dict, samples::Array{T,2}; device::Inte
     end
 end
 
+"""
+    most_probable_states(terms::Dict, n, k=1; device=0) -> states (found x n, Int8 +-1), energies (found)
+
+The found = min(k, 2^n) most probable states of a model of `n` spins (gml_model_best_states, include/gml.h), certified by enumeration
+on the device: energy descending, equal energies in state order (spin i at bit i - 1, -1 a set bit, the smaller number first).
+1 <= k <= 256, connected components of at most 40 spins.  Marshalling only.
+"""
+function most_probable_states(terms::Dict, n::Integer, k::Integer=1; device::Integer=0)
+    keymat, weights, stride = term_arrays(terms)
+    rows = clamp(k, 0, 256)                                # (the library refuses a k outside 1:256 before it writes)
+    states = Array{Int8}(undef, n, rows)                   # C row-major [k][n] == Julia (n x k)
+    energies = Vector{Float64}(undef, rows)
+    found = Ref{Int64}(0)
+    rc = ccall((:gml_model_best_states, libgml), Cint,
+               (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Int64, Cint, Ref{Int64}, Ptr{Int8}, Ptr{Cdouble}),
+               keymat, stride, weights, length(weights), n, k, device, found, states, energies)
+    rc == GML_OK || error("gml_model_best_states: $(lasterr())")
+    return permutedims(states[:, 1:found[]]), energies[1:found[]]
+end
+
+"""
+    conditional_mode(terms::Dict, samples, hidden; device=0) -> states (K x H, Int8 +-1), energy (K), log_p (K)
+
+The most probable joint state of the spins `hidden` (1-based, at most 24) given the other spins of every row of the histogram
+`samples` (K x (1+n)) (gml_conditional_mode, include/gml.h): `states[k, a]` is the value of the a-th hidden spin (ascending),
+`energy[k]` the row's energy at that state, `log_p[k]` its conditional log-probability.  Marshalling only.
+"""
+function conditional_mode(terms::Dict, samples::Array{T,2}, hidden::AbstractVector{<:Integer}; device::Integer=0) where T <: Real
+    s = T <: AbstractFloat ? convert(Array{Float64,2}, samples) : convert(Array{Int64,2}, samples)
+    dtype = eltype(s) == Float64 ? GML_F64 : GML_I64
+    K, n = size(s, 1), size(s, 2) - 1
+    all(i -> 1 <= i <= n, hidden) && !isempty(hidden) && allunique(hidden) ||
+        throw(ArgumentError("conditional_mode: hidden must name distinct spins in 1:$n"))
+    mask = zeros(UInt8, n)
+    mask[hidden] .= 1
+    keymat, weights, stride = term_arrays(terms)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:gml_problem_create, libgml), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Cint, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+               s, dtype, K, n, K, 1 #= column-major =#, 2, 0, n, device, handle)
+    rc == GML_OK || error("gml_problem_create: $(lasterr())")
+    try
+        states = Array{Int8}(undef, K, length(hidden))    # C row-major [H][K] == Julia (K x H)
+        energy = Vector{Float64}(undef, K)
+        log_p = Vector{Float64}(undef, K)
+        rc = ccall((:gml_conditional_mode, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int8}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, handle[], mask, states, energy, log_p)
+        rc == GML_OK || error("gml_conditional_mode: $(lasterr())")
+        return states, energy, log_p
+    finally
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
+    end
+end
+
+"""
+    conditional_mode_masked(terms::Dict, samples; device=0) -> completed (K x n, Int8 +-1), energy (K), log_p (K)
+
+The same for data with holes (gml_conditional_mode_masked): a spin entry of `samples` (K x (1+n)) is -1, +1 or 0 = missing, at most 24
+missing per row; `completed[k, :]` is row k with its missing entries filled by their most probable joint values, the observed ones
+kept.  Two handles are made and destroyed, as in conditional_exact_masked.  Marshalling only.
+"""
+function conditional_mode_masked(terms::Dict, samples::Array{T,2}; device::Integer=0) where T <: Real
+    K, n = size(samples, 1), size(samples, 2) - 1
+    spins = samples[:, 2:end]
+    all(v -> v == -1 || v == 0 || v == 1, spins) || throw(ArgumentError("conditional_mode_masked: spin entries must be -1, +1 or 0"))
+    evidence = Int8.(ifelse.(spins .== 0, 1, spins))
+    holes = Int8.(ifelse.(spins .== 0, -1, 1))
+    keymat, weights, stride = term_arrays(terms)
+    he = Ref{Ptr{Cvoid}}(C_NULL)
+    hm = Ref{Ptr{Cvoid}}(C_NULL)
+    create(bytes, h) = ccall((:gml_problem_create_spins, libgml), Cint,
+                             (Ptr{Cdouble}, Ptr{Int8}, Int64, Int64, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+                             C_NULL, bytes, K, n, 2, 0, n, device, h)
+    rc = create(permutedims(evidence), he)
+    rc == GML_OK || error("gml_problem_create_spins: $(lasterr())")
+    try
+        rc = create(permutedims(holes), hm)
+        rc == GML_OK || error("gml_problem_create_spins: $(lasterr())")
+        completed = Array{Int8}(undef, K, n)              # C row-major [n][K] == Julia (K x n)
+        energy = Vector{Float64}(undef, K)
+        log_p = Vector{Float64}(undef, K)
+        rc = ccall((:gml_conditional_mode_masked, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int8}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, he[], hm[], completed, energy, log_p)
+        rc == GML_OK || error("gml_conditional_mode_masked: $(lasterr())")
+        return completed, energy, log_p
+    finally
+        hm[] == C_NULL || ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), hm[])
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), he[])
+    end
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

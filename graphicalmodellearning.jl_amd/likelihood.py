@@ -172,3 +172,24 @@ def exact_moments(model, terms=None, pairs=True, device=0, method=None):
         return _lib.model_exact(mterms, n, queries=terms, pairs=False, device=device)[3]
     _, m, corr, _ = _lib.model_exact(mterms, n, pairs=pairs, device=device)
     return m, corr
+
+
+@dataclass
+class MostProbable:
+    """states int8 [found, n]: the found = min(k, 2^n) most probable states of the model, +-1, by energy descending, equal energies in
+    state order (spin i at bit i - 1, -1 a set bit, read as a binary number); energy [found]: E(s) = sum_t w_t prod_{i in t} s_i;
+    log_p [found] = energy - log Z with log_prob=True, else None."""
+    states: np.ndarray
+    energy: np.ndarray
+    log_p: np.ndarray = None
+
+
+def most_probable_states(model, k=1, *, log_prob=False, device=0, method=None):
+    """The k most probable states of `model` (as log_partition takes it), certified by enumeration on the device
+    (gml_model_best_states): 1 <= k <= 256, components of at most 40 spins (method: an Exact whose max_spins refuses larger ones).
+    log_prob=True adds their log-probabilities at the price of one exact log Z (gml_model_exact).  Returns a MostProbable."""
+    terms, n = _model_terms(model)
+    _check_exact(Exact() if method is None else method, terms, n)
+    states, energy = _lib.model_best_states(terms, n, k, device=device)
+    log_p = energy - _lib.model_exact(terms, n, pairs=False, device=device)[0] if log_prob else None
+    return MostProbable(states, energy, log_p)

@@ -529,6 +529,71 @@ int gml_conditional_exact_masked(const int32_t *keys, int key_stride, const doub
                                  double *log_w /* [K] or NULL */, double *log_p /* [K] or NULL */);
 
 /*
+ * gml_model_best_states -- the k most probable states of ANY term list whose connected components have at most 40 spins, certified
+ * by streaming enumeration on the device: the states the model "means".  The pipeline of gml_model_exact up to the energies of every
+ * state, which are then selected instead of summed (no exponential, no second transform).  No handle is made; all pointers are host
+ * pointers.
+ * Model.  The conventions of gml_model_exact: 0-based spins, -1 = unused slot, a spin named twice cancels, a term of weight zero joins
+ *   nothing, FP64 weights as given.  E(s) = sum_t w_t prod_{i in t} s_i; a term that reduces to the empty key is a constant of every
+ *   energy.
+ * Outputs.  *found = min(k, 2^n).  states [found][n] row-major, +-1, and energies [found]: the found states of largest E, energy
+ *   descending; equal energies in state order -- the state read as a binary number with spin i at bit i, a set bit = spin -1, the
+ *   smaller number first (for n > 64: compared from the highest spin down).  The rows beyond found are not written.
+ * Limits.  1 <= k <= 256.  The cap is a design choice: a workgroup keeps its running list of k (energy, state) pairs in 4 KB of LDS
+ *   beside the transform's vector, and the groups' lists come down to the host (1024 k pairs at most, 4 MB).
+ * Selection on the device, order on the host.  Per component the device selects by the energies its butterflies produce -- a pure
+ *   function of (model, chunk width) at every state -- and gives equal ones to the lower state.  For every selected state the host
+ *   then recomputes the energy as the plain FP64 sum of the component's reduced terms in the caller's order (no accumulator takes more
+ *   than 1024 summands serially: halves above that) and sorts by (that energy descending, state ascending).  energies are therefore
+ *   plain sums, not butterfly outputs.  Consequence: among states whose true energies agree within the a-priori bound of
+ *   gml_model_exact, (12 + log2 T) 2^-53 sum_t |w_t|, which of them make the cut at position k follows the device's rounding: it is
+ *   deterministic and a pure function of the model, and otherwise unspecified.  The pair s, -s of a model with only even terms
+ *   recomputes to bit-equal energies and comes out in state order when both are inside the cut.
+ * Components.  A sum of independent parts: every component gives its own list of min(k, 2^sb) states (a spin in no term: two states of
+ *   energy 0, +1 first, no device work), and the lists are merged on the host in pairs, in the order of the components' smallest spins,
+ *   starting from the constant: the k best sums e_A + e_B of two sorted lists (a heap over the pairs, carried past k through every sum
+ *   that ties with the k-th), ordered by (sum descending, joint state ascending).  The merge is a function of the model alone.
+ * Two calls with the same arguments return the same bytes.
+ * GML_EINVAL, before any HIP call, in this order: NULL keys or weights with nterms > 0, key_stride < 1; n < 1 or nterms < 0; a spin
+ *   outside [0, n) or a non-finite weight; k < 1; NULL found, states or energies.  GML_EUNSUPPORTED, before any HIP call, the limit
+ *   named in gml_last_error, in this order: k > 256; a component of more than 40 spins, or of more than 2^20 terms of non-zero weight.
+ *   The device is looked for last.
+ * Cost.  One enumeration of 2^sb states per component; k = 1 keeps one best per thread and costs about three quarters of "log Z
+ *   alone"; k > 1 adds a sort only in the chunks that beat the list's k-th energy.  Measured times in DESIGN 3.20.  Device memory is
+ *   released before the call returns.
+ */
+int gml_model_best_states(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t k, int device,
+                          int64_t *found, int8_t *states /* [k][n] row-major, +-1 */, double *energies /* [k] */);
+
+/*
+ * gml_conditional_mode, gml_conditional_mode_masked -- the most probable JOINT completion of every row's hidden spins: s_H* = argmax
+ * over the 2^h hidden states of E_k(s_H), by the enumeration of gml_conditional_exact[_masked] with the energies selected instead of
+ * summed.  Not the signs of the conditional means, which decide spin by spin.
+ * Model, evidence, hidden / mask, E_k, limits: exactly those of gml_conditional_exact and gml_conditional_exact_masked.
+ * Outputs, per row (host).
+ *   states: the values (+-1) of the hidden spins in s_H*.  Equal energies (as the device's butterflies produce them) go to the lower
+ *     local state -- bit j <-> the j-th hidden spin of the row, ascending, a set bit = spin -1 -- so a hidden spin in no term is +1.
+ *     gml_conditional_mode: [H][K], hidden-major, the hidden spins ascending.  gml_conditional_mode_masked: [n][K], an observed entry
+ *     holding its evidence value; a row without holes is legal and comes back as it is.
+ *   energy [K] (or NULL): E_k(s_H*), the row's constant included.
+ *   log_p [K] (or NULL): E_k(s_H*) - log_w[k] = log P(x_H = s_H* | x_O), with log_w[k] the same bits gml_conditional_exact[_masked]
+ *     returns for that row.  With log_p NULL the device computes no exponential and no second transform; states and energy are the
+ *     same bits either way.
+ * Determinism.  The promise of gml_conditional_exact: a row's result is a pure function of the model, that row and that row's hidden
+ *   set; a mask handle whose rows all equal one vector gives, bit for bit, what gml_conditional_mode gives with that vector.
+ * GML_EINVAL and GML_EUNSUPPORTED: the cases of gml_conditional_exact[_masked] in their order, with "states is NULL" in the place of
+ *   "all three outputs NULL".
+ * Cost.  That of gml_conditional_exact[_masked]; without log_p the chunk phase takes about 0.6 of it.  Measured times in DESIGN 3.20.
+ */
+int gml_conditional_mode(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
+                         const uint8_t *hidden /* [n], host */, int8_t *states /* [H][K], hidden-major, hidden spins ascending */,
+                         double *energy /* [K] or NULL */, double *log_p /* [K] or NULL */);
+int gml_conditional_mode_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                gml_problem *evidence, gml_problem *mask,
+                                int8_t *states /* [n][K]; an observed entry holds its evidence value */,
+                                double *energy /* [K] or NULL */, double *log_p /* [K] or NULL */);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
