@@ -103,6 +103,8 @@ def lib():
     L.gml_model_best_states.argtypes = [p, i32, p, i64, i64, i64, i32, C.POINTER(i64), p, p]
     L.gml_conditional_mode.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_mode_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
+    L.gml_conditional_draw.argtypes = [p, i32, p, i64, i64, p, p, i32, C.c_uint64, p, p, p]
+    L.gml_conditional_draw_masked.argtypes = [p, i32, p, i64, i64, p, p, i32, C.c_uint64, p, p, p]
     L.gml_problem_create_sampled_hist.argtypes =[p, i32, p, i64, i64, i64, C.c_uint64, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_problem_get_counts.argtypes = [p, p]
     L.gml_problem_get_spins.argtypes = [p, p]
@@ -890,6 +892,41 @@ def conditional_mode_masked(terms, n, evidence, mask, *, energy=True, log_p=True
     lp = np.zeros(evidence.K) if log_p else None
     check(lib().gml_conditional_mode_masked(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, mask._h, _ptr(st), _ptr(en),
                                             _ptr(lp)))
+    return st, en, lp
+
+
+def conditional_draw(terms, n, evidence, hidden, replicas=1, seed=0, *, energy=True, log_p=True):
+    """gml_conditional_draw on a term list as term_arrays takes it: evidence an open Problem, hidden the 0-BASED hidden spins, the same
+    in every row (at most 24).  Returns (states int8 [H, K replicas], the hidden spins ascending, chain r K + k replica r of row k;
+    energy [K replicas], the unperturbed energy of every draw; log_p [K replicas]), None for what was not asked for: exact draws of
+    every row's hidden spins given its visible ones, by enumeration on the evidence's device (Gumbel-max, no chain).  Without log_p the
+    device computes no exponential of the sums; states and energy are the same bytes either way."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    mask = np.zeros(max(int(n), 0), dtype=np.uint8)
+    hidden = np.asarray(hidden, dtype=np.int64).ravel()
+    if len(hidden) and (hidden.min() < 0 or hidden.max() >= n):
+        raise GMLError(GML_EINVAL, f"a hidden spin lies outside [0, {int(n)})")
+    mask[hidden] = 1
+    chains = evidence.K * max(int(replicas), 0)
+    st = np.zeros((int(mask.sum()), chains), dtype=np.int8)
+    en = np.zeros(chains) if energy else None
+    lp = np.zeros(chains) if log_p else None
+    check(lib().gml_conditional_draw(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, _ptr(mask), int(replicas),
+                                     int(seed), _ptr(st), _ptr(en), _ptr(lp)))
+    return st, en, lp
+
+
+def conditional_draw_masked(terms, n, evidence, mask, replicas=1, seed=0, *, energy=True, log_p=True):
+    """gml_conditional_draw_masked: evidence and mask two open Problems of the same n, K and device; a -1 in row k of the mask hides that
+    spin in row k of the evidence (at most 24 per row).  Returns (states int8 [n, K replicas], observed entries holding the evidence
+    value; energy [K replicas]; log_p [K replicas]), None for what was not asked for."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    chains = evidence.K * max(int(replicas), 0)
+    st = np.zeros((max(int(n), 0), chains), dtype=np.int8)
+    en = np.zeros(chains) if energy else None
+    lp = np.zeros(chains) if log_p else None
+    check(lib().gml_conditional_draw_masked(_ptr(keys), stride, _ptr(wts), len(wts), int(n), evidence._h, mask._h, int(replicas),
+                                            int(seed), _ptr(st), _ptr(en), _ptr(lp)))
     return st, en, lp
 
 

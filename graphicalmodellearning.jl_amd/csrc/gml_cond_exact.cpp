@@ -4,7 +4,9 @@
 // chunk masks), plans and jobs uploaded in slabs, one launch and one synchronisation per slab.  The per-row form reads the hidden
 // sets from the mask handle's sign bits, groups the rows by identical set and plans a set exactly as the uniform form plans its one:
 // a mask whose rows are all equal therefore gives the uniform form's bits.  gml_conditional_mode and gml_conditional_mode_masked (every
-// row's most probable hidden state) are the same two paths with other outputs (CondOutputs) and the kernel's mode forms.
+// row's most probable hidden state) are the same two paths with other outputs (CondOutputs) and the kernel's mode forms;
+// gml_conditional_draw and gml_conditional_draw_masked (exact draws of every row's hidden spins) are the mode calls with
+// `replicas` chains per row and the kernel's draw forms: a plan per distinct hidden set as before, a job per kCondDrawBatch replicas.
 #include "gml_sampled.h"
 
 #include <map>
@@ -194,9 +196,12 @@ struct Slab {
 };
 
 // what a call asks for (host pointers, any but the first of a family NULL): the sums of gml_conditional_exact[_masked] -- means, log_w,
-// log_p -- or, with mode set, the most probable hidden state of every row of gml_conditional_mode[_masked] -- states, energy, log_p
+// log_p -- or, with mode set, the most probable hidden state of every row of gml_conditional_mode[_masked] -- states, energy, log_p --
+// or, with draw set as well, `replicas` exact draws per row with the same three outputs per chain (gml_conditional_draw[_masked])
 struct CondOutputs {
-    bool mode = false;
+    bool mode = false, draw = false;
+    int replicas = 1;
+    uint64_t seed = 0;
     double *means = nullptr, *log_w = nullptr;
     int8_t *states = nullptr;
     double *energy = nullptr;
@@ -204,11 +209,15 @@ struct CondOutputs {
     bool per_spin() const { return mode ? states != nullptr : means != nullptr; }
 };
 
-// the device side of one call: the stream, the outputs [hmax][K], [K], [K] (those asked for) and the slabs
+// the device side of one call: the stream, the outputs [hmax][C], [C], [C] (those asked for; C = K chains, K replicas for the draws)
+// and the slabs
 struct CondExactRun {
     SamplerStaging s;
     const unsigned *dSb = nullptr;
-    int64_t wpr = 0, n = 0, K = 0;
+    int64_t wpr = 0, n = 0, K = 0, C = 0;
+    int replicas = 1; // (of the draws; a job takes kCondDrawBatch of a row's)
+    uint64_t seed = 0;
+    bool draw = false;
     double *dmeans = nullptr, *dlw = nullptr, *dlp = nullptr, *den = nullptr;
     int8_t *dstates = nullptr;
     bool mode = false;
@@ -225,12 +234,20 @@ struct CondExactRun {
     }
     int outputs(size_t hmax, const CondOutputs &o) {
         mode = o.mode;
-        if (o.means) dmeans = s.alloc<double>(std::max<size_t>(hmax, 1) * (size_t)K);
-        if (o.states) dstates = s.alloc<int8_t>(std::max<size_t>(hmax, 1) * (size_t)K);
-        if (o.log_w) dlw = s.alloc<double>((size_t)K);
-        if (o.energy) den = s.alloc<double>((size_t)K);
-        if (o.log_p) dlp = s.alloc<double>((size_t)K);
+        draw = o.draw;
+        replicas = o.replicas;
+        seed = o.seed;
+        C = K * replicas;
+        if (o.means) dmeans = s.alloc<double>(std::max<size_t>(hmax, 1) * (size_t)C);
+        if (o.states) dstates = s.alloc<int8_t>(std::max<size_t>(hmax, 1) * (size_t)C);
+        if (o.log_w) dlw = s.alloc<double>((size_t)C);
+        if (o.energy) den = s.alloc<double>((size_t)C);
+        if (o.log_p) dlp = s.alloc<double>((size_t)C);
         return s.rc;
+    }
+    // the jobs of row k under a plan: one, or one per kCondDrawBatch replicas
+    void add_jobs(Slab &sl, int64_t k, int plan) const {
+        for (int r = 0; r < replicas; r += kCondDrawBatch) sl.jobs.push_back(CondExactJob{(long long)k, plan, r});
     }
     // upload, launch, drain, free: one synchronisation per slab
     int flush(Slab &sl) {
@@ -258,7 +275,8 @@ struct CondExactRun {
         const CondExactPlan *dplans = s.upload(plans);
         const CondExactJob *djobs = s.upload(sl.jobs);
         if (s.rc) return s.rc;
-        if (mode) launch_cond_mode(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, dstates, K, den, dlp, s.st);
+        if (draw) launch_cond_draw(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, K, replicas, seed, dstates, den, dlp, s.st);
+        else if (mode) launch_cond_mode(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, dstates, K, den, dlp, s.st);
         else launch_cond_exact(dplans, djobs, (int64_t)sl.jobs.size(), dSb, wpr, n, dmeans, K, dlw, dlp, s.st);
         if (s.sync()) return s.rc;
         for (size_t i = mark; i < s.tmp.size(); ++i) (void)dev_free(s.tmp[i]);
@@ -276,6 +294,7 @@ struct CondExactRun {
 int check_cond_exact_args(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, const gml_problem *evidence,
                           const void *second, const char *second_name, const gml_problem *rowmask, const CondOutputs &o) {
     if (o.mode && !o.states) return fail(GML_EINVAL, "states is NULL");
+    if (o.replicas < 1) return fail(GML_EINVAL, "replicas = %d: at least 1", o.replicas);
     if (!o.mode && !o.means && !o.log_w && !o.log_p) return fail(GML_EINVAL, "means, log_w and log_p are all NULL");
     if (!evidence) return fail(GML_EINVAL, "evidence is NULL");
     if (!second) return fail(GML_EINVAL, "%s is NULL", second_name);
@@ -325,15 +344,15 @@ int cond_uniform(const int32_t *keys, int key_stride, const double *weights, int
     if (run.open(evidence, nullptr) || run.outputs(hid.size(), o)) return run.s.rc;
     Slab sl;
     const int plan = sl.add(pc);
-    sl.jobs.reserve((size_t)run.K);
-    for (int64_t k = 0; k < run.K; ++k) sl.jobs.push_back(CondExactJob{(long long)k, plan, 0});
+    sl.jobs.reserve((size_t)run.K * (size_t)((o.replicas + kCondDrawBatch - 1) / kCondDrawBatch));
+    for (int64_t k = 0; k < run.K; ++k) run.add_jobs(sl, k, plan);
     if (run.flush(sl)) return run.s.rc;
     clock.before_download();
-    run.download(o.means, run.dmeans, hid.size() * (size_t)run.K);
-    run.download(o.states, run.dstates, hid.size() * (size_t)run.K);
-    run.download(o.log_w, run.dlw, (size_t)run.K);
-    run.download(o.energy, run.den, (size_t)run.K);
-    run.download(o.log_p, run.dlp, (size_t)run.K);
+    run.download(o.means, run.dmeans, hid.size() * (size_t)run.C);
+    run.download(o.states, run.dstates, hid.size() * (size_t)run.C);
+    run.download(o.log_w, run.dlw, (size_t)run.C);
+    run.download(o.energy, run.den, (size_t)run.C);
+    run.download(o.log_p, run.dlp, (size_t)run.C);
     return run.s.sync();
 }
 
@@ -402,27 +421,30 @@ int cond_masked(const int32_t *keys, int key_stride, const double *weights, int6
         CondPattern pc;
         if (int rc = plan_pattern(R, pat.first, loc, pc)) return rc;
         const int plan = sl.add(pc);
-        for (int64_t k : pat.second) sl.jobs.push_back(CondExactJob{(long long)k, plan, 0});
+        for (int64_t k : pat.second) run.add_jobs(sl, k, plan);
         if (sl.bytes() >= kCondSlabBytes || sl.plans.size() >= kCondSlabPlans)
             if (run.flush(sl)) return run.s.rc;
     }
     if (run.flush(sl)) return run.s.rc;
     clock.before_download();
-    std::vector<double> hm(o.means ? std::max<size_t>(hmax, 1) * (size_t)K : 0);
-    std::vector<int8_t> hs(o.states ? std::max<size_t>(hmax, 1) * (size_t)K : 0);
+    const int64_t C = run.C;
+    std::vector<double> hm(o.means ? std::max<size_t>(hmax, 1) * (size_t)C : 0);
+    std::vector<int8_t> hs(o.states ? std::max<size_t>(hmax, 1) * (size_t)C : 0);
     run.download(o.means ? hm.data() : nullptr, run.dmeans, hm.size());
     run.download(o.states ? hs.data() : nullptr, run.dstates, hs.size());
-    run.download(o.log_w, run.dlw, (size_t)K);
-    run.download(o.energy, run.den, (size_t)K);
-    run.download(o.log_p, run.dlp, (size_t)K);
+    run.download(o.log_w, run.dlw, (size_t)C);
+    run.download(o.energy, run.den, (size_t)C);
+    run.download(o.log_p, run.dlp, (size_t)C);
     if (run.s.sync()) return run.s.rc;
-    // [n][K]: the evidence values, then every row's holes from the hidden-major results
+    // [n][C], chain r K + k: the evidence values of row k, then its holes from the hidden-major results
     auto scatter = [&](auto *dst, const auto &src) {
         for (int64_t i = 0; i < n; ++i)
-            for (int64_t k = 0; k < K; ++k) dst[i * K + k] = ((eb[(size_t)i * ewpr + (size_t)(k >> 5)] >> (k & 31)) & 1u) ? -1 : 1;
-        for (int64_t k = 0; k < K; ++k)
-            for (size_t a = off[(size_t)k]; a < off[(size_t)k + 1]; ++a)
-                dst[(int64_t)holes[a] * K + k] = src[(a - off[(size_t)k]) * (size_t)K + (size_t)k];
+            for (int64_t r = 0; r < C; r += K)
+                for (int64_t k = 0; k < K; ++k) dst[i * C + r + k] = ((eb[(size_t)i * ewpr + (size_t)(k >> 5)] >> (k & 31)) & 1u) ? -1 : 1;
+        for (int64_t r = 0; r < C; r += K)
+            for (int64_t k = 0; k < K; ++k)
+                for (size_t a = off[(size_t)k]; a < off[(size_t)k + 1]; ++a)
+                    dst[(int64_t)holes[a] * C + r + k] = src[(a - off[(size_t)k]) * (size_t)C + (size_t)(r + k)];
     };
     if (o.means) scatter(o.means, hm);
     if (o.states) scatter(o.states, hs);
@@ -462,6 +484,32 @@ extern "C" int gml_conditional_mode_masked(const int32_t *keys, int key_stride, 
                                            gml_problem *evidence, gml_problem *mask, int8_t *states, double *energy, double *log_p) {
     CondOutputs o;
     o.mode = true;
+    o.states = states;
+    o.energy = energy;
+    o.log_p = log_p;
+    return cond_masked(keys, key_stride, weights, nterms, n, evidence, mask, o);
+}
+
+// exact draws of every row's hidden spins (include/gml.h; the draw forms of k_cond_exact)
+extern "C" int gml_conditional_draw(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                    gml_problem *evidence, const uint8_t *hidden, int replicas, uint64_t seed, int8_t *states,
+                                    double *energy, double *log_p) {
+    CondOutputs o;
+    o.mode = o.draw = true;
+    o.replicas = replicas;
+    o.seed = seed;
+    o.states = states;
+    o.energy = energy;
+    o.log_p = log_p;
+    return cond_uniform(keys, key_stride, weights, nterms, n, evidence, hidden, o);
+}
+extern "C" int gml_conditional_draw_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                           gml_problem *evidence, gml_problem *mask, int replicas, uint64_t seed, int8_t *states,
+                                           double *energy, double *log_p) {
+    CondOutputs o;
+    o.mode = o.draw = true;
+    o.replicas = replicas;
+    o.seed = seed;
     o.states = states;
     o.energy = energy;
     o.log_p = log_p;

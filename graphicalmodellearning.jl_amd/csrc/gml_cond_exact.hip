@@ -16,10 +16,12 @@
 // an exact doubling, and the factor 2^(kExactChunkBits - c) is taken out of the sum again before its logarithm.
 // The result of a row is a function of the model, the row's bits and the plan alone: not of the job's place, the grid or the other rows.
 // The same kernel, compiled in two more forms, selects the row's most probable hidden state instead of (or beside) summing
-// (gml_conditional_mode, gml_conditional_mode_masked): see kMode below.
+// (gml_conditional_mode, gml_conditional_mode_masked), and in two more it draws from them: the mode of the energies
+// perturbed by Gumbel noise (gml_conditional_draw, gml_conditional_draw_masked): see kMode below.
 #include "../../include/gml.h"
 #include "gml_dev.h"
 #include "gml_exact_wht.h"
+#include "gml_rng.h"
 #include "gml_wg.h"
 
 #include <algorithm>
@@ -50,19 +52,32 @@ __device__ __forceinline__ double item_sum(const double *__restrict__ w, const u
 // ascend, so the lower state keeps a tie -- and the row ends with one arg-max over the workgroup; thread j writes hidden spin j.
 // The mode forms write through the same parameters: means [h][ldm] is then the +-1 bytes of the state (Spin = int8_t), log_w [K] its
 // energy, log_p [K] that energy - log sum exp.
-enum { kCondSums = 0, kCondModeSums = 1, kCondModeOnly = 2 };
+// The draw forms, kCondDrawSums and kCondDrawOnly, are the mode forms on perturbed energies (Gumbel-max): chain ch = r K + k, replica
+// r of row k, takes the state of largest key(ch, s) = E_k(s) - log(-log u01(seed, ch, s)), equal keys to the lower state.  A job names
+// the replicas [rep, rep + kCondDrawBatch) of its row below `replicas`; the row phase and the transform run once for all of them, and
+// every thread keeps (best key, its state, its energy) per replica.  The keys are formed in a rolled loop over the thread's 16 states,
+// which it reads back from its own slots of v (the two logarithms are compiled once per replica of the batch, not 16 times).  Every
+// state is hashed: passing over those whose E + 36.75 (above every perturbation) cannot beat the thread's best key was measured and
+// bought nothing where the energies of a row lie closer together than that.
+// The outputs go to chain ch where the other forms write row k: means [h][ldm] with ldm = K replicas.
+enum { kCondSums = 0, kCondModeSums = 1, kCondModeOnly = 2, kCondDrawSums = 3, kCondDrawOnly = 4 };
 
 template <int kMode, class Spin>
 __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restrict__ plans, const CondExactJob *__restrict__ jobs,
                                                     long long njobs, const unsigned *__restrict__ Sb, long long wpr, int n,
                                                     Spin *__restrict__ means, long long ldm, double *__restrict__ log_w,
-                                                    double *__restrict__ log_p) {
+                                                    double *__restrict__ log_p, long long K, int replicas, unsigned long long seed) {
+    constexpr bool kDraw = kMode == kCondDrawSums || kMode == kCondDrawOnly;
+    constexpr bool kSelect = kMode == kCondModeSums || kMode == kCondModeOnly;
+    constexpr bool kNoSums = kMode == kCondModeOnly || kMode == kCondDrawOnly;
+    constexpr int RB = kDraw ? kCondDrawBatch : 1;
     // v: the transform's vector; the row phase, which does not transform, keeps the row's sign bits (514 words) and its partial sums
     // (kCondParts doubles from element 264 on) in it
     __shared__ double v[kExactVec], coef[kCondCoefs], red[4], res[kCondMaxHidden + 1];
     __shared__ double held_e;
     __shared__ unsigned held_bits;
     __shared__ unsigned long long red_s[4];
+    __shared__ double drawn_e[kCondDrawBatch]; // (the draw forms: the energies of the batch's draws, for log_p)
     unsigned *bits = reinterpret_cast<unsigned *>(v);
     double *part = v + 264;
     const int tid = threadIdx.x;
@@ -72,7 +87,9 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
         const CondExactPlan &P = plans[jobs[job].plan];
         const long long k = jobs[job].row;
         const int h = P.h, c = P.c, S = P.S, ni = P.ni, nm = P.nm, ns = P.ns;
-        __syncthreads(); // (the row before has read v, res and held_e)
+        const int nrep = kDraw ? min(RB, replicas - jobs[job].rep) : 0;
+        const long long ch0 = kDraw ? (long long)jobs[job].rep * K + k : 0; // (the job's first chain; replica r of the batch: ch0 + r K)
+        __syncthreads(); // (the row before has read v, res, held_e and drawn_e)
         // the row's sign bits: bit i of the row = bit (k & 31) of word k / 32 of spin i's sign row.  32 neighbouring rows share every
         // word (and 1024 a cache line): consecutive workgroups take consecutive jobs, so all but the first find the words in L2.
         {
@@ -142,6 +159,10 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
         double acc0 = 0.0, acc1 = 0.0, m0 = -INFINITY, m1 = -INFINITY; // (the maxima are the same in every thread)
         double be = -INFINITY; // (the mode forms: this thread's best)
         unsigned long long bs = ~0ull;
+        double dk[RB], de[RB]; // (the draw forms: per replica of the batch this thread's best key, its energy and its state)
+        unsigned ds[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) dk[r] = de[r] = -INFINITY, ds[r] = ~0u;
         for (int hv = 0; hv < nchunks; ++hv) {
             __syncthreads(); // (the picks of the chunk before, or the row phase, have read v)
 #pragma unroll
@@ -172,15 +193,33 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
                     if ((unsigned)e == (held_lo >> 8)) he = x[e];
                 held_e = he;
             }
-            if constexpr (kMode != kCondSums) {
+            if constexpr (kSelect) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
                     if (tid + 256 * e < (1 << c) && x[e] > be) {
                         be = x[e];
                         bs = ((unsigned long long)hv << c) | (unsigned long long)(tid + 256 * e);
                     }
-                if constexpr (kMode == kCondModeOnly) continue;
             }
+            if constexpr (kDraw) {
+                exact_store(v, baseC, 272, x); // (the slots this thread alone has read)
+#pragma unroll 1
+                for (int e = 0; e < 16 && tid + 256 * e < (1 << c); ++e) {
+                    const double en = v[baseC + 272 * e];
+                    const unsigned s = ((unsigned)hv << c) | (unsigned)(tid + 256 * e);
+#pragma unroll
+                    for (int r = 0; r < RB; ++r) {
+                        if (r >= nrep) continue;
+                        const double key = en - log(-log(u01(seed, (unsigned long long)(ch0 + r * K), s)));
+                        if (best_before(key, s, dk[r], ds[r])) { // (the states ascend: an equal key wins only over no state at all)
+                            dk[r] = key;
+                            de[r] = en;
+                            ds[r] = s;
+                        }
+                    }
+                }
+            }
+            if constexpr (kNoSums) continue;
             // 3. p = exp(E - m0) at the running maximum; a chunk that raises it rescales what has been accumulated
             double mx = x[0];
 #pragma unroll
@@ -212,12 +251,29 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
                 m0 = -INFINITY;
             }
         }
-        if constexpr (kMode != kCondSums) {
+        if constexpr (kSelect) {
             best_of_block(be, bs, red, red_s);
             if (tid < h) means[(long long)tid * ldm + k] = (bs >> tid) & 1ull ? -1 : 1;
             if (tid == 0 && log_w) log_w[k] = be;
         }
-        if constexpr (kMode != kCondModeOnly) {
+        if constexpr (kDraw) {
+            for (int r = 0; r < nrep; ++r) { // (static indices under the unrolled loop; nrep is the same in every thread)
+                double bk = -INFINITY, mye = 0.0;
+                unsigned long long st = ~0ull;
+                unsigned mys = ~0u;
+#pragma unroll
+                for (int q = 0; q < RB; ++q)
+                    if (q == r) bk = dk[q], mye = de[q], mys = ds[q], st = ds[q];
+                best_of_block(bk, st, red, red_s);
+                const long long ch = ch0 + r * K;
+                if (mys == (unsigned)st) { // (one thread: the states of two threads differ, and state 0 is always taken)
+                    if (log_w) log_w[ch] = mye;
+                    drawn_e[r] = mye;
+                }
+                if (tid < h) means[(long long)tid * ldm + ch] = (st >> tid) & 1ull ? -1 : 1;
+            }
+        }
+        if constexpr (!kNoSums) {
             if (tid <= h) res[tid] = acc1;
             __syncthreads();
             if (tid == 0) {
@@ -225,8 +281,10 @@ __global__ __launch_bounds__(256) void k_cond_exact(const CondExactPlan *__restr
                 if constexpr (kMode == kCondSums) {
                     if (log_w) log_w[k] = lw;
                     if (log_p) log_p[k] = held_e - lw;
-                } else {
+                } else if constexpr (kSelect) {
                     log_p[k] = be - lw;
+                } else {
+                    for (int r = 0; r < nrep; ++r) log_p[ch0 + r * K] = drawn_e[r] - lw;
                 }
             }
             if constexpr (kMode == kCondSums)
@@ -240,7 +298,7 @@ void launch_cond_exact(const CondExactPlan *dplans, const CondExactJob *djobs, i
     if (njobs <= 0) return;
     const unsigned grid = (unsigned)std::min<int64_t>(njobs, (int64_t)1 << 20);
     hipLaunchKernelGGL((k_cond_exact<kCondSums, double>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
-                       (long long)wpr, (int)n, dmeans, (long long)ldm, dlog_w, dlog_p);
+                       (long long)wpr, (int)n, dmeans, (long long)ldm, dlog_w, dlog_p, 0ll, 0, 0ull);
 }
 
 void launch_cond_mode(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
@@ -249,10 +307,23 @@ void launch_cond_mode(const CondExactPlan *dplans, const CondExactJob *djobs, in
     const unsigned grid = (unsigned)std::min<int64_t>(njobs, (int64_t)1 << 20);
     if (dlog_p)
         hipLaunchKernelGGL((k_cond_exact<kCondModeSums, int8_t>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
-                           (long long)wpr, (int)n, dstates, (long long)lds, denergy, dlog_p);
+                           (long long)wpr, (int)n, dstates, (long long)lds, denergy, dlog_p, 0ll, 0, 0ull);
     else
         hipLaunchKernelGGL((k_cond_exact<kCondModeOnly, int8_t>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
-                           (long long)wpr, (int)n, dstates, (long long)lds, denergy, dlog_p);
+                           (long long)wpr, (int)n, dstates, (long long)lds, denergy, dlog_p, 0ll, 0, 0ull);
+}
+
+void launch_cond_draw(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
+                      int64_t K, int replicas, uint64_t seed, int8_t *dstates, double *denergy, double *dlog_p, hipStream_t st) {
+    if (njobs <= 0) return;
+    const unsigned grid = (unsigned)std::min<int64_t>(njobs, (int64_t)1 << 20);
+    const long long lds = (long long)K * replicas;
+    if (dlog_p)
+        hipLaunchKernelGGL((k_cond_exact<kCondDrawSums, int8_t>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
+                           (long long)wpr, (int)n, dstates, lds, denergy, dlog_p, (long long)K, replicas, (unsigned long long)seed);
+    else
+        hipLaunchKernelGGL((k_cond_exact<kCondDrawOnly, int8_t>), dim3(grid), dim3(256), 0, st, dplans, djobs, (long long)njobs, dSb,
+                           (long long)wpr, (int)n, dstates, lds, denergy, dlog_p, (long long)K, replicas, (unsigned long long)seed);
 }
 
 } // namespace gml

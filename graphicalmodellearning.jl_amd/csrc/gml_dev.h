@@ -328,7 +328,7 @@ struct CondExactPlan {
 };
 struct CondExactJob {
     long long row;
-    int plan, pad_;
+    int plan, rep; // (rep: the first replica of a draw job, 0 elsewhere)
 };
 void launch_cond_exact(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
                        double *dmeans, int64_t ldm, double *dlog_w, double *dlog_p, hipStream_t st);
@@ -337,6 +337,12 @@ void launch_cond_exact(const CondExactPlan *dplans, const CondExactJob *djobs, i
 // that energy - log_w[k].  With dlog_p NULL the kernel computes no exp and no second transform.
 void launch_cond_mode(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
                       int8_t *dstates, int64_t lds, double *denergy, double *dlog_p, hipStream_t st);
+// The same jobs for exact draws (the draw forms of the kernel): job (plan, row k, rep) draws the replicas rep .. min(rep +
+// kCondDrawBatch, replicas) - 1 of row k.  Chain ch = r K + k: dstates[j K replicas + ch] = +-1, denergy[ch] (or NULL) the unperturbed
+// energy of the drawn state, dlog_p[ch] (or NULL) that energy - log_w[k].  With dlog_p NULL: no exp, no second transform.
+constexpr int kCondDrawBatch = 8;                        // replicas of a row drawn in one pass over its states
+void launch_cond_draw(const CondExactPlan *dplans, const CondExactJob *djobs, int64_t njobs, const unsigned *dSb, int64_t wpr, int64_t n,
+                      int64_t K, int replicas, uint64_t seed, int8_t *dstates, double *denergy, double *dlog_p, hipStream_t st);
 
 // Batched Newton solve on the ragged Hessian blocks: A = s1[r]*H_r - s2*gF gF^T, A d = -pgF, in place
 // (Cholesky, ridge restart).  gF/pgF/dout are R x cap; Sdiag[r] = A[m-1][m-1].

@@ -15,7 +15,9 @@ missing.learn_missing builds stochastic-imputation EM on them.
 With method=Exact() conditional_means, impute and predictive_check use no chain: every row's hidden spins are enumerated on the device
 (gml_conditional_exact, gml_conditional_exact_masked; at most 24 hidden spins per row, any n), with the model's weights as they are
 (the chains quantise them).  The exact path also gives what no chain can: log_p, the joint conditional log-probability of the values a
-row holds on its hidden spins, and log_w, from which likelihood.observed_log_likelihood scores data with holes."""
+row holds on its hidden spins, and log_w, from which likelihood.observed_log_likelihood scores data with holes.  conditional_sample and
+impute_sample with method=Exact() draw exactly, with no burn-in to guess: the same enumeration on energies perturbed by Gumbel noise
+(gml_conditional_draw, gml_conditional_draw_masked); replicas and seed keep their meaning there."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -104,6 +106,26 @@ def _exact_method(method, sampler, replicas, seed):
     return method
 
 
+def _draw_method(method, sampler, replicas):
+    """method=None: the chains.  An Exact: exact draws by enumeration -- no chain runs, so a sampler is refused rather than ignored;
+    replicas and seed keep their meaning."""
+    if method is None:
+        return None
+    if not isinstance(method, Exact):
+        raise ValueError(f"conditional sampling takes method=None (chains) or an Exact, given {type(method).__name__}")
+    if sampler is not None:
+        raise ValueError("method=Exact() draws by enumeration: it takes no sampler")
+    if int(replicas) < 1:
+        raise ValueError(f"replicas must be at least 1 (given {replicas})")
+    return method
+
+
+def _model_terms(model):
+    """(the model's term list, a model without a term as the chains take it; its interaction order)"""
+    args = _term_list_args(model, _problem_args(model))
+    return (args["terms"] if len(args["terms"]) else {(1,): 0.0}), args.get("order", 2)
+
+
 def _run(model, evidence, hidden, sampler, replicas, seed, means):
     sampler = _sampler(sampler)
     if int(replicas) < 1:
@@ -117,13 +139,28 @@ def _run(model, evidence, hidden, sampler, replicas, seed, means):
         return out, spins, (p.counts() if means else None), p.K
 
 
-def conditional_sample(model, evidence, hidden, sampler=None, *, replicas=1, seed=0):
+def conditional_sample(model, evidence, hidden, sampler=None, *, replicas=1, seed=0, method=None):
     """Samples of the hidden spins (1-based, like FactorGraph keys) given the visible spins of every row of `evidence` (an open Problem or
     a K x (1+n) histogram matrix; its counts play no part).  model: a FactorGraph, a {1-based key tuple: weight} dict or a matrix with the
     fields on its diagonal; sampler: a GlauberTermChains (burn_in, thin, samples_per_chain).  Returns a Problem on the evidence's device
     with K replicas samples_per_chain rows of count 1: row (t replicas + r) K + k is sample t of replica r of evidence row k, its
-    visible spins those of the evidence."""
-    return _run(model, evidence, hidden, sampler, replicas, seed, False)[0]
+    visible spins those of the evidence.
+    method=Exact(): exact draws by enumeration of the hidden spins (gml_conditional_draw; at most method.max_hidden <= 24 of them), no
+    chain and no sampler.  The result has K replicas rows of count 1, row r K + k the draw of replica r of evidence row k (chain
+    r K + k of the seed); it is built through the host."""
+    if _draw_method(method, sampler, replicas) is None:
+        return _run(model, evidence, hidden, sampler, replicas, seed, False)[0]
+    ev = _Evidence(evidence)
+    spins = _hidden_spins(hidden, ev.n)
+    if len(spins) > method.max_hidden:  # (refused before a handle is opened)
+        raise ValueError(f"{len(spins)} spins are hidden: more than max_hidden = {method.max_hidden}")
+    terms, order = _model_terms(model)
+    hid = np.asarray(spins) - 1
+    with ev as p:
+        st = _lib.conditional_draw(terms, ev.n, p, hid, int(replicas), seed, energy=False, log_p=False)[0]
+        rows = np.tile(p.spins(), (int(replicas), 1))
+    rows[:, hid] = st.T
+    return _lib.Problem(spins=rows, order=order)
 
 
 def conditional_means(model, evidence, hidden, sampler=None, *, replicas=1, seed=0, method=None):
@@ -233,6 +270,14 @@ class _Holes:
                                               order=args.get("order", 2) if order is None else order)
 
 
+    def draws(self, model, replicas, seed, order=None):
+        """a handle of the K replicas exact draws of `model` on the two handles (_lib.conditional_draw_masked), rows in the handles'
+        order: row r K + j completes handle row j, from chain r K + j; built through the host"""
+        terms, model_order = _model_terms(model)
+        st = _lib.conditional_draw_masked(terms, self.n, self.evidence, self.mask, int(replicas), seed, energy=False, log_p=False)[0]
+        return _lib.Problem(spins=np.ascontiguousarray(st.T), order=model_order if order is None else order, device=self.device)
+
+
 def _exact_holes(model, values, missing, device=0, means=True, log_w=True, log_p=True):
     """_lib.conditional_exact_masked of `model` on data with holes (values int8 [K, n], missing bool [K, n]): (means [K, n], log_w [K],
     log_p [K]) in the caller's row order, None for what was not asked for"""
@@ -307,7 +352,7 @@ def _impute_args(samples, sampler, replicas):
     return sampler, _missing_rows(samples)  # (refused before a handle is opened)
 
 
-def impute_sample(model, samples, sampler=None, *, replicas=1, seed=0):
+def impute_sample(model, samples, sampler=None, *, replicas=1, seed=0, method=None):
     """Completions of data with holes: `samples` is a K x (1+n) histogram matrix whose spin entries are -1, +1 or 0 = missing (counts:
     positive integers; a row of count c stands for c samples, each completed on its own).  Every row keeps its observed spins and has
     its missing ones drawn from the model's conditional distribution given them, by Glauber chains whose hidden set is the row's own
@@ -315,7 +360,19 @@ def impute_sample(model, samples, sampler=None, *, replicas=1, seed=0):
     of count 1, K' the number of expanded rows: row (t replicas + r) K' + k is sample t of replica r of expanded row k, in the caller's
     order.  On the device the rows run in the stable order of their packed masks, so that the 64 chains of a wave lack similar spins;
     chain numbers, and so the random streams, follow that order, and the completed rows are put back into the caller's order through
-    the host (learn_missing, which does not care about the order, skips that)."""
+    the host (learn_missing, which does not care about the order, skips that).
+    method=Exact(): every row's missing spins are drawn exactly, by enumeration (gml_conditional_draw_masked; at most
+    method.max_hidden <= 24 per row), no chain and no sampler: K' replicas rows, row r K' + k the draw of replica r of expanded row k in
+    the caller's order.  The chains are numbered as above: chain r K' + j is replica r of the j-th row in the order of the packed
+    masks, and so are the random streams."""
+    if _draw_method(method, sampler, replicas) is not None:
+        values, missing = _missing_rows(samples)
+        _check_holes(missing, method.max_hidden)  # (refused before a handle is opened)
+        with _Holes(values, missing) as holes:
+            with holes.draws(model, replicas, seed) as q:
+                states, order = q.spins(), q.order
+        states = states.reshape(-1, holes.K, holes.n)[:, holes.inverse].reshape(-1, holes.n)
+        return _lib.Problem(spins=states, order=order)
     sampler, (values, missing) = _impute_args(samples, sampler, replicas)
     with _Holes(values, missing) as holes:
         with holes.chains(model, sampler, replicas, seed, False) as q:

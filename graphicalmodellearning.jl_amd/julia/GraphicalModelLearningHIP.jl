@@ -448,6 +448,90 @@ function conditional_mode_masked(terms::Dict, samples::Array{T,2}; device::Integ
     end
 end
 
+"""
+    conditional_draw(terms::Dict, samples, hidden; replicas=1, seed=0, device=0)
+        -> states (K*replicas x H, Int8 +-1), energy (K*replicas), log_p (K*replicas)
+
+Exact draws of the spins `hidden` (1-based, at most 24) given the other spins of every row of the histogram `samples` (K x (1+n))
+(gml_conditional_draw, include/gml.h; Gumbel-max over the row's enumeration, no chain): row `r*K + k` (0-based) of the results is
+replica r of row k -- `states[c, a]` the value of the a-th hidden spin (ascending), `energy[c]` the unperturbed energy of the draw,
+`log_p[c]` its conditional log-probability.  Marshalling only.
+"""
+function conditional_draw(terms::Dict, samples::Array{T,2}, hidden::AbstractVector{<:Integer}; replicas::Integer=1, seed::Integer=0,
+                          device::Integer=0) where T <: Real
+    s = T <: AbstractFloat ? convert(Array{Float64,2}, samples) : convert(Array{Int64,2}, samples)
+    dtype = eltype(s) == Float64 ? GML_F64 : GML_I64
+    K, n = size(s, 1), size(s, 2) - 1
+    all(i -> 1 <= i <= n, hidden) && !isempty(hidden) && allunique(hidden) ||
+        throw(ArgumentError("conditional_draw: hidden must name distinct spins in 1:$n"))
+    replicas >= 1 || throw(ArgumentError("conditional_draw: replicas must be at least 1"))
+    mask = zeros(UInt8, n)
+    mask[hidden] .= 1
+    keymat, weights, stride = term_arrays(terms)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:gml_problem_create, libgml), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Cint, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+               s, dtype, K, n, K, 1 #= column-major =#, 2, 0, n, device, handle)
+    rc == GML_OK || error("gml_problem_create: $(lasterr())")
+    try
+        chains = K * replicas
+        states = Array{Int8}(undef, chains, length(hidden))    # C row-major [H][K replicas] == Julia (K replicas x H)
+        energy = Vector{Float64}(undef, chains)
+        log_p = Vector{Float64}(undef, chains)
+        rc = ccall((:gml_conditional_draw, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{UInt8}, Cint, UInt64, Ptr{Int8}, Ptr{Cdouble},
+                    Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, handle[], mask, replicas, seed, states, energy, log_p)
+        rc == GML_OK || error("gml_conditional_draw: $(lasterr())")
+        return states, energy, log_p
+    finally
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
+    end
+end
+
+"""
+    conditional_draw_masked(terms::Dict, samples; replicas=1, seed=0, device=0)
+        -> completed (K*replicas x n, Int8 +-1), energy (K*replicas), log_p (K*replicas)
+
+The same for data with holes (gml_conditional_draw_masked): a spin entry of `samples` (K x (1+n)) is -1, +1 or 0 = missing, at most 24
+missing per row; `completed[r*K + k, :]` (0-based) is row k with its missing entries drawn from their joint conditional distribution,
+the observed ones kept.  Two handles are made and destroyed, as in conditional_mode_masked.  Marshalling only.
+"""
+function conditional_draw_masked(terms::Dict, samples::Array{T,2}; replicas::Integer=1, seed::Integer=0,
+                                 device::Integer=0) where T <: Real
+    K, n = size(samples, 1), size(samples, 2) - 1
+    spins = samples[:, 2:end]
+    all(v -> v == -1 || v == 0 || v == 1, spins) || throw(ArgumentError("conditional_draw_masked: spin entries must be -1, +1 or 0"))
+    replicas >= 1 || throw(ArgumentError("conditional_draw_masked: replicas must be at least 1"))
+    evidence = Int8.(ifelse.(spins .== 0, 1, spins))
+    holes = Int8.(ifelse.(spins .== 0, -1, 1))
+    keymat, weights, stride = term_arrays(terms)
+    he = Ref{Ptr{Cvoid}}(C_NULL)
+    hm = Ref{Ptr{Cvoid}}(C_NULL)
+    create(bytes, h) = ccall((:gml_problem_create_spins, libgml), Cint,
+                             (Ptr{Cdouble}, Ptr{Int8}, Int64, Int64, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+                             C_NULL, bytes, K, n, 2, 0, n, device, h)
+    rc = create(permutedims(evidence), he)
+    rc == GML_OK || error("gml_problem_create_spins: $(lasterr())")
+    try
+        rc = create(permutedims(holes), hm)
+        rc == GML_OK || error("gml_problem_create_spins: $(lasterr())")
+        chains = K * replicas
+        completed = Array{Int8}(undef, chains, n)         # C row-major [n][K replicas] == Julia (K replicas x n)
+        energy = Vector{Float64}(undef, chains)
+        log_p = Vector{Float64}(undef, chains)
+        rc = ccall((:gml_conditional_draw_masked, libgml), Cint,
+                   (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Cint, UInt64, Ptr{Int8}, Ptr{Cdouble},
+                    Ptr{Cdouble}),
+                   keymat, stride, weights, length(weights), n, he[], hm[], replicas, seed, completed, energy, log_p)
+        rc == GML_OK || error("gml_conditional_draw_masked: $(lasterr())")
+        return completed, energy, log_p
+    finally
+        hm[] == C_NULL || ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), hm[])
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), he[])
+    end
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

@@ -2,7 +2,9 @@
 
 Every iteration completes the data under the current model -- the missing entries of a row are drawn from the model's conditional
 distribution given the row's observed entries, by the per-row masked chains (gml_problem_create_mcmc_terms_masked) -- and learns on
-the completed handle, started from the previous solution.  Iteration 0 completes under the empty model: coin flips, the baseline that
+the completed handle, started from the previous solution.  With ImputationEM(method=Exact()) the draws are exact instead: every row's
+missing entries are enumerated (gml_conditional_draw_masked, at most 24 per row), so the completions come from p(missing | observed)
+itself and no burn-in has to be guessed.  Iteration 0 completes under the empty model: coin flips, the baseline that
 shrinks every coupling towards zero.
 
 What the estimator is.  Data completed from p_theta*(missing | observed) are distributed as p_theta*, so the true model is a fixed
@@ -18,6 +20,7 @@ import numpy as np
 from . import _lib, inference
 from .factor_graph import FactorGraph, TermArray
 from .formulations import HIP, NLP, RISE, GMLFormulation, GMLMethod, multiRISE
+from .likelihood import Exact
 from .sampling import GlauberTermChains
 
 _learn = import_module(".learn", __package__)  # (the module: the package binds the name `learn` to the function)
@@ -26,10 +29,13 @@ _learn = import_module(".learn", __package__)  # (the module: the package binds 
 class ImputationEM:
     """iterations: imputations and solves, the coin-flip one included; replicas: completions of every row per iteration (all of them
     go into the solve); sampler: the GlauberTermChains of one imputation -- short by default, since every chain starts from the
-    row's observed spins and the model changes little between iterations."""
+    row's observed spins and the model changes little between iterations; method: None for those chains, or an Exact -- every
+    imputation is then an exact draw by enumeration of each row's missing spins (at most method.max_hidden <= 24 per row) and the
+    sampler plays no part."""
     iterations: int = 20
     replicas: int = 2
     sampler: GlauberTermChains = field(default_factory=lambda: GlauberTermChains(burn_in=10, thin=1, samples_per_chain=1))
+    method: Exact = None
 
 
 @dataclass
@@ -56,6 +62,11 @@ def _open_hip(values, missing, order, device):
 def _impute_hip(holes, model, sampler, replicas, seed, order):
     """a handle of the completed rows under `model`"""
     return holes.chains(model, sampler, replicas, seed, False, order=order)
+
+
+def _impute_exact_hip(holes, model, replicas, seed, order):
+    """a handle of the rows completed by exact draws under `model`"""
+    return holes.draws(model, replicas, seed, order=order)
 
 
 def _solve_hip(prob, formulation, x0, method):
@@ -109,8 +120,12 @@ def learn_missing(samples, formulation=None, method=None, em=None, seed=0):
         raise TypeError(f"em is an ImputationEM, not {type(em).__name__}")
     if int(em.iterations) < 1 or int(em.replicas) < 1:
         raise ValueError(f"ImputationEM: iterations and replicas must be at least 1 (given {em.iterations}, {em.replicas})")
-    sampler = inference._sampler(em.sampler)
+    if em.method is not None and not isinstance(em.method, Exact):
+        raise TypeError(f"ImputationEM: method is None (chains) or an Exact, not {type(em.method).__name__}")
+    sampler = None if em.method is not None else inference._sampler(em.sampler)
     values, missing = inference._missing_rows(samples)
+    if em.method is not None:
+        inference._check_holes(missing, em.method.max_hidden)  # (refused before a handle is opened)
     if not missing.any():
         model = _learn.learn(samples, formulation, method_given)
         its = int((method_given.stats if hasattr(method_given, "stats") else {}).get("iterations", 0) or 0)
@@ -119,12 +134,15 @@ def learn_missing(samples, formulation=None, method=None, em=None, seed=0):
     order = int(formulation.interaction_order) if isinstance(formulation, multiRISE) else 2
     device = 0 if method.device is None else int(method.device)
     # (module attributes, looked up per call: the host tests substitute the steps, as with _local_solve_hip in learn.py)
-    open_, impute, solve, assemble = _open_hip, _impute_hip, _solve_hip, _model_of_rows
+    open_, impute, impute_exact, solve, assemble = _open_hip, _impute_hip, _impute_exact_hip, _solve_hip, _model_of_rows
     trace, rows, model = [], None, {(1,): 0.0}  # the empty model: every field is 0, every update a coin flip
     holes = open_(values, missing, order, device)
     try:
         for t in range(int(em.iterations)):
-            completed = impute(holes, model, sampler, int(em.replicas), int(seed) + t, order)
+            if em.method is not None:
+                completed = impute_exact(holes, model, int(em.replicas), int(seed) + t, order)
+            else:
+                completed = impute(holes, model, sampler, int(em.replicas), int(seed) + t, order)
             try:
                 new, st = solve(completed, formulation, rows, method)
             finally:

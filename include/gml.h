@@ -594,6 +594,47 @@ int gml_conditional_mode_masked(const int32_t *keys, int key_stride, const doubl
                                 double *energy /* [K] or NULL */, double *log_p /* [K] or NULL */);
 
 /*
+ * gml_conditional_draw, gml_conditional_draw_masked -- exact draws of every row's hidden spins from P(x_H | x_O), no chain and no
+ * burn-in: the enumeration of gml_conditional_mode[_masked] on energies perturbed by Gumbel noise (Gumbel-max: the state of largest
+ * E(s) + G(s), G i.i.d. standard Gumbel, is a draw from softmax(E)).  The yardstick for the draws of the conditional chains, and the
+ * completion step of learning from data with holes.
+ * Model, evidence, hidden / mask, E_k, limits: exactly those of gml_conditional_exact and gml_conditional_exact_masked.
+ * Chains.  chains = K * replicas.  Chain c = r K + k is replica r of evidence row k, the numbering of gml_conditional_means.
+ * States.  Row k hides h_k <= 24 spins.  Local state s in [0, 2^h_k): bit j <-> the j-th hidden spin of the row, ascending; a set bit =
+ *   spin -1.
+ * Energy.  E_k(s) is that of gml_conditional_exact, over all terms, with the FP64 weights as given.
+ * Perturbation.  u = u01(seed, c, s) of gml_rng.h (stream = c, counter = s); g = -log(-log u) in FP64, u = 0 gives -inf;
+ *   key(c, s) = E_k(s) + g.
+ * Draw.  The draw of chain c is the state of largest key; equal keys go to the lower state (the order of the mode).
+ * A hidden spin in no term is a coin flip here (both of its values have the same energy and their own g), where the mode makes it +1.
+ * A row without a hidden spin (masked form) comes back as it is, with energy E(row) and log_p 0.
+ * Exactness.  Exact up to the 53 bits of u: g <= -log(-log(1 - 2^-53)) = 36.74, so a state whose probability is below about 2^-53 of
+ *   the mode's can never be drawn; every other state is drawn with its probability up to that resolution.
+ * Outputs, per chain (host).
+ *   states: the values (+-1) of the hidden spins in the draw.  gml_conditional_draw: [H][K * replicas], hidden-major, the hidden spins
+ *     ascending.  gml_conditional_draw_masked: [n][K * replicas], an observed entry holding its evidence value.
+ *   energy [K * replicas] (or NULL): the UNPERTURBED E_k of the drawn state, the row's constant included.
+ *   log_p [K * replicas] (or NULL): energy - log_w[k] = log P(x_H = the draw | x_O), with log_w[k] the same bits
+ *     gml_conditional_exact[_masked] returns for that row.  With log_p NULL the device computes no exponential of the sums and no
+ *     second transform; states and energy are the same bytes either way.
+ * Determinism.  A chain's result is a pure function of (model, row k's bits, its hidden set, seed, c): not of the grid, the other rows,
+ *   the slab, how the replicas of a row were batched, or which outputs were asked for; the same bytes on every call.  A mask handle
+ *   whose rows all equal one vector gives, byte for byte, what gml_conditional_draw gives with that vector.
+ * GML_EINVAL and GML_EUNSUPPORTED: the cases of gml_conditional_mode[_masked] in their order, with replicas < 1 after "states is NULL".
+ * Cost.  That of gml_conditional_mode[_masked] per row and distinct hidden set (planning is per hidden set, not per replica), plus one
+ *   hash and two FP64 logarithms per state and replica; eight replicas of a row share one pass over its states.  Measured times in
+ *   DESIGN 3.21.
+ */
+int gml_conditional_draw(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, gml_problem *evidence,
+                         const uint8_t *hidden /* [n], host */, int replicas, uint64_t seed,
+                         int8_t *states /* [H][K * replicas], hidden-major, hidden spins ascending */,
+                         double *energy /* [K * replicas] or NULL */, double *log_p /* [K * replicas] or NULL */);
+int gml_conditional_draw_masked(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                                gml_problem *evidence, gml_problem *mask, int replicas, uint64_t seed,
+                                int8_t *states /* [n][K * replicas]; an observed entry holds its evidence value */,
+                                double *energy /* [K * replicas] or NULL */, double *log_p /* [K * replicas] or NULL */);
+
+/*
  * gml_problem_create_sampled_hist -- sample AND histogram on the device: what `sample(gm, N)` returns is the countmap of the
  * draws (sampling.jl:52-54: one row per distinct configuration, column 1 = its count).  Same term-list arguments as above
  * (mcmc_sweeps = 0: exact sampling, > 0: Glauber chains); n <= 64, N < 2^31.  The N draws become 64-bit keys, are radix-sorted
