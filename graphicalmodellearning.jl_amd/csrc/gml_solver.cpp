@@ -280,6 +280,23 @@ struct Solver {
         HIPCHK(hipStreamSynchronize(st));
         return GML_OK;
     }
+    // the matrix-free events of the iteration (TRC_*).  (The reference holds until the next event is added.)
+    TrajCgEvent &rec_cg(int tag) {
+        rec->its.back().cg.push_back(TrajCgEvent{tag, {}, {}});
+        return rec->its.back().cg.back();
+    }
+    int rec_rows_of(TrajCgEvent &ev, const double *dev, const std::vector<int> &rows) { // whole rows of a [Rp][Qp] device array
+        std::vector<double> all(nd);
+        RCCHK(rec_download(all.data(), dev, sizeof(double) * nd));
+        for (int r : rows) ev.dv.insert(ev.dv.end(), all.begin() + (size_t)r * Qp, all.begin() + (size_t)(r + 1) * Qp);
+        return GML_OK;
+    }
+    int rec_cgstate(TrajCgEvent &ev, const std::vector<int> &rows) {
+        std::vector<CgState> c((size_t)Rp);
+        RCCHK(rec_download(c.data(), dCg, sizeof(CgState) * Rp));
+        for (int r : rows) ev.dv.insert(ev.dv.end(), {c[r].rs, c[r].rs0, c[r].pHp, c[r].rz});
+        return GML_OK;
+    }
 
     Solver(gml_problem *p_, int form, const gml_opts &o_, double lam)
         : p(p_), d(p_->d), formulation(form), o(o_), st(p_->st), R(p_->node1 - p_->node0), Rp(gml_round_up(R, 32)), Qp(p_->d.Qp), P(p_->P),
@@ -1086,9 +1103,61 @@ int Solver::direction_blocks(const std::vector<int> &cg_rows) {
         if (hrc) return fail(hrc, "%s", err.empty() ? "int8 Hessian: working set above 512 entries" : err.c_str());
     }
     if (!gml_is_i8(prec)) launch_hess_f64(d, p->dV, dMt + R, dFidx, dMt, dHoff, (int)R, capP, formulation, Kh, kstride, dH, st);
+    if (rec && ntiles > 0) { // what the tiles were built from, and the blocks before their inversion
+        TrajCgEvent &ev = rec_cg(TRC_BLOCKS);
+        const size_t ncg = cg_rows.size();
+        ev.iv = {(int64_t)ncg, T, ntiles, Kh, kstride, Qp, prec, P};
+        for (int r : cg_rows) ev.iv.push_back(r);
+        for (int r : cg_rows) ev.iv.push_back(nW[r]);
+        std::vector<long long> t0d((size_t)R);
+        RCCHK(rec_download(t0d.data(), dT0m, sizeof(long long) * R));
+        for (int r : cg_rows) ev.iv.push_back(t0d[r]);
+        std::vector<int> tv((size_t)(2 * ntiles)), fv((size_t)ntiles * T);
+        RCCHK(rec_download(tv.data(), dVm, sizeof(int) * 2 * ntiles)); // (vm | wrow)
+        RCCHK(rec_download(fv.data(), dFV, sizeof(int) * ntiles * T));
+        ev.iv.insert(ev.iv.end(), tv.begin(), tv.end());
+        ev.iv.insert(ev.iv.end(), fv.begin(), fv.end());
+        std::vector<uint8_t> kd((size_t)R * Qp);
+        RCCHK(rec_download(kd.data(), kind, kd.size()));
+        for (int r : cg_rows) ev.iv.insert(ev.iv.end(), kd.begin() + (size_t)r * Qp, kd.begin() + (size_t)(r + 1) * Qp);
+        // the unit and the largest magnitude of the rows' V planes (a later objective pass overwrites them)
+        const double *dtau = nullptr;
+        const unsigned *dmm = nullptr;
+        i8_slot_results(p->i8ws, 0, &dtau, &dmm);
+        int smax = 0;
+        for (int r : cg_rows) smax = std::max(smax, slots.slot(r));
+        std::vector<double> tau((size_t)smax + 1, 0.0);
+        std::vector<unsigned> mm((size_t)smax + 1, 0u);
+        if (dtau) RCCHK(rec_download(tau.data(), dtau, sizeof(double) * tau.size()));
+        if (dmm) RCCHK(rec_download(mm.data(), dmm, sizeof(unsigned) * mm.size()));
+        for (int r : cg_rows) ev.iv.push_back(mm[(size_t)slots.slot(r)]);
+        for (int r : cg_rows) { // the column of every parameter of the result's layout
+            if (p->order == 2) {
+                for (int64_t j = 0; j < P; ++j) ev.iv.push_back(j == p->node0 + r ? d.cconst : j);
+            } else {
+                NodeLayout L;
+                gml_build_layout(p, p->node0 + r, L);
+                ev.iv.insert(ev.iv.end(), L.cols.begin(), L.cols.begin() + P);
+            }
+        }
+        ev.dv.push_back(hscale);
+        for (int r : cg_rows) ev.dv.push_back(s1[r]);
+        for (int r : cg_rows) ev.dv.push_back(tau[(size_t)slots.slot(r)]);
+        RCCHK(rec_rows_of(ev, X, cg_rows));
+        RCCHK(rec_rows_of(ev, PG, cg_rows));
+        RCCHK(rec_rows_of(ev, G, cg_rows));
+        const size_t nb = (size_t)ntiles * T * T, at = ev.dv.size();
+        ev.dv.resize(at + 2 * nb);
+        RCCHK(rec_download(ev.dv.data() + at, dH + tile_base, sizeof(double) * nb));
+    }
     if (ntiles > 0) {
         trace("tile inverses");
         launch_tile_inverse(T, dH, dHoffV + R, dVm, dWrow, dS1, formulation == GML_LOGRISE ? 1.0 : 0.0, dgV, ntiles, st);
+    }
+    if (rec && ntiles > 0) { // ... and the inverses the preconditioner applies
+        TrajCgEvent &ev = rec->its.back().cg.back();
+        const size_t nb = (size_t)ntiles * T * T;
+        RCCHK(rec_download(ev.dv.data() + ev.dv.size() - nb, dH + tile_base, sizeof(double) * nb));
     }
     HIPCHK(hipGetLastError());
     ++stats.hessian_passes;
@@ -1190,6 +1259,17 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         return GML_OK;
     };
     RCCHK(set_live(cg_rows));
+    if (rec) {
+        TrajCgEvent &ev = rec_cg(TRC_GROUP);
+        int64_t mw = 1;
+        for (int r : cg_rows) mw = std::max<int64_t>(mw, -(int64_t)sel[r].m);
+        ev.iv = {subsample ? 1 : 0, (int64_t)cg_rows.size(), mw};
+        for (int r : cg_rows) ev.iv.push_back(r);
+        for (int r : cg_rows) ev.iv.push_back(sel[r].nviol);
+        for (int r : cg_rows) ev.iv.push_back(sel[r].nsupp);
+        for (int r : cg_rows) ev.dv.push_back(kkt[r]);
+        for (int r : cg_rows) ev.dv.push_back(Z[r]);
+    }
     // the rows' lists of W (k_cg_tiles, direction_blocks): the per-step vector kernels walk them instead of the 131 k columns
     if (!dNw) HIPCHK(A.get(&dNw, (size_t)Rp));
     HIPCHK(stg.h2d(dNw, nW.data(), sizeof(int) * R));
@@ -1204,7 +1284,7 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
     // not move; one split plan serves every step of this CG solve (one operator).
     int64_t kchunk = 0, kpart = 0;
     // the split plan and the scales of the products over 1/ksub of the configurations
-    auto set_plan = [&](int ksub, size_t nrows) -> int {
+    auto set_plan = [&](int ksub, size_t nrows, int where, int round, int ci) -> int {
         int nsplit = 0;
         i8_split_plan(d, (int)(gml_round_up((int64_t)nrows, 32) / 32), ksub, &kchunk, &kpart, &nsplit);
         double wsub = 0;
@@ -1219,6 +1299,12 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
             for (int64_t r = 0; r < Rp; ++r) sc[r] = r < R && formulation == GML_LOGRISE ? 1.0 / Z[r] : 1.0;
         }
         HIPCHK(stg.h2d(dS1cg, sc.data(), sizeof(double) * Rp)); // (the sub-sample's weight replaces the full sum)
+        if (rec) {
+            TrajCgEvent &ev = rec_cg(TRC_PLAN);
+            ev.iv = {where, round, ci, ksub, kchunk, kpart, nsplit, gml_round_up((int64_t)nrows, 32) / 32, Rp};
+            ev.dv.push_back(wsub);
+            ev.dv.insert(ev.dv.end(), sc.begin(), sc.end());
+        }
         return GML_OK;
     };
     int64_t maxW = 1;
@@ -1226,7 +1312,7 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
     {
         int ksub = o.hv_subsample > 0 ? o.hv_subsample : (int)std::min<int64_t>(8, std::max<int64_t>(1, p->K / (32 * maxW)));
         if (!subsample) ksub = 1;
-        RCCHK(set_plan(ksub, cg_rows.size()));
+        RCCHK(set_plan(ksub, cg_rows.size(), 0, 0, 0));
     }
     // Relaxed products (inexact Krylov: Simoncini & Szyld 2003, van den Eshof & Sleijpen 2004).  The error a product may carry
     // without moving the attainable residual grows like 1 / |r_j|: the first steps of an exact-curvature solve need every
@@ -1246,7 +1332,7 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
     const bool sparse_ok = p->i8ws != nullptr && formulation != GML_RPLE && hv_lf == 2 && hv_lb == 2 && d.ko <= 2 && maxW <= 65536 &&
                            dT0m != nullptr;
     // Hout = (sum_k h_k x_k x_k^T) theta for the listed rows: an hv pass over slots [0, n) of the u-plane workspace
-    auto hv_pass = [&](const std::vector<int> &rows, const double *theta, double *Hout) -> int {
+    auto hv_pass = [&](const std::vector<int> &rows, const double *theta, double *Hout, TrajCgEvent *ev) -> int {
         const int64_t n = (int64_t)rows.size(), np = gml_round_up(n, 32);
         int64_t sumW = 0;
         for (int r : rows) sumW += nW[r];
@@ -1260,6 +1346,20 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         }
         for (int64_t g = 0; g < np / 32; ++g) ctl[3 * np + g] = (int)g;
         HIPCHK(stg.h2d(dHv, ctl.data(), sizeof(int) * ctl.size()));
+        if (ev) { // (the head of a TRC_STEP / TRC_RESOLVE event: the route, the rows, the control block as uploaded)
+            ev->iv.insert(ev->iv.end(), {sparse ? 1 : 0, n, np});
+            ev->iv.insert(ev->iv.end(), rows.begin(), rows.end());
+            ev->iv.insert(ev->iv.end(), ctl.begin(), ctl.end());
+            RCCHK(rec_rows_of(*ev, theta, rows));
+            int smax = 0; // the unit of the rows' V planes (a later objective pass overwrites it)
+            for (int r : rows) smax = std::max(smax, slots.slot(r));
+            const double *dtau = nullptr;
+            const unsigned *dmm = nullptr;
+            i8_slot_results(p->i8ws, 0, &dtau, &dmm);
+            std::vector<double> tau((size_t)smax + 1, 0.0);
+            if (dtau) RCCHK(rec_download(tau.data(), dtau, sizeof(double) * tau.size()));
+            for (int r : rows) ev->dv.push_back(slots.slot(r) >= 0 ? tau[(size_t)slots.slot(r)] : 0.0);
+        }
         std::string err;
         int rc;
         if (sparse) {
@@ -1307,13 +1407,24 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         for (int ci = 0; ci < maxcg && !live.empty(); ++ci) {
             if (round == 0)
                 for (const auto &sk : relax)
-                    if (ci == sk.first) RCCHK(set_plan(sk.second, live.size()));
-            RCCHK(hv_pass(live, Pv, Hp));
+                    if (ci == sk.first) RCCHK(set_plan(sk.second, live.size(), 1, round, ci));
+            TrajCgEvent *ev = nullptr;
+            if (rec) {
+                ev = &rec_cg(TRC_STEP);
+                ev->iv = {round, ci};
+            }
+            RCCHK(hv_pass(live, Pv, Hp, ev));
+            if (ev) {
+                RCCHK(rec_rows_of(*ev, Rv, live));
+                RCCHK(rec_rows_of(*ev, Hp, live));
+            }
             RCCHK(upload_rows(live, dRows2));
             launch_pcg_step(dRows2, (int)live.size(), G, Wm, Qp, dS1cg, s2, Hp, D, Rv, Pv, dCg, wl, st);
             HIPCHK(stg.d2h(cgs.data(), dCg, sizeof(CgState) * Rp));
             HIPCHK(hipGetLastError());
             HIPCHK(stg.sync());
+            if (ev)
+                for (int r : live) ev->dv.insert(ev->dv.end(), {cgs[r].rs, cgs[r].rs0, cgs[r].pHp, cgs[r].rz});
             std::vector<int> nxt;
             for (int r : live) {
                 // a row that is still admitting violators needs a step that is good at the scale of its largest violation, not more
@@ -1333,6 +1444,12 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
             launch_tile_apply(kTile, dH + tile_base, dFV, dVm, dWrow, dLive, ntiles, Qp, Rv, Zv, st);
             launch_pcg_dir(dRows2, (int)live.size(), Qp, Wm, Rv, Zv, Pv, 0, dCg, wl, st);
         }
+        if (rec) {
+            TrajCgEvent &ev = rec_cg(TRC_ROUND_END);
+            ev.iv = {round, (int64_t)cur.size()};
+            ev.iv.insert(ev.iv.end(), cur.begin(), cur.end());
+            RCCHK(rec_rows_of(ev, D, cur));
+        }
         if (round >= face_rounds) break;
         // orthant faces (gml_solver.hip, k_pcg_faces): the rows whose projected step would lose a noticeable part of its
         // predicted decrease to the clipping solve again without the clipped coordinates
@@ -1350,14 +1467,30 @@ int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
         if (o.verbose >= 2)
             fprintf(stderr, "[gml]   cg faces (round %d): %lld coordinates fixed at zero in %zu rows; %zu rows solve again\n", round, (long long)nfixed,
                     cur.size(), again.size());
+        if (rec) {
+            TrajCgEvent &ev = rec_cg(TRC_FACES);
+            ev.iv = {round, (int64_t)cur.size(), (int64_t)again.size()};
+            ev.iv.insert(ev.iv.end(), cur.begin(), cur.end());
+            for (int r : cur) ev.iv.push_back(faces[r].nfixed);
+            ev.iv.insert(ev.iv.end(), again.begin(), again.end());
+            for (int r : cur) ev.dv.push_back(faces[r].mass);
+            for (int r : cur) ev.dv.push_back(faces[r].total);
+        }
         if (again.empty()) break;
         cur.swap(again);
-        if (!relax.empty()) RCCHK(set_plan(1, cur.size())); // (the re-solve starts from the exact residual of the clipped step)
-        RCCHK(hv_pass(cur, D, Hp));
+        if (!relax.empty()) RCCHK(set_plan(1, cur.size(), 2, round + 1, 0)); // (the re-solve starts from the exact residual of the clipped step)
+        TrajCgEvent *ev = nullptr;
+        if (rec) {
+            ev = &rec_cg(TRC_RESOLVE);
+            ev->iv = {round + 1};
+        }
+        RCCHK(hv_pass(cur, D, Hp, ev));
+        if (ev) RCCHK(rec_rows_of(*ev, Hp, cur));
         RCCHK(set_live(cur));
         launch_pcg_resid(dRows2, (int)cur.size(), PG, G, Qp, dS1cg, s2, Hp, D, Wm, Rv, dCg, st);
         launch_tile_apply(kTile, dH + tile_base, dFV, dVm, dWrow, dLive, ntiles, Qp, Rv, Zv, st);
         launch_pcg_dir(dRows2, (int)cur.size(), Qp, Wm, Rv, Zv, Pv, 1, dCg, wl, st);
+        if (ev) RCCHK(rec_cgstate(*ev, cur));
     }
     return GML_OK;
 }
@@ -1436,7 +1569,10 @@ int Solver::line_search() {
                 fprintf(stderr, "[gml]   row %d: ls %d alpha %.3g nreg %d ft %.12e Fobj %.12e dd %.3e fnt %.3e back %.3e ok %d\n", r, ls, alpha[r],
                         (int)nreg[r], ft[r], Fobj[r], dd[r], fnt[r], trial[r].back, (int)ok);
             if (ok) {
-                dref[r] = 0.0; // the iterate moves onto the point the scale was measured at
+                // int8 passes: the iterate moves onto the point the scale was measured at.  FP64 phase: its trial passes measure no scale,
+                // so the iterate moves away from where the last int8 pass of the row measured one -- the objective pass that direction_blocks
+                // borrows for the matrix-free rows must allow for that distance, or its weights leave the fixed-point range
+                dref[r] = gml_is_i8(prec) ? 0.0 : dref[r] + stepn[r];
                 f[r] = ft[r];
                 fn[r] = fnt[r];
                 Z[r] = Zt[r];

@@ -41,8 +41,39 @@ enum { // per local row (doubles; the integers among them are exact)
     TRR_TRIALS, TRR_ALPHA /* of the accepting trial; of the last one for a row that was not accepted */, TRR_NREG /* of that trial */,
     TRR_FULL /* the accepting trial was a full pass (0: forward only, its gradient pass followed) */, TRR_ACCEPTED, TRR_GAVE_UP,
     TRR_N = 24 };
+// What the matrix-free half of an iteration did (direction_blocks, newton_cg_group), in order, for tests/test_gpu_newton_cg_trajectory.py:
+// a list of events, each a tag, integers and doubles.  n = rows of the event, np = n rounded up to 32, ctl = the control block of the
+// product as uploaded (row [np] | node0 + row [np] | plane slot [np] | node tile [np / 32] | 4 unused), rows of vectors are whole rows of Qp.
+enum {
+    // iv: ncg, T, ntiles, Kh, kstride, Qp, prec, P | cg_rows [ncg] | nW [ncg] | t0 [ncg] | vm [ntiles] | wrow [ntiles] (t0, vm, wrow: the device's
+    //     copies) | FV [ntiles T] as k_cg_tiles wrote it | kind [ncg Qp] | mmax [ncg] of the rows' V planes | the column of every parameter
+    //     of the result's layout [ncg P]
+    // dv: hscale | s1 [ncg] | tau [ncg], the unit of the rows' V planes | X [ncg Qp] | PG [ncg Qp] | G [ncg Qp] | the tile blocks of dH before launch_tile_inverse [ntiles T T] | after
+    TRC_BLOCKS = 0,
+    // iv: coarse (1) or fine (0), n, maxW | rows [n] | nviol [n] | nsupp [n];  dv: kkt [n] | Z [n]
+    TRC_GROUP,
+    // iv: where (0 before step 0, 1 at step ci of round 0, 2 before a face re-solve), round, ci, ksub, kchunk, kpart (as the products get
+    //     it), nsplit, node tiles the plan was made for, Rp;  dv: wsub | sc [Rp] as uploaded
+    TRC_PLAN,
+    // iv: round, ci, route (1 entry by entry, 0 GEMM), n, np | live [n] | ctl;  dv: Pv [n Qp] | tau [n], the unit of the rows' V planes | Rv [n Qp] before the step | the raw product Hp [n Qp] | CgState [n 4]
+    // after the step
+    TRC_STEP,
+    // iv: round, n | rows of the round [n];  dv: D [n Qp] after the last step of the round
+    TRC_ROUND_END,
+    // iv: round, n, nagain | rows of the round [n] | nfixed [n] | again [nagain];  dv: mass [n] | total [n]
+    TRC_FACES,
+    // iv: round (the one that begins), route, n, np | rows [n] | ctl;  dv: D [n Qp] the product's vector | tau [n] | the raw product Hp [n Qp] |
+    // CgState [n 4] after the residual and the first direction
+    TRC_RESOLVE
+};
+struct TrajCgEvent {
+    int tag;
+    std::vector<int64_t> iv;
+    std::vector<double> dv;
+};
 struct TrajIter {
     double hdr[TRH_N];
+    std::vector<TrajCgEvent> cg; // matrix-free rows only (empty: the iteration had none)
     std::vector<double> rows; // [R][TRR_N]
     std::vector<int> F;       // [R][capP]: the working sets as k_select left them (F[0..m) of the Cholesky rows)
     std::vector<double> X;    // [R][Qp]: the iterates after the line search (empty: no line search)

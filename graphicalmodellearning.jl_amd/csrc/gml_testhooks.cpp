@@ -82,6 +82,35 @@ extern "C" int gml_test_traj_iter(int i, double *hdr, double *rows, int *F, doub
     if (has_x) *has_x = !t.X.empty();
     return GML_OK;
 }
+// the matrix-free events of record i (gml_solver.h: TRC_*).  gml_test_traj_cg_count: *n = how many; gml_test_traj_cg_event: dims [3] = tag,
+// integers, doubles of event e; gml_test_traj_cg_data: copies them (a NULL output is skipped)
+static const TrajCgEvent *traj_cg_event(int i, int e) {
+    if (i < 0 || (size_t)i >= g_traj.its.size() || e < 0 || (size_t)e >= g_traj.its[(size_t)i].cg.size()) {
+        fail(GML_EINVAL, "no event %d in iteration %d of the record", e, i);
+        return nullptr;
+    }
+    return &g_traj.its[(size_t)i].cg[(size_t)e];
+}
+extern "C" int gml_test_traj_cg_count(int i, int64_t *n) {
+    if (!n || i < 0 || (size_t)i >= g_traj.its.size()) return fail(GML_EINVAL, "no iteration %d in the record of %zu", i, g_traj.its.size());
+    *n = (int64_t)g_traj.its[(size_t)i].cg.size();
+    return GML_OK;
+}
+extern "C" int gml_test_traj_cg_event(int i, int e, int64_t *dims) {
+    const TrajCgEvent *ev = traj_cg_event(i, e);
+    if (!ev || !dims) return GML_EINVAL;
+    dims[0] = ev->tag;
+    dims[1] = (int64_t)ev->iv.size();
+    dims[2] = (int64_t)ev->dv.size();
+    return GML_OK;
+}
+extern "C" int gml_test_traj_cg_data(int i, int e, int64_t *iv, double *dv) {
+    const TrajCgEvent *ev = traj_cg_event(i, e);
+    if (!ev) return GML_EINVAL;
+    if (iv && !ev->iv.empty()) std::memcpy(iv, ev->iv.data(), sizeof(int64_t) * ev->iv.size());
+    if (dv && !ev->dv.empty()) std::memcpy(dv, ev->dv.data(), sizeof(double) * ev->dv.size());
+    return GML_OK;
+}
 // from_best [R]: 1 where finish took the row from the best iterate, 0 where from the last
 extern "C" int gml_test_traj_finish(unsigned char *from_best) {
     if (!from_best || g_traj.from_best.empty()) return fail(GML_EINVAL, "the recorded solve did not reach its finish");

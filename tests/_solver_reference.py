@@ -289,18 +289,22 @@ def solve_faces(B, pg, x, kind, share, rounds, fix=None, dfix=None):
 class Pcg:
     """Preconditioned CG on W = {c: parameter, x_c != 0 or pg_c != 0} of B = s1 Hd - s2 g g^T, B d = -pg, preconditioned by the
     inverses of the diagonal blocks of T consecutive entries of W in column order.  The blocks of the original W stay when faces
-    shrink W (the mask Wm): z is masked instead.  All arithmetic in `dtype`."""
+    shrink W (the mask Wm): z is masked instead.  All arithmetic in `dtype`.
 
-    def __init__(self, Hd, s1, s2, x, pg, g, kind, T, dtype=np.float64):
+    The products can come from outside (the cut the tests make at the device's own recorded products): step(hp) / update(hp) and
+    faces(hd) take Hd @ p and Hd @ d as given, and Minv -- one inverted block per tile, [T][T] or larger with the tile in the leading
+    corner -- replaces the inverses of Hd's blocks; Hd may then be None.  With the products it would form itself, the bits are the same."""
+
+    def __init__(self, Hd, s1, s2, x, pg, g, kind, T, dtype=np.float64, Minv=None):
         self.dt = dtype
-        self.Hd, self.s1, self.s2 = np.asarray(Hd, dtype=dtype), dtype(s1), dtype(s2)
+        self.Hd, self.s1, self.s2 = None if Hd is None else np.asarray(Hd, dtype=dtype), dtype(s1), dtype(s2)
         self.x, self.pg, self.g, self.kind = x, np.asarray(pg, dtype=dtype), np.asarray(g, dtype=dtype), kind
         Qp = len(x)
         inW = (kind != 0) & ((x != 0) | (pg != 0))
         self.W = np.flatnonzero(inW)
         self.tiles = [self.W[a:a + T] for a in range(0, len(self.W), T)]
-        self.Minv = []
-        for t in self.tiles:
+        self.Minv = [] if Minv is None else [np.asarray(Mi, dtype=dtype)[:len(t), :len(t)] for t, Mi in zip(self.tiles, Minv)]
+        for t in (self.tiles if Minv is None else []):
             A = self.s1 * self.Hd[np.ix_(t, t)] - self.s2 * np.outer(self.g[t], self.g[t])
             self.Minv.append(np.asarray(np.linalg.inv(A.astype(np.float64)), dtype=dtype) if dtype is np.float64 else _inv_ld(A))
         self.Wm = inW.copy()
@@ -325,26 +329,36 @@ class Pcg:
         be = self.rz / rzo if (not first and rzo > 0) else self.dt(0)
         self.p[self.W] = np.where(self.Wm[self.W], self.z[self.W] + (0 if first else be * self.p[self.W]), 0)
 
-    def step(self):
-        hp = self.Hd @ self.p
+    def step(self, hp=None):
+        self.update(hp)
+        self.advance()
+
+    def update(self, hp=None, pHp=None):
+        """k_pcg_step: d, r and the scalars pHp, rs (rz is still the one the step length was taken from).  pHp: the step length is taken
+        from this value instead of the model's own sum, which stays in pHp_own (a cut after the kernel's first reduction)"""
+        hp = self.Hd @ self.p if hp is None else np.asarray(hp, dtype=self.dt)
         gp = self.g[self.W] @ self.p[self.W] if self.s2 != 0 else self.dt(0)
         h = np.where(self.Wm, self.s1 * hp - self.s2 * self.g * gp, 0)
-        self.pHp = self.p[self.W] @ h[self.W]
+        self.pHp_own = self.p[self.W] @ h[self.W]
+        self.pHp = self.pHp_own if pHp is None else self.dt(pHp)
         al = self.rz / self.pHp if self.pHp > 0 else self.dt(0)
         self.d[self.W] += al * self.p[self.W]
         self.r[self.W] -= al * h[self.W]
         self.rs = self.r[self.W] @ self.r[self.W]
+
+    def advance(self):
+        """the preconditioner and the next direction (a row that stays live)"""
         self.apply()
         self.direction(False)
 
-    def faces(self):
+    def faces(self, hd=None):
         """k_pcg_faces, then the residual of the shrunk system (k_pcg_resid) and the first direction.  Returns dict(n, mass, total, margin)."""
         d64 = self.d.astype(np.float64)
         pg64 = self.pg.astype(np.float64)
         cand, fixed, mass, total, margin = face_candidates(self.x, d64, pg64, self.kind, self.Wm.copy())
         self.d = np.where(cand, fixed.astype(self.dt), self.d)
         self.Wm &= ~cand
-        hd = self.Hd @ self.d
+        hd = self.Hd @ self.d if hd is None else (hd(self.d) if callable(hd) else np.asarray(hd, dtype=self.dt))
         gd = self.g @ self.d if self.s2 != 0 else self.dt(0)
         self.r = np.where(self.Wm, -self.pg - (self.s1 * hd - self.s2 * self.g * gd), 0)
         self.rs = self.r @ self.r
