@@ -1,5 +1,5 @@
-// Internal host-side interface of libgml_hip shared by gml_host.cpp (handles, packing, operator) and gml_solver.cpp
-// (the l1 solver behind gml_learn).  Not part of the C ABI.
+// Internal host-side interface of libgml_hip shared by gml_host.cpp (handles, packing, operator) and gml_solver.cpp,
+// gml_newton_cg.cpp (the l1 solver behind gml_learn).  Not part of the C ABI.
 #pragma once
 #include "../../include/gml.h"
 #include "gml_dev.h"
@@ -52,7 +52,7 @@ struct gml_problem {
     double *hTh = nullptr, *hG = nullptr, *hF = nullptr; // pinned staging (ws_rows x Qp, ws_rows)
     // int8-limb path workspace (gml_i8_pass.hip, allocated lazily)
     void *i8ws = nullptr;
-    // pinned staging arena of the solver's small control / scalar transfers (gml_solver.cpp), allocated on first use
+    // pinned staging arena of the solver's small control / scalar transfers (gml_solver_impl.h: Stage), allocated on first use
     char *stage = nullptr;
     size_t stage_bytes = 0;
     // device-pointer operator calls (gml_operator.cpp: objgrad_dev / hessvec_dev): parameter-slot -> column table of the node list

@@ -1,5 +1,6 @@
 // libgml_hip, host side: the operator boundary -- gml_objgrad_batch / gml_hessvec_batch (GraphicalModelLearning.jl:191-208,
 // :221-233) and the timing hooks of the benchmark: orchestration of the device passes for host-pointer callers.
+#include "gml_cg_rules.h"
 #include "gml_internal.h"
 #include "gml_solver.h"
 #include "gml_pack.h"
@@ -660,13 +661,13 @@ extern "C" int gml_test_hessian_blocks(gml_problem *p, int formulation, int prec
 }
 
 // Test hook (not part of include/gml.h): the Hessian call of one solver iteration on caller-given blocks -- the flow of
-// gml_test_hessian_blocks (device_pass at theta, rescaled re-runs included, then i8_hessian) with what run_group (gml_solver.cpp) can
+// gml_test_hessian_blocks (device_pass at theta, rescaled re-runs included, then i8_hessian) with what direction_blocks (gml_newton_cg.cpp) can
 // hand the call and that hook cannot: a ragged size per row (mtV[r] tiles of 32, 0 = the row is skipped), blocks at caller-given
 // offsets, and optionally the preconditioner tiles of matrix-free rows.
 //   cols [nrows][cap]: every row's list, parameter indices in the reference's order; all cap entries are translated and uploaded (the
 //                      kernels read the first 32 mtV[r] of them), so the padding is the caller's
 //   ntiles > 0: T in {64, 128}; tcols [ntiles][T] the tiles' lists, parameters of row wrow[t] in the reference's order; vm [ntiles]
-//               (entries in use: uploaded with the control block as run_group lays it out -- hoffV | mtV | vm | wrow | hflag -- the Hessian
+//               (entries in use: uploaded with the control block as direction_blocks lays it out -- hoffV | mtV | vm | wrow | hflag -- the Hessian
 //               kernels do not read it), wrow [ntiles], hflag [nrows] (rows whose weights are needed)
 //   mtV, hoffV [nrows + ntiles]: tiles of 32 and offset of every block in H (tiles: mtV = T / 32); htotal: elements of H
 // precision f64: the FP64 pass, then launch_hess_f64 on its V (the Newton matrices of the FP64 phase); no tiles.
@@ -776,8 +777,8 @@ extern "C" int gml_test_hessian_run(gml_problem *p, int formulation, int precisi
 
 // Test hook (not part of include/gml.h): one Hessian-vector product two ways.  device_pass runs the objective pass (RISE or logRISE, i8x
 // or i8w; rescaled re-runs included) over the rows (nodes, theta), which leaves their curvature weights in the slots 0 .. nrows.  Then,
-// for the nloc product rows -- row i multiplies the weights of slot vslot[i] with the direction vec[i] -- as newton_cg_group's hv_pass
-// (gml_solver.cpp) builds the two calls:
+// for the nloc product rows -- row i multiplies the weights of slot vslot[i] with the direction vec[i] -- through the solver's own
+// product call (hv_product_call, gml_newton_cg.cpp: its control block, its arguments), once per route:
 //   hs: i8_hv_sparse over the caller's lists: row i's nw[i] entries at FV[t0[i] T ..] (parameters of node nodes[vslot[i]] in the
 //       reference's order), wcap >= every nw, the plan (kchunk, kpart);
 //   hg: the GEMM pass with hv = 2, lf = 2 and the same (kchunk, kpart), slot i <- (row i, node, vmap = vslot[i]).
@@ -829,15 +830,10 @@ extern "C" int gml_test_hv_sparse(gml_problem *p, int formulation, int precision
         int nsplit = 0;
         gml::i8_split_plan(p->d, (int)(np / 32), 1, &kchunk, &kpart, &nsplit);
     }
-    // rows | node | vslot [np each] | groups [np / 32 + 4] | nw [nloc]   (hv_pass's control block, then the lists' sizes)
-    std::vector<int> ctl((size_t)(3 * np + np / 32 + 4 + nloc), -1);
-    for (int64_t a = 0; a < np; ++a) {
-        ctl[a] = a < nloc ? (int)a : 0;
-        ctl[np + a] = a < nloc ? (int)lnodes[a] : -1;
-        ctl[2 * np + a] = a < nloc ? vslot[a] : 0;
-    }
-    for (int64_t g = 0; g < np / 32; ++g) ctl[3 * np + g] = (int)g;
-    for (int64_t i = 0; i < nloc; ++i) ctl[3 * np + np / 32 + 4 + i] = nw[i];
+    // the solver's control block of a product (product row i = row i of vec), then the lists' sizes: nw [nloc]
+    const gml::cg::HvCtl L(nloc);
+    std::vector<int> ctl = L.pack([&](int64_t a) { return std::array<int, 3>{(int)a, (int)lnodes[a], vslot[a]}; });
+    ctl.insert(ctl.end(), nw, nw + nloc);
     std::vector<long long> t0l(t0, t0 + nloc);
     std::vector<double> init((size_t)nloc * Qp, fill);
     const size_t bufb = gml::i8_hv_sparse_bytes(p->d, (int)nloc, wcap);
@@ -872,26 +868,10 @@ extern "C" int gml_test_hv_sparse(gml_problem *p, int formulation, int precision
         return fail(GML_EHIP, "gml_test_hv_sparse: %s", hipGetErrorString(e));
     }
     std::string err;
-    rc = gml::i8_hv_sparse(p->i8ws, p->d, (int)nloc, dCtl, dCtl + np, dCtl + 2 * np, dT0, dCtl + 3 * np + np / 32 + 4, dFV, T, wcap, dP, dHs, kchunk,
-                           kpart, dBuf, st, &err);
-    if (rc == GML_OK) {
-        gml::I8Pass a{}; // (slots [0, np); no F)
-        a.theta = dP;
-        a.srow = dCtl;
-        a.rowcol = dCtl + np;
-        a.vmap = dCtl + 2 * np;
-        a.groups = dCtl + 3 * np;
-        a.ngroups = (int)(np / 32);
-        a.slot1 = (int)np;
-        a.form = formulation;
-        a.want_grad = true;
-        a.G = dHg;
-        a.hv = 2;
-        a.lf = 2;
-        a.kchunk = kchunk;
-        a.kpart = kpart;
-        rc = gml::i8_pass(&p->i8ws, p->d, p->ws_rows, a, st, nullptr, &err);
-    }
+    const gml::WList wl{dFV, dT0, dCtl + L.size(), T};
+    const gml::HvPlan plan{kchunk, kpart, 2, 2};
+    rc = gml::hv_product_call(&p->i8ws, p->d, p->ws_rows, formulation, true, L, dCtl, wl, wcap, dBuf, plan, dP, dHs, st, &err);
+    if (rc == GML_OK) rc = gml::hv_product_call(&p->i8ws, p->d, p->ws_rows, formulation, false, L, dCtl, wl, wcap, dBuf, plan, dP, dHg, st, &err);
     if (rc == GML_OK) {
         e = hipMemcpyAsync(hs, dHs, sizeof(double) * (size_t)nloc * Qp, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(hg, dHg, sizeof(double) * (size_t)nloc * Qp, hipMemcpyDeviceToHost, st);

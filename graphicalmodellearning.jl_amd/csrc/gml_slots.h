@@ -1,4 +1,4 @@
-// The slot book of the solver's int8-limb workspace (gml_solver.cpp): which row owns which V planes.
+// The slot book of the solver's int8-limb workspace (gml_solver_impl.h: Solver::slots): which row owns which V planes.
 //
 // A pass evaluates its rows in consecutive slots of the workspace and leaves each row's V planes (the fixed-point weights the
 // Hessians and the Hessian-vector products read) in the row's slot.  The slots are [0, Smain) -- the main range, whose planes

@@ -7,7 +7,8 @@
 //                    rows the int8-limb arithmetic cannot bring below tol continue on the FP64 path (polish);
 //   2. directions    Hessian blocks by one device kernel over a sub-sample of the configurations + batched Cholesky
 //                    (newton_blocks: working sets up to max_working entries), or matrix-free conjugate gradients with
-//                    Hessian-vector products from the same GEMM kernels (newton_cg: larger working sets, dense optima);
+//                    Hessian-vector products from the same GEMM kernels (newton_cg: larger working sets, dense optima) --
+//                    direction_blocks and newton_cg live in gml_newton_cg.cpp, their rules in gml_cg_rules.h;
 //   3. line_search   projected (orthant-wise) backtracking: the first trial is a full pass (it usually succeeds), further
 //                    trials are objective-only passes over the rows that need them.
 // One device pass (run_pass) gives f and the full gradient of every listed row (int8-limb or FP64 MFMA kernels).
@@ -20,356 +21,13 @@
 // download per pass (SlotResult), and the host waits for the stream only where it must decide something: after select,
 // after the trial points, and after each pass (whose acceptance scalars ride along).  On small node shards these round
 // trips, not the kernels, are what an iteration costs.
-#include "gml_internal.h"
-#include "gml_slots.h"
-#include "gml_solver.h"
+#include "gml_solver_impl.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 
 using namespace gml;
-
-#define RCCHK(expr)             \
-    do {                        \
-        const int rc__ = (expr); \
-        if (rc__) return rc__;  \
-    } while (0)
-
-namespace {
-
-// device allocations of one gml_learn call, released together
-struct Arena {
-    std::vector<void *> ptrs;
-    ~Arena() {
-        // also reached by the early returns of a failed solve, with kernels possibly still queued on the blocks: wait once,
-        // then the blocks may go back to the library's cache (which hands them out without waiting)
-        if (!ptrs.empty()) (void)hipDeviceSynchronize();
-        for (void *q : ptrs)
-            if (q) (void)dev_free_synced(q);
-    }
-    // give one block back before the arena dies (regrown buffers)
-    void release(void *q) {
-        for (auto &x : ptrs)
-            if (x == q && q) {
-                (void)dev_free(q);
-                x = nullptr;
-            }
-    }
-    template <typename T> hipError_t get(T **out, size_t count) {
-        *out = nullptr;
-        hipError_t e = dev_malloc(reinterpret_cast<void **>(out), sizeof(T) * std::max<size_t>(count, 1));
-        if (e == hipSuccess) ptrs.push_back(*out);
-        return e;
-    }
-};
-
-// Small host <-> device transfers of the solver (control blocks up, per-row scalars down) go through one pinned arena:
-// a copy from or to pageable memory is staged by the runtime and costs the host 20-30 us each.  h2d copies the bytes into
-// the arena and queues an asynchronous copy from there -- the caller's buffer is free as soon as h2d returns; d2h queues
-// the copy into the arena and hands the bytes to the caller's buffer at the next sync(), which is the only place the
-// stream is waited for.  A transfer too large for the arena goes the plain way and is waited for at once.
-struct Stage {
-    char *base = nullptr;
-    size_t cap = 0, off = 0, floor = 0; // [0, floor): arrays that live as long as the solve (persist); the rest is recycled at every sync()
-    bool mapped = false;                // the device reads and writes the arena under its host address (checked by the solver's init)
-    hipStream_t st = nullptr;
-    struct Pend {
-        void *host;
-        const void *pin;
-        size_t n;
-    };
-    std::vector<Pend> pend;
-    void *take(size_t n) {
-        const size_t a = (off + 63) & ~(size_t)63;
-        if (a + n > cap) return nullptr;
-        off = a + n;
-        return base + a;
-    }
-    // Zero-copy: the arena is pinned, mapped host memory, so a kernel can read its control data from it and write its per-row results
-    // into it directly.  On small node shards an iteration is a chain of short launches, and every hipMemcpyAsync in it was a 4-us blit
-    // kernel plus 5 us of host time (profiles/r5_shard128_trace_before.txt: 15 per iteration).
-    // persist: an array the kernels write and the host reads after sync(), for the whole solve (before the first take only)
-    template <typename T> T *persist(size_t count) {
-        const size_t a = (floor + 63) & ~(size_t)63;
-        // only while nothing has been taken from the recycled part: [floor, off) may hold bytes of a copy still in flight
-        if (!mapped || off != floor || !pend.empty() || a + sizeof(T) * count > cap / 2) return nullptr;
-        floor = a + sizeof(T) * count;
-        if (off < floor) off = floor;
-        return reinterpret_cast<T *>(base + a);
-    }
-    // put: control data for kernels queued before the next sync(); NULL when it does not fit (the caller copies to a device buffer)
-    template <typename T> const T *put(const T *host, size_t count) {
-        void *q = mapped && sizeof(T) * count <= cap / 4 ? take(sizeof(T) * std::max<size_t>(count, 1)) : nullptr;
-        if (q && count) std::memcpy(q, host, sizeof(T) * count);
-        return reinterpret_cast<const T *>(q);
-    }
-    hipError_t h2d(void *dev, const void *host, size_t n) {
-        if (n == 0) return hipSuccess;
-        void *q = n <= cap / 4 ? take(n) : nullptr;
-        if (!q) {
-            hipError_t e = hipMemcpyAsync(dev, host, n, hipMemcpyHostToDevice, st);
-            return e != hipSuccess ? e : hipStreamSynchronize(st); // the caller's buffer may die after return
-        }
-        std::memcpy(q, host, n);
-        return hipMemcpyAsync(dev, q, n, hipMemcpyHostToDevice, st);
-    }
-    hipError_t d2h(void *host, const void *dev, size_t n) {
-        if (n == 0) return hipSuccess;
-        void *q = n <= cap / 4 ? take(n) : nullptr;
-        if (!q) return hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, st);
-        pend.push_back({host, q, n});
-        return hipMemcpyAsync(q, dev, n, hipMemcpyDeviceToHost, st);
-    }
-    hipError_t sync() {
-        const hipError_t e = hipStreamSynchronize(st);
-        for (const Pend &x : pend) std::memcpy(x.host, x.pin, x.n);
-        pend.clear();
-        off = floor;
-        return e;
-    }
-};
-
-// Device time of the direction phase (Hessians, Cholesky, CG): measured with events, so that the host need not wait for
-// the stream there just to read a clock.
-struct PhaseTimer {
-    std::vector<hipEvent_t> ev;
-    size_t used = 0;
-    hipStream_t st = nullptr;
-    ~PhaseTimer() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    void mark() {
-        if (used == ev.size()) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            ev.push_back(e);
-        }
-        (void)hipEventRecord(ev[used++], st);
-    }
-    double seconds() { // sum over the (begin, end) pairs; call after the stream has been waited for
-        double s = 0;
-        for (size_t i = 0; i + 1 < used; i += 2) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) s += ms * 1e-3;
-        }
-        return s;
-    }
-};
-
-template <typename T> const T *rebase(const T *p, int64_t lo) { // p' with p'[lo + i] == p[i] (indexed by absolute slot on the device only)
-    return reinterpret_cast<const T *>(reinterpret_cast<uintptr_t>(p) - sizeof(T) * (size_t)lo);
-}
-
-struct Solver {
-    // ---- problem, options ----------------------------------------------------------------------------------------------
-    gml_problem *p;
-    const DevProblem &d;
-    const int formulation;
-    gml_opts o;
-    gml_stats stats{};
-    hipStream_t st;
-    const double *x0 = nullptr; // warm start (gml_learn_warm): the rows to start from, reference layout [R][P], host or device; NULL = zeros
-    // the caller's structure (gml_learn_structured): kind of every parameter slot of every local row, reference layout [R][ld_s] bytes, host or
-    // device; NULL = the reference's (field free, the rest penalised: k_kind alone)
-    const uint8_t *structure = nullptr;
-    int64_t ld_s = 0;
-    std::vector<int> nparam; // with a structure: parameters (slots not excluded) per row; a row without any is complete before the first pass
-    int32_t *dColsRef = nullptr; // multi-body: column of every parameter slot of every local row (:94-104), built once (warm start, finish)
-    int compact_skip = 0, compact_backoff = 0; // passes that do not try the column compaction after one that came out dense (run_pass)
-    bool underflow = false; // the solve ended because a row's weights left the fixed-point range at an iterate (gml_learn: auto -> FP64)
-    bool at_zero = false; // the pass being queued evaluates X = 0 (the first pass of a solve; also its rescaled re-runs)
-    double tune[GML_NTUNE] = {}; // the experiment knobs as they stood when the solve began (gml_test_tune may be called meanwhile)
-    Stage stg;
-    Arena A;
-    PhaseTimer dir_time;
-    double t_dir_host = 0; // host time between the two marks of the direction phases (launches, and the waits of the CG steps)
-    const int64_t R, Rp, Qp, P;
-    const size_t nd;
-    int capW = 0, capP = 0;
-    double lambda = 0;
-    int64_t Scap = 0;  // slots of the int8-limb workspace
-    PlaneSlots slots;  // ... and which row owns which V planes in them (gml_slots.h)
-    double viol_frac = 0.5, cg_eta = 0.05, eta_admit = 0.25;
-    int maxcg = 16, hv_lf = 2, hv_lb = 2;
-    int64_t dbg_row = 0, worst_row = 0;
-    const double t_begin = gml_now_s();
-    // precision i8w: the passes run in their coarse form (30-bit theta, 23-bit weights) until the first active row comes within
-    // coarse_thr of its optimum, then at full width for the rest of the solve
-    bool coarse_on = false;
-    double coarse_thr = 1e-7;
-    int prec = GML_PREC_I8X; // arithmetic of the passes: switches to FP64 for the rows the int8 path leaves above tol ("polish")
-    bool can_polish = false;
-    int stall_cap = 10;
-
-    // ---- device state ----------------------------------------------------------------------------------------------------
-    double *X = nullptr, *G = nullptr, *Xt = nullptr, *Gt = nullptr, *Xb = nullptr, *D = nullptr, *PG = nullptr, *Gs = nullptr;
-    double *Rv = nullptr, *Pv = nullptr, *Hp = nullptr, *Zv = nullptr; // CG vectors, on first use
-    uint8_t *Wm = nullptr;                                             // ... and the mask of the system's coordinates
-    FaceOut *dFaces = nullptr;
-    int face_rounds = 2;      // re-solves of a CG system without the coordinates its step would push through zero
-    double face_share = 0.05; // ... for the rows where those carry more than this share of the predicted decrease
-    uint8_t *kind = nullptr;
-    int *dNode = nullptr, *dRows = nullptr, *dRows2 = nullptr, *dRowsP = nullptr, *dFidx = nullptr, *dHv = nullptr;
-    char *dPass = nullptr;  // control block of a pass: srow | rowcol | groups | tau overrides (one upload)
-    char *dHctl = nullptr;  // control block of the direction phase (one upload)
-    SlotResult *dRes = nullptr;
-    CgState *dCg = nullptr;
-    double *dBest = nullptr, *dAlpha = nullptr, *dFs = nullptr, *dgF = nullptr, *dpgF = nullptr, *dsol = nullptr,
-           *dSdiag = nullptr, *dH = nullptr;
-    SelectOut *dSel = nullptr;
-    TrialOut *dTrial = nullptr;
-    int64_t dH_elems = 0;
-    // pointers into dHctl (set by direction_blocks)
-    int *dMt = nullptr, *dPlane = nullptr;
-    long long *dHoff = nullptr;
-    double *dS1 = nullptr, *dS1cg = nullptr;
-    // secant pairs of the Cholesky rows (k_secant): previous working set, x and g on it, the last two (s, y)
-    int *dFprev = nullptr, *dMprev = nullptr, *dNpairs = nullptr;
-    double *dXprev = nullptr, *dGprev = nullptr, *dSec = nullptr, *dYnoise = nullptr;
-    // preconditioner tiles of the matrix-free rows (direction_blocks): control block, column lists, gradient entries
-    static constexpr int kTile = 128;
-    char *dTctl = nullptr;
-    size_t dTctl_bytes = 0;
-    int *dFV = nullptr, *dVm = nullptr, *dWrow = nullptr, *dLive = nullptr;
-    double *dgV = nullptr;
-    // the last rows' Hessian-vector products on the vector ALUs over their working sets only (gml_hv_sparse.hip)
-    const long long *dT0m = nullptr; // first tile of each local row's working-set list (device; direction_blocks)
-    int *dNw = nullptr;              // |W| by local row
-    void *dHvsBuf = nullptr;
-    size_t hvs_bytes = 0;
-    double hv_sparse_ratio = g_hv_sparse_ratio; // sparse when sum |W| of the live rows < ratio * columns * node tiles of the GEMM pass
-    int64_t tile_cap = 0, ntiles = 0, tile_base = 0; // capacity of dFV / dgV in tiles; tiles of this iteration; offset of the first in dH
-
-    // ---- host state (scalars per row) ------------------------------------------------------------------------------------
-    std::vector<double> f, ft, Fobj, kkt, best, Z, Zt, alpha, dd, fn, fnt, l1t, Fbest;
-    std::vector<uint8_t> done, atfloor, nreg, accepted_fwd, need, iscg;
-    std::vector<int> stall, msz, nW;
-    // per-row results of k_select / k_trial + k_back / the passes' last kernels: written by the kernels straight into pinned host
-    // memory (Stage::persist) and read here after the stream has been waited for; device arrays + one download each when the
-    // pinned arena is too small for them (tens of thousands of local rows)
-    SelectOut *sel = nullptr, *kSel = nullptr;
-    TrialOut *trial = nullptr, *kTrial = nullptr;
-    SlotResult *res = nullptr, *kRes = nullptr;
-    std::vector<SelectOut> sel_v;
-    std::vector<TrialOut> trial_v;
-    std::vector<SlotResult> res_v;
-    bool zc = false;
-    double *dStepn = nullptr; // |trial - x|_1 by row, left on the device by k_trial: scales the weights' unit of the trial pass (k_quant_theta)
-    // Scale of the fixed-point V (int8 path): instead of the worst-case bound w_max exp(sum|theta|) every pass after a row's
-    // first uses vref = max_k |V_rk| measured by its previous pass, times exp(||theta - theta_ref||_1), which bounds the new
-    // weights rigorously (|E_k' - E_k| <= ||theta' - theta||_1).  Near the optimum the steps are tiny, so V keeps all 31 bits
-    // relative to its actual maximum and the noise floor of f and grad drops by the bits the bound would have wasted.
-    std::vector<double> vref, dref, stepn;
-    // where a pass leaves its results, by row: f (or log Z), Z (logRISE), the noise of f -- at the iterates, at the trial points
-    struct PassOut {
-        std::vector<double> &f, &Z, &noise;
-    };
-    const PassOut at_x{f, Z, fn}, at_xt{ft, Zt, fnt};
-    // sub-sampled Newton: Hessians over Kh configurations -- every kstride-th block of 512 (set_kh)
-    int64_t Kh_base = 0, nblk512 = 0, Kh = 0, kstride = 1;
-    double hscale = 1.0;
-    // the record of the outer iterations (gml_solver.h: TrajRecorder), NULL unless a test armed it before the solve began
-    TrajRecorder *rec = nullptr;
-    double *rec_row(int64_t r) { return rec->its.back().rows.data() + (size_t)r * TRR_N; }
-    int rec_select(int it, int64_t nactive);
-    int rec_download(void *host, const void *dev, size_t bytes) { // (armed only: waits for the stream)
-        HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return GML_OK;
-    }
-    // the matrix-free events of the iteration (TRC_*).  (The reference holds until the next event is added.)
-    TrajCgEvent &rec_cg(int tag) {
-        rec->its.back().cg.push_back(TrajCgEvent{tag, {}, {}});
-        return rec->its.back().cg.back();
-    }
-    int rec_rows_of(TrajCgEvent &ev, const double *dev, const std::vector<int> &rows) { // whole rows of a [Rp][Qp] device array
-        std::vector<double> all(nd);
-        RCCHK(rec_download(all.data(), dev, sizeof(double) * nd));
-        for (int r : rows) ev.dv.insert(ev.dv.end(), all.begin() + (size_t)r * Qp, all.begin() + (size_t)(r + 1) * Qp);
-        return GML_OK;
-    }
-    int rec_cgstate(TrajCgEvent &ev, const std::vector<int> &rows) {
-        std::vector<CgState> c((size_t)Rp);
-        RCCHK(rec_download(c.data(), dCg, sizeof(CgState) * Rp));
-        for (int r : rows) ev.dv.insert(ev.dv.end(), {c[r].rs, c[r].rs0, c[r].pHp, c[r].rz});
-        return GML_OK;
-    }
-
-    Solver(gml_problem *p_, int form, const gml_opts &o_, double lam)
-        : p(p_), d(p_->d), formulation(form), o(o_), st(p_->st), R(p_->node1 - p_->node0), Rp(gml_round_up(R, 32)), Qp(p_->d.Qp), P(p_->P),
-          nd((size_t)Rp * p_->d.Qp), lambda(lam) {}
-
-    void trace(const char *name) {
-        if (o.verbose >= 3) {
-            (void)stg.sync();
-            fprintf(stderr, "[gml]     stage %s at %.4f s (last error: %s)\n", name, gml_now_s() - t_begin, hipGetErrorString(hipGetLastError()));
-            fflush(stderr);
-        }
-    }
-    // still building its support: violators at the scale of the support itself (k_select admits them by halves of the largest
-    // violation; once they are few next to the support, all at once)
-    bool admitting(int64_t r) const { return (int64_t)sel[r].nviol * 16 > sel[r].nsupp; }
-    void reopen(int r) { // a finished row is solved on (other arithmetic): its best-iterate record and its stall count start over
-        done[r] = atfloor[r] = 0;
-        stall[r] = 0;
-        best[r] = Fbest[r] = INFINITY;
-    }
-    int upload_rows(const std::vector<int> &rows, int *dst) {
-        if (!rows.empty()) HIPCHK(stg.h2d(dst, rows.data(), sizeof(int) * rows.size()));
-        return GML_OK;
-    }
-    // a row list (or any small control array) for kernels queued before the next wait: read from the pinned arena where it fits,
-    // else uploaded to `fallback`
-    template <typename T> int ctl(const std::vector<T> &v, T *fallback, const T **out) {
-        const T *q = v.empty() ? nullptr : stg.put(v.data(), v.size());
-        *out = q ? q : fallback;
-        if (!q && !v.empty()) HIPCHK(stg.h2d(fallback, v.data(), sizeof(T) * v.size()));
-        return GML_OK;
-    }
-    int fetch(void *host, const void *dev, size_t bytes) { // results the kernels left in device arrays (not zero-copy)
-        if (!zc) HIPCHK(stg.d2h(host, dev, bytes));
-        return GML_OK;
-    }
-
-    int init();
-    void set_kh(int64_t nactive);
-    // One objective(/gradient) pass over the listed rows.  src: X or Xt; dst: G or Gt (want_grad); out: where the results per row
-    // go.  pp: the arithmetic of this pass (< 0: the solver's current precision; the FP64 phase borrows int8 passes for the V planes
-    // its matrix-free rows need).  after: queued on the stream right behind the pass and before the host waits for it (the
-    // acceptance scalars of a trial ride along with the pass results).  step_on_device: a trial whose |trial - x|_1 is still on
-    // the device (dStepn) and comes down with the results.
-    int run_pass(const std::vector<int> &rows, const double *src, double *dst, bool want_grad, bool at_trial, const PassOut &out, int pp = -1,
-                 const std::function<int()> *after = nullptr, bool step_on_device = false);
-    struct PassArgs { // what every round of one run_pass call shares
-        const double *src;
-        double *dst;
-        bool want_grad, at_trial;
-        int pp;
-        const std::function<int()> *after;
-    };
-    using PassRaw = std::vector<SlotResult>; // per listed row, as the kernels left it: f (or Z); on the int8 path also tau and mmax
-    int pass_i8(const PassArgs &q, const std::vector<int> &rows, const std::vector<double> *ovr_in, bool step_on_device, PassRaw &raw);
-    int pass_f64(const PassArgs &q, const std::vector<int> &rows, PassRaw &raw);
-    void compaction_backoff(const std::vector<int> &ctab);
-    void judge_rows(const PassArgs &q, const std::vector<int> &rows, const PassRaw &raw, const PassOut &out, std::vector<int> &again,
-                    std::vector<double> &ovr2);
-    int select(int it, int64_t *nactive);
-    int start_polish(bool *started);
-    int refresh_stale();
-    int direction_blocks(const std::vector<int> &cg_rows);
-    int newton_blocks(const std::vector<int> &chol_rows);
-    int newton_cg(const std::vector<int> &cg_rows);
-    int newton_cg_group(const std::vector<int> &cg_rows, bool subsample);
-    int line_search();
-    int finish(double *out, double *kkt_out, int iterations);
-    int ref_cols();
-    int apply_structure();
-    int load_x0();
-    int iterate(double *out, double *kkt_out);
-};
 
 int Solver::init() {
     if (!(o.tol > 0)) o.tol = 1e-9;
@@ -384,19 +42,19 @@ int Solver::init() {
     // largest -- 0.25 -- the projected Newton steps are damped to nothing by the line search; 0.5 takes full steps throughout;
     // 0.7 converges too, in 1.6x the iterations)
     viol_frac = o.cg_viol_frac > 0 ? o.cg_viol_frac : 0.5;
-    cg_eta = o.cg_eta > 0 ? o.cg_eta : 0.05;
+    mf.cg_eta = o.cg_eta > 0 ? o.cg_eta : 0.05;
     // at most 16 CG steps per Newton step: the number of Newton iterations is set by the admission of the violators, not by
     // the accuracy of the directions (order-3 probe: 32 iterations with a cap of 40, 16 or 15 -- 545 / 349 / 333
     // Hessian-vector passes; 40 iterations, 279 passes with a cap of 8)
-    maxcg = o.max_cg > 0 ? o.max_cg : 16;
+    mf.maxcg = o.max_cg > 0 ? o.max_cg : 16;
     // limbs of the CG direction p in the Hessian-vector passes: 2 (14 bits of max|p|) are enough for an inexact Newton
     // step that stops at a residual of 5 % -- the iteration counts of the 64-node probe of config 5 are 59 / 59 / 56
     // with 4 / 3 / 2 limbs, and the forward GEMM of an H.v pass costs in proportion
-    hv_lf = o.hv_limbs_fwd ? std::min(5, std::max(2, (int)o.hv_limbs_fwd)) : 2;
+    mf.hv_lf = o.hv_limbs_fwd ? std::min(5, std::max(2, (int)o.hv_limbs_fwd)) : 2;
     // ... and the products u_k = h_k (x_k . p) go to the backward GEMM in 2 limbs (15 bits of the largest) instead of 4:
     // half the MFMAs and half the V reads of that GEMM; config 5 at the default regulariser 116 -> 93 s with 10 % more
     // iterations
-    hv_lb = o.hv_limbs_bwd == 4 ? 4 : 2;
+    mf.hv_lb = o.hv_limbs_bwd == 4 ? 4 : 2;
     dbg_row = o.debug_row > 0 ? o.debug_row : 0;
     if (o.limbs_fwd != 0 && o.limbs_fwd != 3 && o.limbs_fwd != 4 && o.limbs_fwd != 5) return fail(GML_EINVAL, "limbs_fwd must be 3, 4 or 5");
 
@@ -456,7 +114,7 @@ int Solver::init() {
     HIPCHK(A.get(&dRowsP, (size_t)Rp));
     HIPCHK(A.get(&dPass, (size_t)(sizeof(int) * (2 * Scap + Scap / 32 + 16) + sizeof(double) * Scap + 64)));
     HIPCHK(A.get(&dHctl, (size_t)(sizeof(int) * 5 * Rp + sizeof(long long) * (Rp + 1) + sizeof(double) * 3 * Rp + 256)));
-    HIPCHK(A.get(&dLive, (size_t)Rp));
+    HIPCHK(A.get(&mf.dLive, (size_t)Rp));
     HIPCHK(A.get(&dFprev, (size_t)Rp * capP));
     HIPCHK(A.get(&dMprev, (size_t)Rp));
     HIPCHK(A.get(&dNpairs, (size_t)Rp));
@@ -951,223 +609,10 @@ int Solver::refresh_stale() {
     return GML_OK;
 }
 
-// Hessian blocks (int8 kernel over the limb planes of the rows' last passes, or the FP64 MFMA kernel over V): the working
-// set of a Cholesky row; for a matrix-free row the tiles of its block-diagonal preconditioner (gml_solver.hip), inverted here.
-// One upload carries the control block of the rows, one that of the tiles.
-int Solver::direction_blocks(const std::vector<int> &cg_rows) {
-    if (!cg_rows.empty() && !gml_is_i8(prec)) {
-        // FP64 phase: the curvature weights of the matrix-free rows' Hessian-vector products and preconditioner tiles come from
-        // an int8-limb objective pass at the same iterate (those run on the int8 cores either way; only the curvature is
-        // approximate)
-        std::vector<double> tf((size_t)R), tz((size_t)R, 1.0), tn((size_t)R);
-        RCCHK(run_pass(cg_rows, X, nullptr, false, false, PassOut{tf, tz, tn}, gml_is_i8(o.precision) ? o.precision : GML_PREC_I8X));
-    }
-    // layout of the block: mt [R] | node [R] | msz of the Cholesky rows [R] | (unused) [R] | plane slot [R] | hoff [R+1] |
-    // s1 [Rp] | ynoise [Rp] | s1cg [Rp]
-    const size_t ibytes = (sizeof(int) * 5 * R + 7) & ~(size_t)7, lbytes = sizeof(long long) * (R + 1);
-    std::vector<char> blk(ibytes + lbytes + sizeof(double) * 3 * Rp, 0);
-    int *mt2 = reinterpret_cast<int *>(blk.data()), *vs = mt2 + 4 * R;
-    long long *hoff = reinterpret_cast<long long *>(blk.data() + ibytes);
-    double *s1 = reinterpret_cast<double *>(blk.data() + ibytes + lbytes), *yn = s1 + Rp, *s1cg = s1 + 2 * Rp;
-    hoff[0] = 0;
-    for (int64_t r = 0; r < Rp; ++r) s1[r] = s1cg[r] = 1.0;
-    for (int64_t r = 0; r < R; ++r) yn[r] = 100.0 * fn[r]; // a gradient difference below this is noise of the pass arithmetic, not curvature
-    for (int64_t r = 0; r < R; ++r) {
-        const int m = done[r] || iscg[r] ? 0 : msz[r];
-        mt2[r] = (m + 31) / 32;
-        mt2[R + r] = (int)(p->node0 + r);
-        mt2[2 * R + r] = m; // the Cholesky step solves these
-        vs[r] = slots.slot((int)r);
-        hoff[r + 1] = hoff[r] + (long long)mt2[r] * 32 * mt2[r] * 32;
-        const double zi = formulation == GML_LOGRISE ? 1.0 / Z[r] : 1.0; // Hess log Z = Hess Z / Z - g g^T
-        s1[r] = hscale * zi; // sub-sampled blocks
-        s1cg[r] = zi;        // the Hessian-vector products use every configuration
-    }
-    if (rec)
-        for (int64_t r = 0; r < R; ++r) {
-            rec_row(r)[TRR_S1] = s1[r];
-            rec_row(r)[TRR_YNOISE] = yn[r];
-        }
-    // the tiles: kTile consecutive entries of W each, behind the rows' blocks
-    constexpr int T = kTile;
-    std::vector<long long> t0((size_t)R, 0);
-    ntiles = 0;
-    for (int r : cg_rows) {
-        t0[r] = ntiles;
-        ntiles += (nW[r] + T - 1) / T;
-    }
-    tile_base = hoff[R];
-    const int64_t NV = R + ntiles, htotal = std::max<long long>(tile_base + ntiles * (long long)T * T, 1);
-    std::vector<int> mtV, vmV, wrowV, hflag;
-    std::vector<long long> hoffV;
-    if (ntiles > 0) {
-        mtV.assign((size_t)NV, T / 32);
-        hoffV.resize((size_t)NV);
-        vmV.resize((size_t)ntiles);
-        wrowV.resize((size_t)ntiles);
-        hflag.assign((size_t)R, 0);
-        const bool rows_i8 = gml_is_i8(prec); // (FP64 phase: the rows' blocks come from launch_hess_f64, not from this call)
-        for (int64_t r = 0; r < R; ++r) {
-            mtV[r] = rows_i8 ? mt2[r] : 0;
-            hoffV[r] = hoff[r];
-            hflag[r] = mtV[r] > 0;
-        }
-        for (int r : cg_rows) {
-            const int64_t nt = (nW[r] + T - 1) / T;
-            hflag[r] = 1;
-            for (int64_t t = 0; t < nt; ++t) {
-                vmV[t0[r] + t] = (int)std::min<int64_t>(T, nW[r] - t * T);
-                wrowV[t0[r] + t] = r;
-                hoffV[R + t0[r] + t] = tile_base + (t0[r] + t) * (long long)T * T;
-            }
-        }
-    }
-    if (htotal > dH_elems) {
-        // regrown: the superseded block goes back now (a long solve of rows that keep admitting violators would otherwise hold
-        // every earlier size until gml_learn returns), and the new size is checked against what the device has left
-        A.release(dH);
-        dH = nullptr;
-        dH_elems = htotal + htotal / 4;
-        size_t freeb = 0, totalb = 0;
-        HIPCHK(dev_mem_info(&freeb, &totalb));
-        if (8.0 * (double)dH_elems > 0.95 * (double)freeb) {
-            if (8.0 * (double)htotal > 0.95 * (double)freeb)
-                return fail(GML_ENOMEM, "Hessian blocks of %.1f GB do not fit in %.1f GB free HBM (lower max_working)", 8.0 * htotal / 1e9, freeb / 1e9);
-            dH_elems = htotal;
-        }
-        HIPCHK(A.get(&dH, (size_t)dH_elems));
-    }
-    for (int64_t r = 0; r < R; ++r) {
-        const bool needs_planes = (gml_is_i8(prec) && mt2[r] > 0) || (ntiles > 0 && iscg[r] && !done[r]);
-        if (needs_planes && !slots.valid((int)r))
-            return fail(GML_EHIP, "internal: row %lld enters the Hessian without valid V planes (slot %d, owner %d, stale %d)", (long long)r,
-                        slots.slot((int)r), slots.slot_owner((int)r), (int)slots.stale((int)r));
-    }
-    HIPCHK(stg.h2d(dHctl, blk.data(), blk.size()));
-    dMt = reinterpret_cast<int *>(dHctl);
-    dPlane = dMt + 4 * R;
-    dHoff = reinterpret_cast<long long *>(dHctl + ibytes);
-    dS1 = reinterpret_cast<double *>(dHctl + ibytes + lbytes);
-    dYnoise = dS1 + Rp;
-    dS1cg = dS1 + 2 * Rp;
-    HessTiles tl;
-    int *dMtV = dMt;
-    long long *dHoffV = dHoff;
-    if (ntiles > 0) {
-        // control block of the tiles: hoffV [NV] | t0 [R] | mtV [NV] | vm [ntiles] | wrow [ntiles] | hflag [R]
-        const size_t tb = sizeof(long long) * (NV + R) + sizeof(int) * (NV + 2 * ntiles + R);
-        if (tb > dTctl_bytes) {
-            A.release(dTctl);
-            dTctl_bytes = tb + tb / 4;
-            HIPCHK(A.get(&dTctl, dTctl_bytes));
-        }
-        if (ntiles > tile_cap) {
-            A.release(dFV);
-            A.release(dgV);
-            tile_cap = ntiles + ntiles / 4;
-            HIPCHK(A.get(&dFV, (size_t)tile_cap * T));
-            HIPCHK(A.get(&dgV, (size_t)tile_cap * T));
-        }
-        std::vector<char> tblk(tb);
-        long long *h_hoff = reinterpret_cast<long long *>(tblk.data()), *h_t0 = h_hoff + NV;
-        int *h_mt = reinterpret_cast<int *>(h_t0 + R), *h_vm = h_mt + NV, *h_wrow = h_vm + ntiles, *h_flag = h_wrow + ntiles;
-        std::memcpy(h_hoff, hoffV.data(), sizeof(long long) * NV);
-        std::memcpy(h_t0, t0.data(), sizeof(long long) * R);
-        std::memcpy(h_mt, mtV.data(), sizeof(int) * NV);
-        std::memcpy(h_vm, vmV.data(), sizeof(int) * ntiles);
-        std::memcpy(h_wrow, wrowV.data(), sizeof(int) * ntiles);
-        std::memcpy(h_flag, hflag.data(), sizeof(int) * R);
-        HIPCHK(stg.h2d(dTctl, tblk.data(), tb));
-        dHoffV = reinterpret_cast<long long *>(dTctl);
-        const long long *dT0 = dHoffV + NV;
-        dT0m = dT0;
-        dMtV = reinterpret_cast<int *>(dTctl + sizeof(long long) * (NV + R));
-        dVm = dMtV + NV;
-        dWrow = dVm + ntiles;
-        RCCHK(upload_rows(cg_rows, dRows2));
-        launch_cg_tiles(dRows2, (int)cg_rows.size(), X, PG, G, kind, Qp, T, dT0, dFV, dgV, st);
-        tl.n = ntiles;
-        tl.T = T;
-        tl.F = dFV;
-        tl.wrow = dWrow;
-        tl.hflag = dWrow + ntiles;
-    }
-    // (the int8 kernel's finalisation writes every lower tile of the rows' blocks and the solve reads nothing else of them; the FP64
-    // kernel accumulates in place, and the tiles' inverses read whole tiles)
-    if (!gml_is_i8(prec) || ntiles > 0) HIPCHK(hipMemsetAsync(dH, 0, sizeof(double) * htotal, st));
-    trace("hessian");
-    if (gml_is_i8(prec) || ntiles > 0) {
-        std::string err;
-        const int hrc = i8_hessian(p->i8ws, d, dMt + R, dPlane, dFidx, dMtV, ntiles > 0 ? mtV.data() : mt2, dHoffV, htotal, (int)R, capP, formulation, Kh,
-                                   kstride, dH, st, &err, ntiles > 0 ? &tl : nullptr);
-        if (hrc) return fail(hrc, "%s", err.empty() ? "int8 Hessian: working set above 512 entries" : err.c_str());
-    }
-    if (!gml_is_i8(prec)) launch_hess_f64(d, p->dV, dMt + R, dFidx, dMt, dHoff, (int)R, capP, formulation, Kh, kstride, dH, st);
-    if (rec && ntiles > 0) { // what the tiles were built from, and the blocks before their inversion
-        TrajCgEvent &ev = rec_cg(TRC_BLOCKS);
-        const size_t ncg = cg_rows.size();
-        ev.iv = {(int64_t)ncg, T, ntiles, Kh, kstride, Qp, prec, P};
-        for (int r : cg_rows) ev.iv.push_back(r);
-        for (int r : cg_rows) ev.iv.push_back(nW[r]);
-        std::vector<long long> t0d((size_t)R);
-        RCCHK(rec_download(t0d.data(), dT0m, sizeof(long long) * R));
-        for (int r : cg_rows) ev.iv.push_back(t0d[r]);
-        std::vector<int> tv((size_t)(2 * ntiles)), fv((size_t)ntiles * T);
-        RCCHK(rec_download(tv.data(), dVm, sizeof(int) * 2 * ntiles)); // (vm | wrow)
-        RCCHK(rec_download(fv.data(), dFV, sizeof(int) * ntiles * T));
-        ev.iv.insert(ev.iv.end(), tv.begin(), tv.end());
-        ev.iv.insert(ev.iv.end(), fv.begin(), fv.end());
-        std::vector<uint8_t> kd((size_t)R * Qp);
-        RCCHK(rec_download(kd.data(), kind, kd.size()));
-        for (int r : cg_rows) ev.iv.insert(ev.iv.end(), kd.begin() + (size_t)r * Qp, kd.begin() + (size_t)(r + 1) * Qp);
-        // the unit and the largest magnitude of the rows' V planes (a later objective pass overwrites them)
-        const double *dtau = nullptr;
-        const unsigned *dmm = nullptr;
-        i8_slot_results(p->i8ws, 0, &dtau, &dmm);
-        int smax = 0;
-        for (int r : cg_rows) smax = std::max(smax, slots.slot(r));
-        std::vector<double> tau((size_t)smax + 1, 0.0);
-        std::vector<unsigned> mm((size_t)smax + 1, 0u);
-        if (dtau) RCCHK(rec_download(tau.data(), dtau, sizeof(double) * tau.size()));
-        if (dmm) RCCHK(rec_download(mm.data(), dmm, sizeof(unsigned) * mm.size()));
-        for (int r : cg_rows) ev.iv.push_back(mm[(size_t)slots.slot(r)]);
-        for (int r : cg_rows) { // the column of every parameter of the result's layout
-            if (p->order == 2) {
-                for (int64_t j = 0; j < P; ++j) ev.iv.push_back(j == p->node0 + r ? d.cconst : j);
-            } else {
-                NodeLayout L;
-                gml_build_layout(p, p->node0 + r, L);
-                ev.iv.insert(ev.iv.end(), L.cols.begin(), L.cols.begin() + P);
-            }
-        }
-        ev.dv.push_back(hscale);
-        for (int r : cg_rows) ev.dv.push_back(s1[r]);
-        for (int r : cg_rows) ev.dv.push_back(tau[(size_t)slots.slot(r)]);
-        RCCHK(rec_rows_of(ev, X, cg_rows));
-        RCCHK(rec_rows_of(ev, PG, cg_rows));
-        RCCHK(rec_rows_of(ev, G, cg_rows));
-        const size_t nb = (size_t)ntiles * T * T, at = ev.dv.size();
-        ev.dv.resize(at + 2 * nb);
-        RCCHK(rec_download(ev.dv.data() + at, dH + tile_base, sizeof(double) * nb));
-    }
-    if (ntiles > 0) {
-        trace("tile inverses");
-        launch_tile_inverse(T, dH, dHoffV + R, dVm, dWrow, dS1, formulation == GML_LOGRISE ? 1.0 : 0.0, dgV, ntiles, st);
-    }
-    if (rec && ntiles > 0) { // ... and the inverses the preconditioner applies
-        TrajCgEvent &ev = rec->its.back().cg.back();
-        const size_t nb = (size_t)ntiles * T * T;
-        RCCHK(rec_download(ev.dv.data() + ev.dv.size() - nb, dH + tile_base, sizeof(double) * nb));
-    }
-    HIPCHK(hipGetLastError());
-    ++stats.hessian_passes;
-    return GML_OK;
-}
 
 // batched Cholesky on the device; the directions are scattered into D
 int Solver::newton_blocks(const std::vector<int> &chol_rows) {
     if (chol_rows.empty()) return GML_OK;
-    const double s2 = formulation == GML_LOGRISE ? 1.0 : 0.0;
     trace("cholesky");
     int maxm = 1;
     for (int r : chol_rows) maxm = std::max(maxm, msz[r]);
@@ -1176,7 +621,7 @@ int Solver::newton_blocks(const std::vector<int> &chol_rows) {
     // (a block over every configuration is the Hessian itself: nothing to correct -- and a secant over a finite step would spoil it)
     const bool secant = Kh < d.Kp;
     if (secant)
-        launch_secant(rows_k, (int)chol_rows.size(), dFidx, dMt + 2 * R, capP, X, Qp, dgF, dH, dHoff, dMt, dS1, s2, dYnoise, dFprev, dMprev, dXprev, dGprev,
+        launch_secant(rows_k, (int)chol_rows.size(), dFidx, dMt + 2 * R, capP, X, Qp, dgF, dH, dHoff, dMt, dS1, s2(), dYnoise, dFprev, dMprev, dXprev, dGprev,
                       dSec, dSec + 2 * Rp * capP, dNpairs, Rp * (int64_t)capP, kCholLds, st);
     if (secant && o.verbose >= 2) {
         std::vector<int> npv((size_t)Rp);
@@ -1193,10 +638,10 @@ int Solver::newton_blocks(const std::vector<int> &chol_rows) {
     nf.X = X;
     nf.kind = kind;
     nf.Qp = Qp;
-    nf.share = face_share;
+    nf.share = cg::kFaceShare;
     // (a re-solve costs as much as the solve; what it saves is backtracking passes, whose cost grows with configurations x
     // statistics: config 2 -- 1e5 x 256 -- is 0.4 ms faster without, the headline problem 4 % faster with)
-    nf.rounds = (double)p->K * (double)Qp >= 268435456.0 ? face_rounds : 0;
+    nf.rounds = (double)p->K * (double)Qp >= 268435456.0 ? cg::kFaceRounds : 0;
     if (tune[GML_TUNE_FACE_ROUNDS] > 0) nf.rounds = (int)tune[GML_TUNE_FACE_ROUNDS] - 1;
     if (rec) { // the pairs as k_secant left them (without a secant: as they were)
         std::vector<int> npv((size_t)Rp);
@@ -1209,291 +654,12 @@ int Solver::newton_blocks(const std::vector<int> &chol_rows) {
     // pairs and corrected the larger blocks itself)
     SecantPairs sp;
     if (secant) sp = SecantPairs{dSec, dSec + 2 * Rp * capP, dNpairs, Rp * (int64_t)capP};
-    launch_newton_solve(dH, dHoff, dMt, dMt + 2 * R, dS1, s2, dgF, dpgF, (int)R, capP, dsol, dSdiag, st, maxm, &nf, nullptr, nullptr, secant ? &sp : nullptr);
+    launch_newton_solve(dH, dHoff, dMt, dMt + 2 * R, dS1, s2(), dgF, dpgF, (int)R, capP, dsol, dSdiag, st, maxm, &nf, nullptr, nullptr, secant ? &sp : nullptr);
     launch_scatter_dir(rows_k, (int)chol_rows.size(), dFidx, dsol, dMt + 2 * R, capP, Qp, D, st);
     HIPCHK(hipGetLastError());
     return GML_OK;
 }
 
-// Matrix-free Newton-CG: H_WW d = -pg_W by preconditioned conjugate gradients, Hessian-vector products from the device
-// operator (forward GEMM of the direction, weights of the rows' last objective pass, backward GEMM), preconditioner =
-// the inverted Hessian blocks of tiles of kTile neighbouring entries of W (direction_blocks).  Inexact Newton:
-// the residual is reduced by eta = min(cg_eta, sqrt(kkt)), in at most max_cg steps.
-int Solver::newton_cg(const std::vector<int> &cg_rows) {
-    if (cg_rows.empty()) return GML_OK;
-    // Two groups.  Rows that are still ADMITTING violators (coordinates at zero whose pseudo-gradient is not: the support is
-    // not final, the iteration count of a dense optimum is set by how many of them are let in per iteration, not by the
-    // accuracy of the step) and are not yet within max(1e3 tol, 1e-5) of their optimum take Hessian-vector products over a
-    // sub-sample of the configurations (below).  Rows whose support is final take every configuration: with the approximate
-    // curvature a row converges only linearly (the residual halves per iteration at 60 configurations per working-set
-    // entry -- the weights exp(-E) are far from uniform), and the last digits come from a few exact Newton steps (measured on
-    // config 5 at the default regulariser: sub-sampled throughout, a handful of the 512 rows creep at 5e-6 for a hundred
-    // iterations).
-    std::vector<int> coarse, fine;
-    const double thr = std::max(1e3 * o.tol, 1e-5);
-    for (int r : cg_rows) (o.hv_subsample != 1 && admitting(r) && kkt[r] > thr ? coarse : fine).push_back(r);
-    if (o.verbose >= 2) fprintf(stderr, "[gml]   cg groups: %zu rows admitting (sub-sampled curvature), %zu rows with every configuration\n", coarse.size(), fine.size());
-    RCCHK(newton_cg_group(coarse, true));
-    return newton_cg_group(fine, false);
-}
-
-int Solver::newton_cg_group(const std::vector<int> &cg_rows, bool subsample) {
-    if (cg_rows.empty()) return GML_OK;
-    const double s2 = formulation == GML_LOGRISE ? 1.0 : 0.0;
-    trace("pcg");
-    if (!Rv) {
-        HIPCHK(A.get(&Rv, nd));
-        HIPCHK(A.get(&Pv, nd));
-        HIPCHK(A.get(&Hp, nd));
-        HIPCHK(A.get(&Zv, nd));
-        HIPCHK(A.get(&Wm, nd));
-        HIPCHK(A.get(&dFaces, (size_t)Rp));
-        HIPCHK(A.get(&dHv, (size_t)(3 * Rp + Rp / 32 + 8)));
-    }
-    std::vector<int> liveflag((size_t)Rp, 0);
-    auto set_live = [&](const std::vector<int> &rows) -> int { // the rows of the kernels that follow: their list, and a flag by row
-        RCCHK(upload_rows(rows, dRows2));
-        std::fill(liveflag.begin(), liveflag.end(), 0);
-        for (int r : rows) liveflag[r] = 1;
-        HIPCHK(stg.h2d(dLive, liveflag.data(), sizeof(int) * Rp));
-        return GML_OK;
-    };
-    RCCHK(set_live(cg_rows));
-    if (rec) {
-        TrajCgEvent &ev = rec_cg(TRC_GROUP);
-        int64_t mw = 1;
-        for (int r : cg_rows) mw = std::max<int64_t>(mw, -(int64_t)sel[r].m);
-        ev.iv = {subsample ? 1 : 0, (int64_t)cg_rows.size(), mw};
-        for (int r : cg_rows) ev.iv.push_back(r);
-        for (int r : cg_rows) ev.iv.push_back(sel[r].nviol);
-        for (int r : cg_rows) ev.iv.push_back(sel[r].nsupp);
-        for (int r : cg_rows) ev.dv.push_back(kkt[r]);
-        for (int r : cg_rows) ev.dv.push_back(Z[r]);
-    }
-    // the rows' lists of W (k_cg_tiles, direction_blocks): the per-step vector kernels walk them instead of the 131 k columns
-    if (!dNw) HIPCHK(A.get(&dNw, (size_t)Rp));
-    HIPCHK(stg.h2d(dNw, nW.data(), sizeof(int) * R));
-    const WList wl{dFV, dT0m, dNw, kTile};
-    launch_pcg_init(dRows2, (int)cg_rows.size(), X, PG, kind, Qp, D, Rv, Zv, Pv, Wm, dCg, st);
-    launch_tile_apply(kTile, dH + tile_base, dFV, dVm, dWrow, dLive, ntiles, Qp, Rv, Zv, st);
-    launch_pcg_dir(dRows2, (int)cg_rows.size(), Qp, Wm, Rv, Zv, Pv, 1, dCg, wl, st);
-    // Sub-sampled curvature: the Hessian-vector products run over ~1/ksub of the configurations -- as many as keep 32 of
-    // them per working-set entry (the sample covariance of |W| statistics from 32 |W| configurations has its eigenvalues
-    // within (1 +- 0.18)^2 of the true ones: a Newton step that is only solved to a 5 % residual loses nothing to that) --
-    // spread over the whole histogram, rescaled by the weight of the part.  The gradient is always exact, so the optimum does
-    // not move; one split plan serves every step of this CG solve (one operator).
-    int64_t kchunk = 0, kpart = 0;
-    // the split plan and the scales of the products over 1/ksub of the configurations
-    auto set_plan = [&](int ksub, size_t nrows, int where, int round, int ci) -> int {
-        int nsplit = 0;
-        i8_split_plan(d, (int)(gml_round_up((int64_t)nrows, 32) / 32), ksub, &kchunk, &kpart, &nsplit);
-        double wsub = 0;
-        for (int c = 0; c < nsplit; ++c)
-            for (int64_t b = c * kchunk / 512; b < std::min((c * kchunk + kpart) / 512, d.Kp / 512); ++b) wsub += p->wblk[(size_t)b];
-        std::vector<double> sc((size_t)Rp);
-        if (kpart < kchunk && wsub > 0) {
-            for (int64_t r = 0; r < Rp; ++r) sc[r] = (r < R && formulation == GML_LOGRISE ? 1.0 / Z[r] : 1.0) / wsub;
-            if (o.verbose >= 2) fprintf(stderr, "[gml]   cg: Hessian-vector products over 1/%d of the configurations (weight %.4f)\n", ksub, wsub);
-        } else {
-            kpart = kchunk;
-            for (int64_t r = 0; r < Rp; ++r) sc[r] = r < R && formulation == GML_LOGRISE ? 1.0 / Z[r] : 1.0;
-        }
-        HIPCHK(stg.h2d(dS1cg, sc.data(), sizeof(double) * Rp)); // (the sub-sample's weight replaces the full sum)
-        if (rec) {
-            TrajCgEvent &ev = rec_cg(TRC_PLAN);
-            ev.iv = {where, round, ci, ksub, kchunk, kpart, nsplit, gml_round_up((int64_t)nrows, 32) / 32, Rp};
-            ev.dv.push_back(wsub);
-            ev.dv.insert(ev.dv.end(), sc.begin(), sc.end());
-        }
-        return GML_OK;
-    };
-    int64_t maxW = 1;
-    for (int r : cg_rows) maxW = std::max<int64_t>(maxW, -(int64_t)sel[r].m);
-    {
-        int ksub = o.hv_subsample > 0 ? o.hv_subsample : (int)std::min<int64_t>(8, std::max<int64_t>(1, p->K / (32 * maxW)));
-        if (!subsample) ksub = 1;
-        RCCHK(set_plan(ksub, cg_rows.size(), 0, 0, 0));
-    }
-    // Relaxed products (inexact Krylov: Simoncini & Szyld 2003, van den Eshof & Sleijpen 2004).  The error a product may carry
-    // without moving the attainable residual grows like 1 / |r_j|: the first steps of an exact-curvature solve need every
-    // configuration, the later ones -- whose search directions only correct a residual that is already a fraction of the
-    // right-hand side -- do not.  From step 2 on the products run over 1/2, from step 4 on over 1/8 of the configurations
-    // (as long as 16 configurations per working-set entry remain).  Config 5 at the default regulariser: the same 43-44 Newton
-    // iterations and 59-67 k products, 36.4 -> 26.2 s; the step where the cut starts matters (over 1/4 from step 2: 28.1 s and
-    // 70 k products; from step 1: 31.3 s, 56 iterations).  hv_subsample = 1 keeps every product exact.
-    std::vector<std::pair<int, int>> relax;
-    if (!subsample && o.hv_subsample == 0)
-        for (const std::pair<int, int> sk : {std::pair<int, int>{2, 2}, std::pair<int, int>{4, 8}}) {
-            const int ks = (int)std::min<int64_t>(sk.second, p->K / (16 * maxW));
-            if (ks > 1) relax.push_back({sk.first, ks});
-        }
-    // The GEMM pass costs the same for a tile of 32 rows whatever the number of live ones in it; few rows go entry by entry
-    // instead (same integers, gml_hv_sparse.hip: their iterates do not depend on the path)
-    const bool sparse_ok = p->i8ws != nullptr && formulation != GML_RPLE && hv_lf == 2 && hv_lb == 2 && d.ko <= 2 && maxW <= 65536 &&
-                           dT0m != nullptr;
-    // Hout = (sum_k h_k x_k x_k^T) theta for the listed rows: an hv pass over slots [0, n) of the u-plane workspace
-    auto hv_pass = [&](const std::vector<int> &rows, const double *theta, double *Hout, TrajCgEvent *ev) -> int {
-        const int64_t n = (int64_t)rows.size(), np = gml_round_up(n, 32);
-        int64_t sumW = 0;
-        for (int r : rows) sumW += nW[r];
-        const bool sparse = sparse_ok && (double)sumW < hv_sparse_ratio * (double)d.Qfp * (double)(np / 32) &&
-                            i8_hv_sparse_bytes(d, (int)n, maxW) <= ((size_t)2 << 30);
-        std::vector<int> ctl((size_t)(3 * np + np / 32 + 4), -1);
-        for (int64_t a = 0; a < np; ++a) {
-            ctl[a] = a < n ? rows[a] : 0;
-            ctl[np + a] = a < n ? (int)(p->node0 + rows[a]) : -1;
-            ctl[2 * np + a] = a < n ? slots.slot(rows[a]) : 0;
-        }
-        for (int64_t g = 0; g < np / 32; ++g) ctl[3 * np + g] = (int)g;
-        HIPCHK(stg.h2d(dHv, ctl.data(), sizeof(int) * ctl.size()));
-        if (ev) { // (the head of a TRC_STEP / TRC_RESOLVE event: the route, the rows, the control block as uploaded)
-            ev->iv.insert(ev->iv.end(), {sparse ? 1 : 0, n, np});
-            ev->iv.insert(ev->iv.end(), rows.begin(), rows.end());
-            ev->iv.insert(ev->iv.end(), ctl.begin(), ctl.end());
-            RCCHK(rec_rows_of(*ev, theta, rows));
-            int smax = 0; // the unit of the rows' V planes (a later objective pass overwrites it)
-            for (int r : rows) smax = std::max(smax, slots.slot(r));
-            const double *dtau = nullptr;
-            const unsigned *dmm = nullptr;
-            i8_slot_results(p->i8ws, 0, &dtau, &dmm);
-            std::vector<double> tau((size_t)smax + 1, 0.0);
-            if (dtau) RCCHK(rec_download(tau.data(), dtau, sizeof(double) * tau.size()));
-            for (int r : rows) ev->dv.push_back(slots.slot(r) >= 0 ? tau[(size_t)slots.slot(r)] : 0.0);
-        }
-        std::string err;
-        int rc;
-        if (sparse) {
-            const size_t need = i8_hv_sparse_bytes(d, (int)n, maxW);
-            if (need > hvs_bytes) {
-                const double tr = gml_now_s();
-                A.release(dHvsBuf);
-                dHvsBuf = nullptr;
-                hvs_bytes = std::max(need + need / 2, (size_t)16 << 20);
-                char *b = nullptr;
-                HIPCHK(A.get(&b, hvs_bytes));
-                dHvsBuf = b;
-                if (o.verbose) fprintf(stderr, "[gml]   scratch of the entry-by-entry products: %.0f MB (%.1f ms)\n", hvs_bytes / 1048576.0, 1e3 * (gml_now_s() - tr));
-            }
-            rc = i8_hv_sparse(p->i8ws, d, (int)n, dHv, dHv + np, dHv + 2 * np, dT0m, dNw, dFV, kTile, maxW, theta, Hout, kchunk, kpart, dHvsBuf, st, &err);
-            if (!rc) ++g_hv_sparse_calls;
-        } else {
-            I8Pass a{}; // (slots [0, np); no F)
-            a.theta = theta;
-            a.srow = dHv;
-            a.rowcol = dHv + np;
-            a.vmap = dHv + 2 * np;
-            a.groups = dHv + 3 * np;
-            a.ngroups = (int)(np / 32);
-            a.slot1 = (int)np;
-            a.form = formulation;
-            a.want_grad = true;
-            a.G = Hout;
-            a.hv = hv_lb == 2 ? 2 : 1;
-            a.lf = hv_lf;
-            a.kchunk = kchunk;
-            a.kpart = kpart;
-            rc = i8_pass(&p->i8ws, d, Scap, a, st, nullptr, &err);
-        }
-        if (rc) return fail(rc, "%s", err.c_str());
-        ++stats.hessian_passes;
-        stats.hv_evals += n;
-        return GML_OK;
-    };
-    std::vector<CgState> cgs((size_t)Rp);
-    std::vector<FaceOut> faces((size_t)Rp);
-    std::vector<int> cur = cg_rows; // rows of this round
-    for (int round = 0;; ++round) {
-        std::vector<int> live = cur;
-        for (int ci = 0; ci < maxcg && !live.empty(); ++ci) {
-            if (round == 0)
-                for (const auto &sk : relax)
-                    if (ci == sk.first) RCCHK(set_plan(sk.second, live.size(), 1, round, ci));
-            TrajCgEvent *ev = nullptr;
-            if (rec) {
-                ev = &rec_cg(TRC_STEP);
-                ev->iv = {round, ci};
-            }
-            RCCHK(hv_pass(live, Pv, Hp, ev));
-            if (ev) {
-                RCCHK(rec_rows_of(*ev, Rv, live));
-                RCCHK(rec_rows_of(*ev, Hp, live));
-            }
-            RCCHK(upload_rows(live, dRows2));
-            launch_pcg_step(dRows2, (int)live.size(), G, Wm, Qp, dS1cg, s2, Hp, D, Rv, Pv, dCg, wl, st);
-            HIPCHK(stg.d2h(cgs.data(), dCg, sizeof(CgState) * Rp));
-            HIPCHK(hipGetLastError());
-            HIPCHK(stg.sync());
-            if (ev)
-                for (int r : live) ev->dv.insert(ev->dv.end(), {cgs[r].rs, cgs[r].rs0, cgs[r].pHp, cgs[r].rz});
-            std::vector<int> nxt;
-            for (int r : live) {
-                // a row that is still admitting violators needs a step that is good at the scale of its largest violation, not more
-                const double eta = admitting(r) ? eta_admit : std::min(cg_eta, std::sqrt(std::max(kkt[r], 1e-300)));
-                if (cgs[r].pHp > 0 && cgs[r].rs > eta * eta * cgs[r].rs0) nxt.push_back(r);
-            }
-            if (o.verbose >= 2) {
-                fprintf(stderr, "[gml]   cg %2d: %zu rows live", ci, nxt.size());
-                for (int64_t r : {dbg_row, worst_row})
-                    if (r < R && std::find(cur.begin(), cur.end(), (int)r) != cur.end())
-                        fprintf(stderr, "  row %lld |r|/|r0| %.3e", (long long)r, std::sqrt(cgs[r].rs / std::max(cgs[r].rs0, 1e-300)));
-                fprintf(stderr, "\n");
-            }
-            live.swap(nxt);
-            if (live.empty() || ci + 1 == maxcg) break; // (at the cap the next direction would not be used)
-            RCCHK(set_live(live));
-            launch_tile_apply(kTile, dH + tile_base, dFV, dVm, dWrow, dLive, ntiles, Qp, Rv, Zv, st);
-            launch_pcg_dir(dRows2, (int)live.size(), Qp, Wm, Rv, Zv, Pv, 0, dCg, wl, st);
-        }
-        if (rec) {
-            TrajCgEvent &ev = rec_cg(TRC_ROUND_END);
-            ev.iv = {round, (int64_t)cur.size()};
-            ev.iv.insert(ev.iv.end(), cur.begin(), cur.end());
-            RCCHK(rec_rows_of(ev, D, cur));
-        }
-        if (round >= face_rounds) break;
-        // orthant faces (gml_solver.hip, k_pcg_faces): the rows whose projected step would lose a noticeable part of its
-        // predicted decrease to the clipping solve again without the clipped coordinates
-        RCCHK(upload_rows(cur, dRows2));
-        launch_pcg_faces(dRows2, (int)cur.size(), X, PG, kind, Qp, D, Wm, dFaces, st);
-        HIPCHK(stg.d2h(faces.data(), dFaces, sizeof(FaceOut) * Rp));
-        HIPCHK(hipGetLastError());
-        HIPCHK(stg.sync());
-        std::vector<int> again;
-        int64_t nfixed = 0;
-        for (int r : cur) {
-            nfixed += faces[r].nfixed;
-            if (faces[r].nfixed > 0 && faces[r].mass > face_share * faces[r].total) again.push_back(r);
-        }
-        if (o.verbose >= 2)
-            fprintf(stderr, "[gml]   cg faces (round %d): %lld coordinates fixed at zero in %zu rows; %zu rows solve again\n", round, (long long)nfixed,
-                    cur.size(), again.size());
-        if (rec) {
-            TrajCgEvent &ev = rec_cg(TRC_FACES);
-            ev.iv = {round, (int64_t)cur.size(), (int64_t)again.size()};
-            ev.iv.insert(ev.iv.end(), cur.begin(), cur.end());
-            for (int r : cur) ev.iv.push_back(faces[r].nfixed);
-            ev.iv.insert(ev.iv.end(), again.begin(), again.end());
-            for (int r : cur) ev.dv.push_back(faces[r].mass);
-            for (int r : cur) ev.dv.push_back(faces[r].total);
-        }
-        if (again.empty()) break;
-        cur.swap(again);
-        if (!relax.empty()) RCCHK(set_plan(1, cur.size(), 2, round + 1, 0)); // (the re-solve starts from the exact residual of the clipped step)
-        TrajCgEvent *ev = nullptr;
-        if (rec) {
-            ev = &rec_cg(TRC_RESOLVE);
-            ev->iv = {round + 1};
-        }
-        RCCHK(hv_pass(cur, D, Hp, ev));
-        if (ev) RCCHK(rec_rows_of(*ev, Hp, cur));
-        RCCHK(set_live(cur));
-        launch_pcg_resid(dRows2, (int)cur.size(), PG, G, Qp, dS1cg, s2, Hp, D, Wm, Rv, dCg, st);
-        launch_tile_apply(kTile, dH + tile_base, dFV, dVm, dWrow, dLive, ntiles, Qp, Rv, Zv, st);
-        launch_pcg_dir(dRows2, (int)cur.size(), Qp, Wm, Rv, Zv, Pv, 1, dCg, wl, st);
-        if (ev) RCCHK(rec_cgstate(*ev, cur));
-    }
-    return GML_OK;
-}
 
 // Projected backtracking line search.  Two acceptance regimes per row:
 //  * the predicted decrease is well above the uncertainty of f  -> Armijo on F;
@@ -1809,6 +975,8 @@ int Solver::iterate(double *out, double *kkt_out) {
     }
     return finish(out, kkt_out, it);
 }
+
+namespace {
 
 // one solve of gml_learn_structured at precision prec, under `structure` (NULL: the reference's), from x0 (NULL: zeros) to out / kkt_out;
 // *st: its stats, the wall-clock columns filled

@@ -1,4 +1,4 @@
-// Interface between the host solver (gml_solver.cpp) and its device kernels (gml_solver.hip).
+// Interface between the host solver (gml_solver.cpp, gml_newton_cg.cpp) and its device kernels (gml_solver.hip).
 #pragma once
 #include "gml_dev.h"
 
@@ -41,7 +41,7 @@ enum { // per local row (doubles; the integers among them are exact)
     TRR_TRIALS, TRR_ALPHA /* of the accepting trial; of the last one for a row that was not accepted */, TRR_NREG /* of that trial */,
     TRR_FULL /* the accepting trial was a full pass (0: forward only, its gradient pass followed) */, TRR_ACCEPTED, TRR_GAVE_UP,
     TRR_N = 24 };
-// What the matrix-free half of an iteration did (direction_blocks, newton_cg_group), in order, for tests/test_gpu_newton_cg_trajectory.py:
+// What the matrix-free half of an iteration did (gml_newton_cg.cpp: direction_blocks, newton_cg_group), in order, for tests/test_gpu_newton_cg_trajectory.py:
 // a list of events, each a tag, integers and doubles.  n = rows of the event, np = n rounded up to 32, ctl = the control block of the
 // product as uploaded (row [np] | node0 + row [np] | plane slot [np] | node tile [np / 32] | 4 unused), rows of vectors are whole rows of Qp.
 enum {
@@ -94,6 +94,21 @@ struct WList {
     const int *nw;
     int T;
 };
+
+// One Hessian-vector product of the matrix-free rows as the solver calls it (gml_newton_cg.cpp; the test hook gml_test_hv_sparse of
+// gml_operator.cpp makes the same call): out = (sum_k h_k x_k x_k^T) vec for the n product rows of the control block ctl (device, laid
+// out by cg::HvCtl of gml_cg_rules.h), over the configurations of the plan.  sparse: entry by entry over the rows' lists wl (wcap >= every
+// listed size, scratch of i8_hv_sparse_bytes); else the GEMM pass over the slots [0, np) of the workspace *ws.
+namespace cg {
+struct HvCtl;
+}
+struct HvPlan {
+    int64_t kchunk, kpart;
+    int lf, lb; // limbs of the direction in the forward GEMM, of the products in the backward one (GEMM route)
+};
+int hv_product_call(void **ws, const DevProblem &d, int64_t slot_capacity, int formulation, bool sparse, const cg::HvCtl &L, const int *ctl,
+                    const WList &wl, int64_t wcap, void *scratch, const HvPlan &plan, const double *vec, double *out, hipStream_t st,
+                    std::string *err);
 
 struct CgState {
     double rs, rs0, pHp, rz;

@@ -1,5 +1,5 @@
-"""Host model of the matrix-free direction phase of learn() (csrc/gml_solver.cpp: the matrix-free half of direction_blocks, newton_cg,
-newton_cg_group), restated from the rules the solver documents, and the comparison of a recorded iteration (csrc/gml_solver.h: TRC_*)
+"""Host model of the matrix-free direction phase of learn() (csrc/gml_newton_cg.cpp: the matrix-free half of direction_blocks, newton_cg,
+newton_cg_group; its rules: csrc/gml_cg_rules.h), restated from the rules the solver documents, and the comparison of a recorded iteration (csrc/gml_solver.h: TRC_*)
 with it.  Numpy only; nothing of the code under test is imported.
 
 Three parts.

@@ -1,4 +1,4 @@
-"""The matrix-free direction phase of learn() (csrc/gml_solver.cpp: the matrix-free half of direction_blocks, newton_cg,
+"""The matrix-free direction phase of learn() (csrc/gml_newton_cg.cpp: the matrix-free half of direction_blocks, newton_cg,
 newton_cg_group), iteration by iteration, against the host model of tests/_newton_cg_reference.py.  The solver records what this phase
 did while the recorder of csrc/gml_testhooks.cpp is armed (gml_test_traj_cg_*; csrc/gml_solver.h: TRC_*); the rows need not converge,
 what is held is each recorded iteration.

@@ -549,7 +549,7 @@ def test_newton_cg_reduced_limbs_reach_the_same_optimum():
 
 def test_newton_cg_relaxed_products_reach_the_same_optimum():
     # Rows whose support is final solve their Newton system with every configuration in the first two CG steps and with 1/2, then
-    # 1/8 of them in the later ones (inexact Krylov, gml_solver.cpp newton_cg_group); hv_subsample = 1 keeps every product exact.
+    # 1/8 of them in the later ones (inexact Krylov, gml_cg_rules.h relax_schedule); hv_subsample = 1 keeps every product exact.
     # Same (unique) optimum either way, certified by the oracle's gradient, and no more Newton iterations than a few.
     n, K = 192, 30000
     spins, J = synthetic.block_ising(n, K, block=16, seed=7)
