@@ -13,8 +13,8 @@ from .formulations import (HIP, ISODUS, NLP, RISE, RISEA, RPLE, GMLFormulation, 
 from .inference import (ConditionalMeans, ConditionalMode, Imputation, ImputedMode, PredictiveCheck, conditional_means,  # noqa: F401
                         conditional_mode, conditional_sample, impute, impute_mode, impute_sample, predictive_check)
 from .learn import learn  # noqa: F401
-from .likelihood import (AIS, Exact, LogLikelihood, LogPartition, MostProbable, exact_moments, log_likelihood,  # noqa: F401
-                         log_partition, most_probable_states, observed_log_likelihood)
+from .likelihood import (AIS, Elimination, Exact, LogLikelihood, LogPartition, MostProbable, exact_moments, log_likelihood,  # noqa: F401
+                         log_partition, model_term_moments, most_probable_states, observed_log_likelihood)
 from .missing import EMStep, ImputationEM, MissingDataResult, learn_missing  # noqa: F401
 from .path import PathResult, learn_path  # noqa: F401
 from .sampling import GMSampler, Gibbs, Glauber, GlauberChains, GlauberTermChains, TemperedTermChains, sample  # noqa: F401
@@ -26,4 +26,4 @@ __all__ = ["learn", "GMLFormulation", "RISE", "logRISE", "RPLE", "RISEA", "multi
            "LogLikelihood", "conditional_sample", "conditional_means", "predictive_check", "ConditionalMeans", "PredictiveCheck",
            "impute", "impute_sample", "Imputation", "learn_missing", "ImputationEM", "EMStep", "MissingDataResult", "Exact",
            "exact_moments", "observed_log_likelihood", "most_probable_states", "MostProbable", "conditional_mode", "ConditionalMode",
-           "impute_mode", "ImputedMode"]
+           "impute_mode", "ImputedMode", "Elimination", "model_term_moments"]

@@ -101,6 +101,8 @@ def lib():
     L.gml_conditional_exact.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_exact_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_model_best_states.argtypes = [p, i32, p, i64, i64, i64, i32, C.POINTER(i64), p, p]
+    L.gml_model_elim_plan.argtypes = [p, i32, p, i64, i64, p, p, C.POINTER(C.c_int32), C.POINTER(dbl), C.POINTER(dbl)]
+    L.gml_model_elim.argtypes = [p, i32, p, i64, i64, p, i32, C.POINTER(dbl), p, p]
     L.gml_conditional_mode.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_mode_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_draw.argtypes = [p, i32, p, i64, i64, p, p, i32, C.c_uint64, p, p, p]
@@ -412,6 +414,44 @@ def model_best_states(terms, n, k, device=0):
     check(lib().gml_model_best_states(_ptr(keys), stride, _ptr(wts), len(wts), n, k, int(device), C.byref(found), _ptr(states),
                                       _ptr(energies)))
     return states[:found.value], energies[:found.value]
+
+
+def _elim_order(order, n):
+    """a caller's elimination order (1-based spins, as the keys of a model are) as the 0-based int32 array of the C ABI, or None"""
+    if order is None:
+        return None
+    order = np.ascontiguousarray(np.asarray(order, dtype=np.int64).ravel() - 1, dtype=np.int32)
+    if len(order) != n:
+        raise GMLError(GML_EINVAL, f"order must name each of the {n} spins once (given {len(order)} entries)")
+    return order
+
+
+def model_elim_plan(terms, n, order=None):
+    """gml_model_elim_plan on a term list as term_arrays takes it: (order int32 [n] of 1-based spins, width, work, stored) -- the
+    elimination order (order=None: the greedy one; else a permutation of 1 .. n), the largest scope, sum_t 2^|scope_t| and
+    sum_t 2^|F_t|.  Host only: no device is needed."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    n = int(n)
+    order = _elim_order(order, n)
+    out = np.zeros(max(n, 0), dtype=np.int32)
+    width, work, stored = C.c_int32(), C.c_double(), C.c_double()
+    check(lib().gml_model_elim_plan(_ptr(keys), stride, _ptr(wts), len(wts), n, _ptr(order), _ptr(out), C.byref(width), C.byref(work),
+                                    C.byref(stored)))
+    return out + 1, int(width.value), float(work.value), float(stored.value)
+
+
+def model_elim(terms, n, order=None, mean=True, texp=True, device=0):
+    """gml_model_elim on a term list as term_arrays takes it: (log_z, m [n] or None, e [number of terms] or None) -- exact log Z, the
+    means and the expectation of every term of the model (in the order term_arrays lists them: a dict's own order; the non-zero terms
+    of an array-backed model), by variable elimination on the device; elimination orders of width at most 30."""
+    keys, wts, stride, n = term_arrays(terms, n)
+    n = int(n)
+    order = _elim_order(order, n)
+    log_z = C.c_double()
+    m = np.zeros(max(n, 0)) if mean else None
+    e = np.zeros(len(wts)) if texp else None
+    check(lib().gml_model_elim(_ptr(keys), stride, _ptr(wts), len(wts), n, _ptr(order), int(device), C.byref(log_z), _ptr(m), _ptr(e)))
+    return float(log_z.value), m, e
 
 
 class Problem:

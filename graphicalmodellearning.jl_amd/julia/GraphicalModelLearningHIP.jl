@@ -532,6 +532,45 @@ function conditional_draw_masked(terms::Dict, samples::Array{T,2}; replicas::Int
     end
 end
 
+# a caller's elimination order (1-based spins) as the C ABI takes it, or C_NULL for the library's greedy order
+elim_order(order, n) = order === nothing ? Ptr{Int32}(C_NULL) :
+    (length(order) == n || throw(ArgumentError("order must name each of the $n spins once")); Int32.(order .- 1))
+
+"""
+    model_elim_plan(terms::Dict, n; order=nothing) -> order (n, 1-based), width, work, stored
+
+The elimination order of a model of `n` spins and what it costs (gml_model_elim_plan, include/gml.h): the largest scope of a step,
+sum_t 2^|scope_t| and sum_t 2^|F_t|.  `order`: a permutation of 1:n, or `nothing` for the greedy order.  Host only; marshalling only.
+"""
+function model_elim_plan(terms::Dict, n::Integer; order=nothing)
+    keymat, weights, stride = term_arrays(terms)
+    out = Vector{Int32}(undef, n)
+    width, work, stored = Ref{Int32}(0), Ref{Cdouble}(0), Ref{Cdouble}(0)
+    rc = ccall((:gml_model_elim_plan, libgml), Cint,
+               (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Int32}, Ptr{Int32}, Ref{Int32}, Ref{Cdouble}, Ref{Cdouble}),
+               keymat, stride, weights, length(weights), n, elim_order(order, n), out, width, work, stored)
+    rc == GML_OK || error("gml_model_elim_plan: $(lasterr())")
+    return Int.(out) .+ 1, Int(width[]), work[], stored[]
+end
+
+"""
+    model_elim(terms::Dict, n; order=nothing, device=0) -> log_z, mean (n), texp (length(terms), in the Dict's iteration order)
+
+Exact log Z, means and the expectation of every term of a sparse model of `n` spins by variable elimination on the device
+(gml_model_elim, include/gml.h): elimination orders of width at most 30.  Marshalling only.
+"""
+function model_elim(terms::Dict, n::Integer; order=nothing, device::Integer=0)
+    keymat, weights, stride = term_arrays(terms)
+    log_z = Ref{Cdouble}(0)
+    mean = Vector{Float64}(undef, n)
+    texp = Vector{Float64}(undef, length(weights))
+    rc = ccall((:gml_model_elim, libgml), Cint,
+               (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Int32}, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               keymat, stride, weights, length(weights), n, elim_order(order, n), device, log_z, mean, texp)
+    rc == GML_OK || error("gml_model_elim: $(lasterr())")
+    return log_z[], mean, texp
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

@@ -5,7 +5,10 @@ sums on the device); log Z is estimated by annealed importance sampling on the d
 walked from beta = 0 to beta = 1 with a running weight).  AIS is unbiased for Z, hence biased low for log Z: the likelihood is an
 optimistic one, and the standard error does not see a well that no chain found (include/gml.h).  Where every connected component of
 the model has at most 40 spins, Exact() gives log Z itself (gml_model_exact: enumeration on the device), and exact_moments the
-model's own means, correlations and term expectations: the model-side twin of moments(samples)."""
+model's own means, correlations and term expectations: the model-side twin of moments(samples).  Where the model is sparse --
+a lattice, a Chimera graph, a tree, an l1 solution of thousands of spins in one component -- Elimination() gives the exact log Z by
+variable elimination (gml_model_elim: the cost follows the width of an elimination order, not the number of spins), and
+model_term_moments the model's own sufficient statistics to hold against Problem.term_moments."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -46,6 +49,20 @@ class Exact:
             raise ValueError(f"max_spins must lie in [1, 40] (given {max_spins})")
         if not 1 <= self.max_hidden <= 24:
             raise ValueError(f"max_hidden must lie in [1, 24] (given {max_hidden})")
+
+
+class Elimination:
+    """Exact variable elimination on the device (gml_model_elim) for log Z, the means and the model's own term expectations: any
+    number of spins, as long as the elimination order has width (the largest scope of a step) at most `max_width`, itself at most 30
+    (the library's limit; a step of scope k costs 2^k table entries).  order: a permutation of the 1-based spins, or None for the
+    library's greedy order.  The width is planned on the host (gml_model_elim_plan), so a model too wide is refused before any
+    device work."""
+
+    def __init__(self, max_width=26, order=None):
+        self.max_width = int(max_width)
+        if not 1 <= self.max_width <= 30:
+            raise ValueError(f"max_width must lie in [1, 30] (given {max_width})")
+        self.order = None if order is None else np.asarray(order, dtype=np.int64).ravel()
 
 
 @dataclass
@@ -103,14 +120,24 @@ def _check_exact(method, terms, n):
         raise ValueError(f"a connected component of the model has more than max_spins = {method.max_spins} spins")
 
 
+def _check_elimination(method, terms, n):
+    width = _lib.model_elim_plan(terms, n, method.order)[1]
+    if width > method.max_width:
+        raise ValueError(f"the elimination order has width {width}, above max_width = {method.max_width}")
+
+
 def log_partition(model, method=None, *, seed=0, device=0, return_states=False):
     """log Z of `model` (a FactorGraph, a {1-based key tuple: weight} dict or a matrix with the fields on its diagonal) by annealed
-    importance sampling on the device; method: an AIS (default AIS()), or an Exact for the exact value by enumeration (seed and
-    return_states play no part then).  Returns a LogPartition."""
+    importance sampling on the device; method: an AIS (default AIS()), an Exact for the exact value by enumeration, or an Elimination
+    for the exact value by variable elimination (seed and return_states play no part in the exact ones).  Returns a LogPartition."""
     method = AIS() if method is None else method
-    if not isinstance(method, (AIS, Exact)):
+    if not isinstance(method, (AIS, Exact, Elimination)):
         raise ValueError(f"log_partition takes an AIS method, given {type(method).__name__}")
     terms, n = _model_terms(model)
+    if isinstance(method, Elimination):
+        _check_elimination(method, terms, n)
+        log_z = _lib.model_elim(terms, n, method.order, mean=False, texp=False, device=device)[0]
+        return LogPartition(log_z, 0.0, float("nan"), np.zeros(0))
     if isinstance(method, Exact):
         _check_exact(method, terms, n)
         log_z = _lib.model_exact(terms, n, pairs=False, device=device)[0]
@@ -143,8 +170,8 @@ def observed_log_likelihood(data, model, method=None, *, log_z=None, seed=0, dev
     """The log-likelihood of data with holes: `data` is a K x (1+n) histogram matrix whose spin entries are -1, +1 or 0 = missing, as
     impute takes it (counts: positive integers), every row hiding at most 24 spins.  A row contributes log P(x_O), the marginal
     probability of what it observes: log sum over its missing spins of exp(E), by enumeration on the device
-    (gml_conditional_exact_masked: exact, whatever `method` is), minus log Z.  log_z and method (an AIS, or an Exact whose max_hidden
-    also bounds the holes of a row) as in log_likelihood.  Returns a LogLikelihood whose data_term is the count-weighted mean of
+    (gml_conditional_exact_masked: exact, whatever `method` is), minus log Z.  log_z and method (an AIS, an Elimination, or an Exact
+    whose max_hidden also bounds the holes of a row) as in log_likelihood.  Returns a LogLikelihood whose data_term is the count-weighted mean of
     log sum exp(E); on data without holes it equals log_likelihood."""
     from . import inference  # (inference imports this module)
 
@@ -187,9 +214,43 @@ class MostProbable:
 def most_probable_states(model, k=1, *, log_prob=False, device=0, method=None):
     """The k most probable states of `model` (as log_partition takes it), certified by enumeration on the device
     (gml_model_best_states): 1 <= k <= 256, components of at most 40 spins (method: an Exact whose max_spins refuses larger ones).
-    log_prob=True adds their log-probabilities at the price of one exact log Z (gml_model_exact).  Returns a MostProbable."""
+    log_prob=True adds their log-probabilities at the price of one exact log Z: by enumeration (gml_model_exact), or with
+    method=Elimination() by variable elimination (the states themselves are enumerated either way).  Returns a MostProbable."""
     terms, n = _model_terms(model)
-    _check_exact(Exact() if method is None else method, terms, n)
+    if isinstance(method, Elimination):
+        if log_prob:
+            _check_elimination(method, terms, n)
+    else:
+        _check_exact(Exact() if method is None else method, terms, n)
     states, energy = _lib.model_best_states(terms, n, k, device=device)
-    log_p = energy - _lib.model_exact(terms, n, pairs=False, device=device)[0] if log_prob else None
-    return MostProbable(states, energy, log_p)
+    if not log_prob:
+        return MostProbable(states, energy, None)
+    if isinstance(method, Elimination):
+        log_z = _lib.model_elim(terms, n, method.order, mean=False, texp=False, device=device)[0]
+    else:
+        log_z = _lib.model_exact(terms, n, pairs=False, device=device)[0]
+    return MostProbable(states, energy, energy - log_z)
+
+
+def model_term_moments(model, method=None, device=0):
+    """The model's own sufficient statistics: (m [n], e [number of terms]) -- the means <s_i> and the expectation <prod_{i in t} s_i>
+    of every term of `model` under the model itself, the terms in the model's own order: the model-side twin of
+    Problem.term_moments(model.terms).  method: an Exact (the default: gml_model_exact with the model's terms as queries; components
+    of at most 40 spins) or an Elimination (gml_model_elim: sparse models of any size; a term of weight zero over two or more spins
+    gives NaN there)."""
+    method = Exact() if method is None else method
+    if not isinstance(method, (Exact, Elimination)):
+        raise ValueError(f"model_term_moments takes an Exact or Elimination method, given {type(method).__name__}")
+    terms, n = _model_terms(model)
+    if isinstance(method, Elimination):
+        _check_elimination(method, terms, n)
+        _, m, e = _lib.model_elim(terms, n, method.order, device=device)
+        if hasattr(terms, "keys_array"):  # (an array-backed model goes to the library without its zero weights: NaN, as above)
+            nz = np.flatnonzero(terms.weights != 0.0)
+            full = np.full(len(terms), np.nan)
+            full[nz] = e[:len(nz)]
+            e = full
+        return m, e
+    _check_exact(method, terms, n)
+    _, m, _, e = _lib.model_exact(terms, n, queries=terms, pairs=False, device=device)
+    return m, e

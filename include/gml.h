@@ -566,6 +566,51 @@ int gml_model_best_states(const int32_t *keys, int key_stride, const double *wei
                           int64_t *found, int8_t *states /* [k][n] row-major, +-1 */, double *energies /* [k] */);
 
 /*
+ * gml_model_elim_plan, gml_model_elim -- exact log Z, means and term expectations of a SPARSE term list of any number of spins, by
+ * variable elimination on the device.  The cost follows the width of an elimination order, not the number of spins: a 16 x 16
+ * lattice (256 spins in one component, refused by gml_model_exact) has width 17.  No handle is made; all pointers are host pointers.
+ * Model.  The conventions of gml_model_exact: 0-based spins, -1 = unused slot, a spin named twice cancels, a term of weight zero joins
+ *   nothing.  Spins that share a term of non-zero weight are neighbours.
+ * Order.  order [n]: a permutation of 0 .. n - 1, or NULL for the greedy one.  The connected components are taken in the order of
+ *   their smallest spin, each one's spins in the order the permutation names them.  Greedy: a component starts at its lowest spin;
+ *   then, among the unprocessed spins with a processed neighbour, the one whose step leaves the smallest frontier, the lowest index
+ *   among equals.  order_out [n] (or NULL): the order used, component by component.
+ * Plan.  A term is applied at the step of its last spin.  The frontier F_t: the processed spins with an unprocessed neighbour.  The
+ *   scope of step t: F_{t-1} and v_t.  *width = the largest scope; *work = sum_t 2^|scope_t|; *stored = sum_t 2^|F_t| (t = 1 .. n;
+ *   both sums in step order in FP64).  A spin in no term is a step of scope 1.  gml_model_elim_plan makes no HIP call and refuses
+ *   nothing but bad arguments: it is how a caller learns the width beforehand.
+ * Recursion, per component, every table in the log domain (couplings of +-150 neither overflow nor underflow), FP64:
+ *   alpha_t = logsumexp over the spins retiring at t of (alpha_{t-1} + phi_t), phi_t = the signed weights of the terms applied at t in
+ *   the caller's order; log Z = alpha_n + the weights of the empty keys + ln 2 per spin in no term, the components in order.  With
+ *   mean or texp a backward pass: p_t = exp(alpha_{t-1} + phi_t + beta_t - alpha_n), <s_u> = sum p_t s_u for u retiring at t,
+ *   <prod_{i in k} s_i> = sum p_t prod s_i for term k applied at t, beta_{t-1} = logsumexp over v_t of (phi_t + beta_t).
+ * Outputs.  *log_z.  mean [n] (or NULL); a spin in no term has mean 0.  texp [nterms] (or NULL): the expectation of every term's
+ *   reduced key, in the caller's order; an empty or cancelled key gives 1.0.  The recursion sees a key's spins in one scope only where
+ *   the term has a non-zero weight (it is what makes them neighbours): a term of weight zero gives NaN, unless its reduced key has
+ *   at most one spin (1.0, or that spin's mean).  A key of non-zero weight lies within one component by construction, so no product
+ *   over components arises; use gml_model_exact for the expectation of a key the model does not hold.
+ * Determinism.  Every sum has a fixed order and every grid is a function of the table sizes: per thread in index order, per workgroup
+ *   a tree, the workgroups 1024 at a time in index order; two calls with the same arguments return the same bits.
+ * Error.  With L = sum_t |w_t| + n ln 2 and T terms: about 2^-53 (T + 4 n) L for log Z, four times that plus 1e-13 for the
+ *   expectations.
+ * GML_EINVAL, before any HIP call, in this order: log_z NULL; NULL keys or weights with nterms > 0, key_stride < 1; n < 1 or
+ *   nterms < 0; a spin outside [0, n) or a non-finite weight; order not a permutation of 0 .. n - 1.  GML_EUNSUPPORTED, before any
+ *   HIP call: a width above GML_ELIM_MAX_WIDTH; with mean or texp, stored above 2^32 entries (32 GiB of forward tables; log_z alone
+ *   keeps two tables).  The device is looked for last.  GML_ENOMEM: the device cannot hold the tables.
+ * Cost.  Planning: per step the neighbour lists of the current candidates (up to frontier x degree of them) -- quadratic in n on
+ *   hub-like graphs whose frontier grows with n.  All components run on one stream with one synchronisation per call.  One launch per
+ *   step forward (more where over 3 spins retire at once), one or two per step backward; a forward step reads
+ *   2^|F_{t-1}| and writes 2^|F_t| doubles.  Measured times in DESIGN 3.22.  Device memory is released before the call returns.
+ */
+#define GML_ELIM_MAX_WIDTH 30
+int gml_model_elim_plan(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                        const int32_t *order /* [n] permutation, or NULL: greedy */, int32_t *order_out /* [n] or NULL */,
+                        int32_t *width, double *work /* sum_t 2^|scope_t| */, double *stored /* sum_t 2^|F_t| */);
+int gml_model_elim(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                   const int32_t *order /* or NULL */, int device, double *log_z, double *mean /* [n] or NULL */,
+                   double *texp /* [nterms] or NULL */);
+
+/*
  * gml_conditional_mode, gml_conditional_mode_masked -- the most probable JOINT completion of every row's hidden spins: s_H* = argmax
  * over the 2^h hidden states of E_k(s_H), by the enumeration of gml_conditional_exact[_masked] with the energies selected instead of
  * summed.  Not the signs of the conditional means, which decide spin by spin.
