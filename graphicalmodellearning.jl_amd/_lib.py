@@ -103,6 +103,7 @@ def lib():
     L.gml_model_best_states.argtypes = [p, i32, p, i64, i64, i64, i32, C.POINTER(i64), p, p]
     L.gml_model_elim_plan.argtypes = [p, i32, p, i64, i64, p, p, C.POINTER(C.c_int32), C.POINTER(dbl), C.POINTER(dbl)]
     L.gml_model_elim.argtypes = [p, i32, p, i64, i64, p, i32, C.POINTER(dbl), p, p]
+    L.gml_problem_create_sampled_elim.argtypes = [p, i32, p, i64, i64, i64, C.c_uint64, p, i32, i32, i64, i64, i32, C.POINTER(p)]
     L.gml_conditional_mode.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_mode_masked.argtypes = [p, i32, p, i64, i64, p, p, p, p, p]
     L.gml_conditional_draw.argtypes = [p, i32, p, i64, i64, p, p, i32, C.c_uint64, p, p, p]
@@ -459,7 +460,8 @@ class Problem:
 
     def __init__(self, samples=None, *, counts=None, spins=None, packed=None, model=None, terms=None, n=None, num_samples=None,
                  seed=0, mcmc_sweeps=None, order=2, node_range=None, device=0, ingest="host", histogram=False, burn_in=None, thin=None,
-                 samples_per_chain=None, mcmc_thin=None, mcmc_samples_per_chain=None, mcmc_betas=None, mcmc_swap_every=1):
+                 samples_per_chain=None, mcmc_thin=None, mcmc_samples_per_chain=None, mcmc_betas=None, mcmc_swap_every=1, elim=False,
+                 elim_order=None):
         """histogram=True (sampled handles, n <= 64): the handle holds the distinct configurations with their counts
         (gml_problem_create_sampled_hist: sorted and run-length encoded on the device), not one row per draw.
         burn_in / thin / samples_per_chain (with model=): num_samples // samples_per_chain Glauber chains of a pairwise model on the
@@ -471,9 +473,19 @@ class Problem:
         mcmc_betas (with terms=; needs mcmc_sweeps): replica exchange -- num_samples // mcmc_samples_per_chain ladders of
         len(mcmc_betas) rungs at these inverse temperatures (non-increasing, the first positive; 1, 2, 4 .. 64 of them), swaps
         between neighbouring rungs every mcmc_swap_every sweeps, rung 0 recorded as above (gml_problem_create_mcmc_terms_tempered).
-        The handle's swap_counts is then the (2, R - 1) int64 array of swap attempts and accepts per pair (None otherwise)."""
+        The handle's swap_counts is then the (2, R - 1) int64 array of swap attempts and accepts per pair (None otherwise).
+        elim=True (with terms=): num_samples exact, independent draws by backward sampling on the tables of variable elimination
+        (gml_problem_create_sampled_elim: sparse models of any size, elimination orders of width at most 30); elim_order: a
+        permutation of the 1-based spins, or None for the library's greedy order, as in model_elim."""
         L = lib()
         h = C.c_void_p()
+        if elim or elim_order is not None:
+            if not elim or terms is None or model is not None or samples is not None or spins is not None or packed is not None:
+                raise GMLError(GML_EINVAL, "elim / elim_order apply to a term list given as terms= (with elim=True)")
+            if mcmc_sweeps or mcmc_thin is not None or mcmc_samples_per_chain is not None or mcmc_betas is not None:
+                raise GMLError(GML_EINVAL, "elim=True draws exactly: the mcmc_ arguments do not apply")
+            if num_samples is None:
+                raise GMLError(GML_EINVAL, "elim=True needs num_samples")
         term_chains = mcmc_thin is not None or mcmc_samples_per_chain is not None or mcmc_betas is not None
         self.swap_counts = None
         if term_chains:
@@ -532,7 +544,11 @@ class Problem:
             # sample on the device from a model of any order given as {1-based key tuple: weight}: sampling.jl:60-88
             keys, wts, stride, n = term_arrays(terms, n)
             n0, n1 = _node_range(node_range, n)
-            if mcmc_betas is not None:  # replica exchange on the same chains: ladders of len(betas) rungs, rung 0 recorded
+            if elim:  # exact draws by backward sampling on the elimination's tables (sparse models of any size)
+                check(L.gml_problem_create_sampled_elim(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples), int(seed),
+                                                        _ptr(_elim_order(elim_order, int(n))), int(bool(histogram)), int(order), n0, n1,
+                                                        int(device), C.byref(h)))
+            elif mcmc_betas is not None:  # replica exchange on the same chains: ladders of len(betas) rungs, rung 0 recorded
                 betas = np.ascontiguousarray(mcmc_betas, dtype=np.float64).ravel()
                 swaps = np.zeros((2, max(len(betas) - 1, 0)), dtype=np.int64)
                 check(L.gml_problem_create_mcmc_terms_tempered(_ptr(keys), stride, _ptr(wts), len(wts), int(n), int(num_samples) // tc_spc,

@@ -1,7 +1,8 @@
 // libgml_hip, host side: exact log Z, means and term expectations by variable elimination (gml_model_elim_plan, gml_model_elim;
-// gml_elim.hip).  The planner -- adjacency of the reduced keys, the greedy order, the frontier sizes -- is plain C++
+// gml_elim.hip) and exact draws by backward sampling on the same tables (gml_problem_create_sampled_elim;
+// gml_elim_draw.hip).  The planner -- adjacency of the reduced keys, the greedy order, the frontier sizes -- is plain C++
 // and makes no HIP call; the driver turns every connected component's steps into launches (slots, scope masks, maps) and runs the
-// forward pass and, for the moments, the backward pass.
+// forward pass and then, for the moments, the backward pass or, for the draws, every sample's walk over the kept tables.
 #include "gml_elim.h"
 #include "gml_sampled.h"
 
@@ -152,12 +153,15 @@ int check_model_args(const int32_t *keys, int key_stride, const double *weights,
 // ------------------------------------------------------------------------------------------
 // One component as the kernels take it
 // ------------------------------------------------------------------------------------------
-struct Launch { // a forward launch; out_step: the step (1-based within the component) whose table it writes, -1: scratch
+struct Launch { // a forward launch; out_step: the step (1-based within the component) whose table it writes, -1: a table between
+                // the launches of one step (scratch, unless the draws keep it); out_off: that table's place in the component's store
     int kin, kout, r, nt, t_off, mv_off, nmove, out_step;
     unsigned rbit[kElimMaxRetire], same;
+    int spin[kElimMaxRetire]; // the spins at the retiring bits
+    size_t out_off;
 };
 struct Step {
-    int kin, kout, nt, t_off, mv_off, nmove, q_off, nq, first_launch, nlaunch;
+    int kin, kout, nt, t_off, mv_off, nmove, q_off, nq;
     unsigned same;
 };
 struct Component {
@@ -168,6 +172,7 @@ struct Component {
     std::vector<unsigned short> mv;
     std::vector<int64_t> q_term; // per quantity: the caller's term (>= 0) or ~spin (a mean)
     std::vector<size_t> table_off; // table_off[t]: alpha_t in the forward store (t = 0 .. steps)
+    size_t kept = 0;               // entries of the store with the tables between launches behind the alpha_t (the draws)
     int max_bits = 0, max_scratch_bits = 0;
     double log_z = 0.0;
     std::vector<double> res;
@@ -234,7 +239,6 @@ void plan_component(const ElimOrder &P, int t0, int t1, const std::vector<std::v
             }
         S.nq = (int)C.qmask.size() - S.q_off;
         // the launches: the first introduces v and adds phi; each sums out at most kElimMaxRetire of the retiring spins
-        S.first_launch = (int)C.launches.size();
         size_t done = 0;
         do {
             Launch L{};
@@ -250,16 +254,19 @@ void plan_component(const ElimOrder &P, int t0, int t1, const std::vector<std::v
                 now.push_back(p);
             }
             std::sort(now.begin(), now.end());
-            for (int i = 0; i < L.r; ++i) L.rbit[i] = 1u << now[(size_t)i];
+            for (int i = 0; i < L.r; ++i) {
+                L.rbit[i] = 1u << now[(size_t)i];
+                L.spin[i] = cur[(size_t)now[(size_t)i]];
+            }
             L.mv_off = (int)C.mv.size();
             L.same = retire_bits(cur, now, C.mv, L.nmove);
             L.kout = (int)cur.size();
             done += (size_t)L.r;
             L.out_step = done == ret.size() ? t - t0 + 1 : -1;
+            L.out_off = stored; // (alpha_t; a table between launches gets its place below)
             if (L.out_step < 0) C.max_scratch_bits = std::max(C.max_scratch_bits, L.kout);
             C.launches.push_back(L);
         } while (done < ret.size());
-        S.nlaunch = (int)C.launches.size() - S.first_launch;
         S.kout = (int)cur.size();
         // scope state -> index of the step's final table, for the backward pass
         S.mv_off = (int)C.mv.size();
@@ -276,40 +283,138 @@ void plan_component(const ElimOrder &P, int t0, int t1, const std::vector<std::v
         stored += (size_t)1 << S.kout;
         C.table_off.push_back(stored - ((size_t)1 << S.kout));
     }
+    for (Launch &L : C.launches)
+        if (L.out_step < 0) {
+            L.out_off = stored;
+            stored += (size_t)1 << L.kout;
+        }
+    C.kept = stored;
+}
+
+// The whole model: the terms by the step of their last spin, in the caller's order (an empty key is a constant of log Z: its weight goes
+// to `constants`); the components that need the device, in order; the spins in no term.
+void plan_components(const ElimOrder &P, const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n,
+                     std::vector<Component> &comps, std::vector<int> &free_spins, std::vector<double> &constants) {
+    std::vector<std::vector<int64_t>> step_terms((size_t)n);
+    std::vector<int> sp;
+    for (int64_t t = 0; t < nterms; ++t) {
+        if (weights[t] == 0.0) continue;
+        reduce_key(keys + t * key_stride, key_stride, sp);
+        if (sp.empty()) {
+            constants.push_back(weights[t]);
+            continue;
+        }
+        int at = 0;
+        for (int u : sp) at = std::max(at, P.pos[(size_t)u]);
+        step_terms[(size_t)at].push_back(t);
+    }
+    for (size_t c = 0, t0 = 0; c < P.comp_end.size(); t0 = (size_t)P.comp_end[c++]) {
+        if ((size_t)P.comp_end[c] == t0 + 1 && step_terms[t0].empty()) {
+            free_spins.push_back(P.seq[t0]);
+            continue;
+        }
+        comps.emplace_back();
+        plan_component(P, (int)t0, P.comp_end[c], step_terms, keys, key_stride, weights, comps.back());
+    }
+}
+
+// the entries of the tables between the launches of one step, over the whole order (what the draws keep beyond `stored`): a step of
+// scope k that retires R > 3 spins leaves tables of k - 3, k - 6, ... bits before its last launch
+double entries_between_launches(const ElimOrder &P) {
+    std::vector<int> retiring(P.seq.size(), 0);
+    for (int l : P.last) ++retiring[(size_t)l];
+    double extra = 0.0;
+    int F = 0;
+    for (size_t t = 0; t < P.seq.size(); ++t) {
+        for (int done = kElimMaxRetire; done < retiring[t]; done += kElimMaxRetire) extra += std::ldexp(1.0, F + 1 - done);
+        F += 1 - retiring[t];
+    }
+    return extra;
 }
 
 ElimMap map_of(const unsigned short *dmv, int off, int nmove, unsigned same) { return ElimMap{same, nmove, dmv + off}; }
 
-// All components of a call on one stream: their terms, quantities and moves uploaded together, the tables sized for the largest
-// component and used by one after the other (the stream orders them), every component's alpha_n kept on the device for its backward
-// pass, and one synchronisation at the end.
+// What the launches of a call read, uploaded once: the terms and moves of all components in one array each; t0, q0, mv0: where
+// component c starts in them (q0: in the quantities, which only the moments upload).  The host arrays live here until the caller has
+// synchronised.
+struct Uploaded {
+    const unsigned *tmask = nullptr;
+    const double *tw = nullptr;
+    const unsigned short *mv = nullptr;
+    std::vector<size_t> t0, q0, mv0;
+    std::vector<unsigned> h_tmask, qmask;
+    std::vector<double> h_tw;
+    std::vector<unsigned short> h_mv;
+    std::vector<ElimDrawLaunch> h_launches; // (the draws: the launch records, and the moves again as 32-bit words)
+    std::vector<unsigned> h_mv32;
+};
+
+void upload_components(SamplerStaging &s, const std::vector<Component> &comps, Uploaded &U) {
+    std::vector<unsigned> &tmask = U.h_tmask;
+    std::vector<double> &tw = U.h_tw;
+    std::vector<unsigned short> &mv = U.h_mv;
+    mv.assign(1, 0); // (no empty upload)
+    for (const Component &C : comps) {
+        U.t0.push_back(tmask.size());
+        U.q0.push_back(U.qmask.size());
+        U.mv0.push_back(mv.size());
+        tmask.insert(tmask.end(), C.tmask.begin(), C.tmask.end());
+        tw.insert(tw.end(), C.tw.begin(), C.tw.end());
+        U.qmask.insert(U.qmask.end(), C.qmask.begin(), C.qmask.end());
+        mv.insert(mv.end(), C.mv.begin(), C.mv.end());
+    }
+    U.tmask = s.upload(tmask);
+    U.tw = s.upload(tw);
+    U.mv = s.upload(mv);
+}
+
+// The forward pass of component c on the stream: alpha_0 = 0 at alpha0, then its launches in order, each writing where place(L) says.
+// Returns the place of alpha_n.
+template <class Place> const double *run_forward(SamplerStaging &s, const Uploaded &U, const Component &C, size_t c, double *alpha0, Place &&place) {
+    const unsigned *dtm = U.tmask + U.t0[c];
+    const double *dtw = U.tw + U.t0[c];
+    const unsigned short *dmv = U.mv + U.mv0[c];
+    s.ok(hipMemsetAsync(alpha0, 0, sizeof(double), s.st), "hipMemsetAsync");
+    const double *in = alpha0;
+    for (const Launch &L : C.launches) {
+        double *out = place(L);
+        ElimForward A{};
+        A.in = in;
+        A.out = out;
+        A.tmask = dtm + L.t_off;
+        A.tw = dtw + L.t_off;
+        A.nt = L.nt;
+        A.map = map_of(dmv, L.mv_off, L.nmove, L.same);
+        for (int i = 0; i < kElimMaxRetire; ++i) A.rbit[i] = L.rbit[i];
+        A.kin = L.kin;
+        A.kout = L.kout;
+        launch_elim_forward(A, L.r, s.st);
+        in = out;
+    }
+    return in;
+}
+
+// log Z and the moments.  All components of a call on one stream: their terms, quantities and moves uploaded together, the tables sized
+// for the largest component and used by one after the other (the stream orders them), every component's alpha_n kept on the device for
+// its backward pass, and one synchronisation at the end.
 int run_components(std::vector<Component> &comps, bool moments, int device) {
     if (comps.empty()) return GML_OK;
     SamplerStaging s;
     if (int rc = s.open(device)) return rc;
-    std::vector<unsigned> tmask, qmask;
-    std::vector<double> tw;
-    std::vector<unsigned short> mv(1, 0); // (no empty upload)
-    std::vector<size_t> t0, q0s, mv0;
+    Uploaded U;
+    upload_components(s, comps, U);
+    const std::vector<size_t> &q0s = U.q0;
     int max_bits = 0, max_scratch_bits = 0;
     size_t max_store = 0;
     for (const Component &C : comps) {
-        t0.push_back(tmask.size());
-        q0s.push_back(qmask.size());
-        mv0.push_back(mv.size());
-        tmask.insert(tmask.end(), C.tmask.begin(), C.tmask.end());
-        tw.insert(tw.end(), C.tw.begin(), C.tw.end());
-        qmask.insert(qmask.end(), C.qmask.begin(), C.qmask.end());
-        mv.insert(mv.end(), C.mv.begin(), C.mv.end());
         max_bits = std::max(max_bits, C.max_bits);
         max_scratch_bits = std::max(max_scratch_bits, C.max_scratch_bits);
         max_store = std::max(max_store, C.table_off.back() + 1);
     }
-    const unsigned *dtm_all = s.upload(tmask), *dqm_all = s.upload(qmask);
-    const double *dtw_all = s.upload(tw);
-    const unsigned short *dmv_all = s.upload(mv);
-    // forward tables: with the moments every alpha_t is kept; without, two tables take turns
-    const size_t big = (size_t)1 << max_bits, scratch = (size_t)1 << max_scratch_bits, nq_all = qmask.size();
+    const unsigned *dqm_all = s.upload(U.qmask);
+    // forward tables: with the moments every alpha_t is kept; without, two tables take turns; the tables between the launches of one
+    // step take turns in either case
+    const size_t big = (size_t)1 << max_bits, scratch = (size_t)1 << max_scratch_bits, nq_all = U.qmask.size();
     const size_t wgs_max = std::max<size_t>(1, big / kElimChunk);
     double *store = nullptr, *ping[2] = {nullptr, nullptr}, *tmp[2], *beta[2] = {nullptr, nullptr}, *part[2] = {nullptr, nullptr};
     double *dres = nullptr;
@@ -330,33 +435,15 @@ int run_components(std::vector<Component> &comps, bool moments, int device) {
     if (s.rc) return s.rc;
     for (size_t c = 0; c < comps.size() && s.rc == GML_OK; ++c) {
         const Component &C = comps[c];
-        const unsigned *dtm = dtm_all + t0[c], *dqm = dqm_all + q0s[c];
-        const double *dtw = dtw_all + t0[c];
-        const unsigned short *dmv = dmv_all + mv0[c];
+        const unsigned *dtm = U.tmask + U.t0[c], *dqm = dqm_all + q0s[c];
+        const double *dtw = U.tw + U.t0[c];
+        const unsigned short *dmv = U.mv + U.mv0[c];
         const size_t nsteps = C.steps.size();
-        double *alpha0 = moments ? store : ping[0];
-        s.ok(hipMemsetAsync(alpha0, 0, sizeof(double), s.st), "hipMemsetAsync"); // alpha_0 = 0
-        const double *in = alpha0;
         int turn = 0, tturn = 0;
-        for (size_t t = 0; t < nsteps; ++t)
-            for (int l = 0; l < C.steps[t].nlaunch; ++l) {
-                const Launch &L = C.launches[(size_t)(C.steps[t].first_launch + l)];
-                double *out;
-                if (L.out_step < 0) out = tmp[tturn ^= 1];
-                else out = moments ? store + C.table_off[(size_t)L.out_step] : ping[turn ^= 1];
-                ElimForward A{};
-                A.in = in;
-                A.out = out;
-                A.tmask = dtm + L.t_off;
-                A.tw = dtw + L.t_off;
-                A.nt = L.nt;
-                A.map = map_of(dmv, L.mv_off, L.nmove, L.same);
-                for (int i = 0; i < kElimMaxRetire; ++i) A.rbit[i] = L.rbit[i];
-                A.kin = L.kin;
-                A.kout = L.kout;
-                launch_elim_forward(A, L.r, s.st);
-                in = out;
-            }
+        const double *in = run_forward(s, U, C, c, moments ? store : ping[0], [&](const Launch &L) {
+            if (L.out_step < 0) return tmp[tturn ^= 1];
+            return moments ? store + L.out_off : ping[turn ^= 1];
+        });
         s.ok(hipMemcpyAsync(dlogz + c, in, sizeof(double), hipMemcpyDeviceToDevice, s.st), "hipMemcpyAsync"); // alpha_n
         if (!moments) continue;
         // backward: beta_n = 0; step t reads beta_t and writes beta_{t-1}, whether or not it has quantities to sum; the quantities
@@ -404,6 +491,63 @@ int run_components(std::vector<Component> &comps, bool moments, int device) {
     return GML_OK;
 }
 
+// The draws, into the output bytes of a begun staging (spin-major, leading dimension ld).  Every table of every component is kept --
+// the store holds the components one behind the other -- so one kernel can walk all launches backward for every sample; then the
+// spins in no term.  All on the staging's stream: no host round trip between the components, the synchronisation is finish()'s (U and
+// free_spins hold the host side of the uploads until then).
+void draw_components(SamplerStaging &s, const std::vector<Component> &comps, Uploaded &U, const std::vector<int> &free_spins, uint64_t seed,
+                     int64_t N, int64_t ld) {
+    if (!comps.empty()) {
+        upload_components(s, comps, U);
+        std::vector<size_t> base;
+        size_t total = 0;
+        for (const Component &C : comps) {
+            base.push_back(total);
+            total += C.kept;
+        }
+        double *store = s.alloc<double>(total);
+        std::vector<ElimDrawLaunch> &recs = U.h_launches;
+        for (size_t c = 0; c < comps.size() && s.rc == GML_OK; ++c) {
+            const Component &C = comps[c];
+            double *mine = store + base[c];
+            run_forward(s, U, C, c, mine, [&](const Launch &L) { return mine + L.out_off; });
+            size_t in_off = base[c]; // alpha_0
+            for (const Launch &L : C.launches) {
+                ElimDrawLaunch D{};
+                D.in_off = (long long)in_off;
+                D.t_off = (long long)(U.t0[c] + (size_t)L.t_off);
+                D.same = L.same;
+                for (int i = 0; i < kElimMaxRetire; ++i) {
+                    D.rbit[i] = L.rbit[i];
+                    D.spin[i] = L.spin[i];
+                }
+                D.kin = L.kin;
+                D.r = L.r;
+                D.nt = L.nt;
+                D.mv_off = (int)(U.mv0[c] + (size_t)L.mv_off);
+                D.nmove = L.nmove;
+                recs.push_back(D);
+                in_off = base[c] + L.out_off;
+            }
+        }
+        ElimDraw D{};
+        D.launches = s.upload(recs);
+        D.nlaunch = (int)recs.size();
+        D.store = store;
+        D.tmask = U.tmask;
+        D.tw = U.tw;
+        U.h_mv32.assign(U.h_mv.begin(), U.h_mv.end());
+        D.mv = s.upload(U.h_mv32);
+        D.seed = seed;
+        D.N = N;
+        D.ld = ld;
+        D.out = s.out;
+        if (s.rc == GML_OK) launch_elim_draw(D, s.st);
+    }
+    const int *dfree = free_spins.empty() ? nullptr : s.upload(free_spins);
+    if (s.rc == GML_OK) launch_elim_draw_free(dfree, (int)free_spins.size(), seed, N, ld, s.out, s.st);
+}
+
 double pairwise_sum(const double *v, size_t count) { // at most 1024 summands serially into one accumulator
     if (count <= 1024) {
         double s = 0.0;
@@ -438,32 +582,12 @@ extern "C" int gml_model_elim(const int32_t *keys, int key_stride, const double 
         return fail(GML_EUNSUPPORTED, "the elimination order has width %d: variable elimination is limited to %d", P.width, GML_ELIM_MAX_WIDTH);
     if (moments && P.stored > std::ldexp(1.0, 32))
         return fail(GML_EUNSUPPORTED, "the moments need %.3g forward table entries: at most 2^32 (32 GiB) are stored", P.stored);
-    // the terms by the step of their last spin, in the caller's order; the empty key is a constant of log Z
-    std::vector<std::vector<int64_t>> step_terms((size_t)n);
-    std::vector<double> parts;
-    std::vector<int> sp;
-    for (int64_t t = 0; t < nterms; ++t) {
-        if (weights[t] == 0.0) continue;
-        reduce_key(keys + t * key_stride, key_stride, sp);
-        if (sp.empty()) {
-            parts.push_back(weights[t]);
-            continue;
-        }
-        int at = 0;
-        for (int u : sp) at = std::max(at, P.pos[(size_t)u]);
-        step_terms[(size_t)at].push_back(t);
-    }
     // a spin in no term needs no device: ln 2, mean 0
     std::vector<Component> comps;
-    int64_t nfree = 0;
-    for (size_t c = 0, t0 = 0; c < P.comp_end.size(); t0 = (size_t)P.comp_end[c++]) {
-        if ((size_t)P.comp_end[c] == t0 + 1 && step_terms[t0].empty()) {
-            ++nfree;
-            continue;
-        }
-        comps.emplace_back();
-        plan_component(P, (int)t0, P.comp_end[c], step_terms, keys, key_stride, weights, comps.back());
-    }
+    std::vector<int> free_spins, sp;
+    std::vector<double> parts;
+    plan_components(P, keys, key_stride, weights, nterms, n, comps, free_spins, parts);
+    const int64_t nfree = (int64_t)free_spins.size();
     if (int rc = gml_check_device(device)) return rc;
     std::vector<double> m((size_t)n, 0.0);
     if (texp)
@@ -487,4 +611,34 @@ extern "C" int gml_model_elim(const int32_t *keys, int key_stride, const double 
             else if (weights[t] == 0.0 && sp.size() == 1) texp[t] = m[(size_t)sp[0]];
         }
     return GML_OK;
+}
+
+extern "C" int gml_problem_create_sampled_elim(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t N,
+                                               uint64_t seed, const int32_t *order, int histogram, int porder, int64_t node0, int64_t node1,
+                                               int device, gml_problem **out) {
+    if (int rc = check_out(out)) return rc;
+    if (int rc = check_model_args(keys, key_stride, weights, nterms, n)) return rc;
+    if (int rc = gml_check_handle_args(n, porder, node0, node1)) return rc;
+    if (N < 1 || N > (int64_t)1 << 40) return fail(GML_EINVAL, "N must lie in [1, 2^40] (given %lld)", (long long)N);
+    ElimOrder P;
+    if (int rc = plan_order(keys, key_stride, weights, nterms, n, order, P)) return rc;
+    if (P.width > GML_ELIM_MAX_WIDTH)
+        return fail(GML_EUNSUPPORTED, "the elimination order has width %d: variable elimination is limited to %d", P.width, GML_ELIM_MAX_WIDTH);
+    const double kept = P.stored + entries_between_launches(P);
+    if (kept > std::ldexp(1.0, 32))
+        return fail(GML_EUNSUPPORTED, "the draws need %.3g kept table entries: at most 2^32 (32 GiB) are stored", kept);
+    if (n > 16384) return fail(GML_EUNSUPPORTED, "the draws by elimination support n <= 16384 spins (n = %lld)", (long long)n);
+    if (histogram)
+        if (int rc = check_hist_limits(n, N)) return rc;
+    std::vector<Component> comps;
+    std::vector<int> free_spins;
+    std::vector<double> constants; // (the empty keys: no part of a draw)
+    plan_components(P, keys, key_stride, weights, nterms, n, comps, free_spins, constants);
+    if (int rc = gml_check_device(device)) return rc;
+    const int64_t ld = gml_round_up(N, 256);
+    Uploaded U;
+    SamplerStaging s;
+    if (int rc = s.begin(device, N, n, porder, node0, node1, (size_t)n * (size_t)ld, true)) return rc;
+    draw_components(s, comps, U, free_spins, seed, N, ld);
+    return s.finish(true, ld, histogram != 0, out);
 }

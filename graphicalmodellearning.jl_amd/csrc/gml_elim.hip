@@ -11,23 +11,6 @@
 
 namespace gml {
 
-__device__ __forceinline__ unsigned elim_scope_of(unsigned j, const ElimMap &m) {
-    unsigned s = j & m.same;
-    for (int i = 0; i < m.nmove; ++i) {
-        const unsigned mv = m.mv[i];
-        s |= ((j >> (mv & 255u)) & 1u) << (mv >> 8);
-    }
-    return s;
-}
-__device__ __forceinline__ unsigned elim_index_of(unsigned s, const ElimMap &m) {
-    unsigned j = s & m.same;
-    for (int i = 0; i < m.nmove; ++i) {
-        const unsigned mv = m.mv[i];
-        j |= ((s >> (mv >> 8)) & 1u) << (mv & 255u);
-    }
-    return j;
-}
-
 // phi[c] += the signed weights of the step's terms at the scope states s[c]; the terms in list order, staged in LDS tile by tile
 template <int C>
 __device__ __forceinline__ void elim_phi(const unsigned *__restrict__ tmask, const double *__restrict__ tw, int nt, const unsigned (&s)[C],
@@ -60,15 +43,9 @@ template <int R> __global__ __launch_bounds__(256) void k_elim_forward(const Eli
     const unsigned base = elim_scope_of(live ? j : 0u, S.map);
     unsigned s[C];
     double x[C];
+    elim_candidates<R>(base, S.rbit, s);
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        unsigned v = base;
-#pragma unroll
-        for (int i = 0; i < R; ++i)
-            if (c >> i & 1) v |= S.rbit[i];
-        s[c] = v;
-        x[c] = 0.0;
-    }
+    for (int c = 0; c < C; ++c) x[c] = 0.0;
     elim_phi<C>(S.tmask, S.tw, S.nt, s, x, lm, lw);
     if (!live) return;
     const unsigned inmask = (1u << S.kin) - 1u;

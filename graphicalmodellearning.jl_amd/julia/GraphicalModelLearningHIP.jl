@@ -571,6 +571,39 @@ function model_elim(terms::Dict, n::Integer; order=nothing, device::Integer=0)
     return log_z[], mean, texp
 end
 
+"""
+    sample_elim(terms::Dict, n, N; seed=0, order=nothing, device=0) -> counts (K), spins (K x n, +-1)
+
+`N` exact, independent draws of a sparse model of `n` spins by backward sampling on the tables of variable elimination
+(gml_problem_create_sampled_elim, include/gml.h): elimination orders of width at most 30, no chain and no burn-in.  For n <= 64 and
+N < 2^31 the distinct configurations with their counts (histogrammed on the device), otherwise one row of count 1 per draw.
+Marshalling only.
+"""
+function sample_elim(terms::Dict, n::Integer, N::Integer; seed::Integer=0, order=nothing, device::Integer=0)
+    keymat, weights, stride = term_arrays(terms)
+    porder = max(2, maximum(length, keys(terms)))
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:gml_problem_create_sampled_elim, libgml), Cint,
+               (Ptr{Int32}, Cint, Ptr{Cdouble}, Int64, Int64, Int64, UInt64, Ptr{Int32}, Cint, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+               keymat, stride, weights, length(weights), n, N, seed, elim_order(order, n), (n <= 64 && N < 2^31) ? 1 : 0, porder, 0, n,
+               device, handle)
+    rc == GML_OK || error("gml_problem_create_sampled_elim: $(lasterr())")
+    try
+        K = Ref{Int64}(0)
+        ccall((:gml_problem_info, libgml), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ref{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+              handle[], C_NULL, K, C_NULL, C_NULL, C_NULL, C_NULL)
+        rows = Matrix{Int8}(undef, n, K[])  # (the library writes row-major [K][n])
+        counts = Vector{Float64}(undef, K[])
+        rc = ccall((:gml_problem_get_spins, libgml), Cint, (Ptr{Cvoid}, Ptr{Int8}), handle[], rows)
+        rc == GML_OK || error("gml_problem_get_spins: $(lasterr())")
+        rc = ccall((:gml_problem_get_counts, libgml), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), handle[], counts)
+        rc == GML_OK || error("gml_problem_get_counts: $(lasterr())")
+        return counts, permutedims(rows)
+    finally
+        ccall((:gml_problem_destroy, libgml), Cvoid, (Ptr{Cvoid},), handle[])
+    end
+end
+
 # all nodes over method.devices: gml_multi_* (one handle + one host thread per GPU inside the library)
 function solve_rows_multi(s, dtype, formulation, method::HIP, order::Int)
     K, n = size(s, 1), size(s, 2) - 1

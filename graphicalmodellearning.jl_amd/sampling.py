@@ -3,7 +3,9 @@ the on-device exact sampler (gml_problem_create_sampled / _sampled_terms).  Any 
 connected component of the term hypergraph must have at most 22 spins (the reference enumerates all 2^n
 states of the whole model, which limits it to n ~ 25).  Beyond that, Markov chains on the device: Glauber (one sample per
 chain), GlauberChains (long thinned chains of dense pairwise models), GlauberTermChains (long thinned chains of any term
-list) and TemperedTermChains (replica exchange on those, for models with more than one deep well)."""
+list) and TemperedTermChains (replica exchange on those, for models with more than one deep well).  Sparse models of any size --
+lattices, Chimera graphs, trees, l1 solutions -- need no chain: Elimination() (the class of likelihood.py) draws exactly and
+independently by backward sampling on the tables of variable elimination (gml_problem_create_sampled_elim)."""
 import numpy as np
 
 from . import _lib
@@ -100,7 +102,10 @@ def _check_whole_chains(number_sample, sampler):
 
 def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, device=0):
     """sample(gm, N) -> histogram matrix [count, s_1..s_n], one row per observed configuration
-    (sampling.jl:52-54); sample(gm, N, replicates) -> list of such matrices (:91)."""
+    (sampling.jl:52-54); sample(gm, N, replicates) -> list of such matrices (:91).  sampler: None or Gibbs() for exact enumeration, one
+    of the chain samplers above, or an Elimination for exact draws of a sparse model (planned on the host first: ValueError where the
+    order is wider than its max_width)."""
+    from .likelihood import Elimination, _check_elimination  # (likelihood.py imports this module)
     args = _problem_args(model)
     if isinstance(sampler, GlauberChains):
         if "model" not in args:
@@ -119,6 +124,10 @@ def sample(model, number_sample, replicates=None, sampler=None, *, seed=0, devic
     elif isinstance(sampler, Glauber):
         args = _term_list_args(model, args)
         args["mcmc_sweeps"] = sampler.sweeps
+    elif isinstance(sampler, Elimination):
+        args = _term_list_args(model, args)
+        _check_elimination(sampler, args["terms"], args.get("n"))
+        args.update(elim=True, elim_order=sampler.order)
     reps = 1 if replicates is None else int(replicates)
     nspins = args["model"].shape[0] if "model" in args else args["n"] if "n" in args else max(max(k) for k in args["terms"] if len(k))
     out = []

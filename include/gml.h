@@ -611,6 +611,54 @@ int gml_model_elim(const int32_t *keys, int key_stride, const double *weights, i
                    double *texp /* [nterms] or NULL */);
 
 /*
+ * gml_problem_create_sampled_elim -- N exact, independent draws of a SPARSE term list of any number of spins into a resident handle,
+ * by backward sampling on the tables of gml_model_elim: no chain, no burn-in.  Where gml_problem_create_sampled_terms refuses a
+ * component of more than 22 spins, this one asks for an elimination order of width at most GML_ELIM_MAX_WIDTH.
+ * Model, order, plan.  Exactly those of gml_model_elim: the conventions of the keys, the components in the order of their smallest
+ *   spin, the caller's permutation or the greedy order, a term applied at the step of its last spin.
+ * Tables.  A table over a frontier of k spins has 2^k entries; bit b of an index set <=> the spin in slot b is -1.  The scope of a
+ *   step: the slots of its input table plus, at bit k, the spin the step introduces.  A step whose retiring spins number R is run as
+ *   max(1, ceil(R / 3)) launches: the first introduces the spin and adds phi (the signed weights of the step's terms in the caller's
+ *   order, summed from 0.0 in FP64), each sums out the at most 3 retiring spins of lowest scope position that are left.  Slot rule of
+ *   a launch's output table: the surviving bits below the new size keep their place; the others fill the freed bits in ascending
+ *   order.  scope_of(j): the scope state whose surviving bits are those of output index j, the retiring bits 0.
+ *   out[j] = logsumexp over the retiring bits of (in[s & inmask] + phi(s)), inmask = 2^kin - 1: the forward pass of gml_model_elim
+ *   with moments, which keeps every step's table; here the tables between the launches of one step are kept too.
+ * Launch numbers.  The forward launches of the whole call are numbered 0, 1, 2, ...: the components in their order, the launches of
+ *   a component in forward order.  A component of a single spin with a field is a launch like any other.
+ * The draw.  Sample k walks the launches from the last to the first and carries one table index j: the entry of the launch's output
+ *   table that the spins drawn so far select.  The last launch of a component writes one entry: j = 0.  At launch l with r retiring
+ *   bits rbit[0] < ... < rbit[r-1]:
+ *     candidates  c = 0 .. 2^r - 1 in ascending order, bit i of c <-> rbit[i]; s_c = scope_of(j) | the bits of c;
+ *                 x_c = in[s_c & inmask] + phi(s_c), the expression, the term order and the bits of the forward pass
+ *     weights     m = max_c x_c; p_c = exp(x_c - m); total = p_0 + ... + p_{2^r - 1}, summed in that order
+ *     number      u = u01(seed, l, k) of gml_rng.h (stream = the launch number, counter = the sample)
+ *     pick        the smallest c with p_0 + ... + p_c > u * total (the running sum of the total); the last c if rounding leaves none
+ *     result      retiring spin i is -1 iff bit i of the picked c is set; the index for launch l - 1 is s_c & inmask
+ *   A launch with r = 0 draws nothing, consumes no number and maps the index: j <- scope_of(j) & inmask.
+ *   A spin i in no term (of non-zero weight) is +1 iff u01(seed, 2^62 + i, k) < 0.5.
+ * Exactness.  The product of the picked p_c / total along a walk telescopes to exp(E(s) - log Z): the draws are exact and
+ *   independent up to FP64 rounding of the tables (the error of gml_model_elim) and the 53 bits of u per launch.  The limit: a
+ *   candidate whose p_c is below about 2^-53 of its launch's total is never drawn.
+ * Determinism.  Row k is a pure function of (model, order, seed, k): not of N, the grid, `histogram` or the device.  The same
+ *   arguments give the same bytes.
+ * Handle.  porder, node0, node1, histogram: those of gml_problem_create_mcmc_terms_chains.  N rows of count 1, M = N; with
+ *   histogram != 0 the distinct configurations with their counts (n <= 64, N < 2^31).
+ * GML_EINVAL, before any HIP call, in this order: out NULL; NULL keys or weights with nterms > 0, key_stride < 1; n < 1 or
+ *   nterms < 0; a spin outside [0, n) or a non-finite weight; porder outside [1, 8] or a bad node range; N outside [1, 2^40]; order not a
+ *   permutation of 0 .. n - 1.  GML_EUNSUPPORTED, before any HIP call, the limit named in gml_last_error, in this order: a width above
+ *   GML_ELIM_MAX_WIDTH; more than 2^32 kept table entries (`stored` of gml_model_elim_plan plus the tables between the launches of
+ *   one step); n > 16384; histogram with n > 64 or N >= 2^31.  The device is looked for last.  GML_ENOMEM: the device cannot hold
+ *   the tables and the n x N output bytes.
+ * Cost.  The forward pass once per call, whatever N is; then per sample one read of every launch record and term of the model and
+ *   2^r table entries per launch.  All on one stream with one synchronisation before the handle is built.  Measured times in
+ *   DESIGN 3.23.  Everything but the handle is released before the call returns.
+ */
+int gml_problem_create_sampled_elim(const int32_t *keys, int key_stride, const double *weights, int64_t nterms, int64_t n, int64_t N,
+                                    uint64_t seed, const int32_t *order /* [n] or NULL: greedy */, int histogram, int porder,
+                                    int64_t node0, int64_t node1, int device, gml_problem **out);
+
+/*
  * gml_conditional_mode, gml_conditional_mode_masked -- the most probable JOINT completion of every row's hidden spins: s_H* = argmax
  * over the 2^h hidden states of E_k(s_H), by the enumeration of gml_conditional_exact[_masked] with the energies selected instead of
  * summed.  Not the signs of the conditional means, which decide spin by spin.
